@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: HMSG build (frames/s) + retrieval (queries/s) on synthetic posed RGB-D.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json configs[1]): one 1000-frame 640x480 scene per GPU, 32 masks/frame, 512-d
 features, build A1..A7 + node table + 1000 hierarchical object queries.  A "step" is one full pass of
@@ -9,9 +9,15 @@ the hot path over that scene (reset -> frames -> map -> fuse -> merge -> pool ->
 the inputs already resident in HBM.  N>1: one scene per rank (weak scaling), node tables all-gathered
 over RCCL for cross-scene retrieval, every rank answers Q/N of the queries on the global table.
 
-Prints ONE JSON line (rank 0): the driver contract + `roofline` (dominant kernel, HIP-event timed on
-the library's own stream) + `cpu_baseline` (the numpy/scipy/sklearn oracle on a bounded sample of the
-same frames, N=1 only).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the driver contract
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, stage times).  `--full` adds everything else:
+`roofline` (dominant kernel, HIP-event timed on the library's own stream in the last timed step) and the per-kernel
+figures, the resident-index retrieval leg, scenes in flight, rooms handed in, the encoder hand-off leg and
+`cpu_baseline` (the compiled CPU restatement on a bounded sample of the same frames, N=1 only).
+
+`--dump-outputs DIR` writes what the timed path handed its caller in the last timed step (retrieval answers, node
+table, graph records, a fixed sample of the map) as float32 / float64 .npy files; the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -84,10 +90,57 @@ def assign_rooms(boxes, rooms):
     return rid.astype(np.int32)
 
 
+DUMP_MAX_BYTES = 64 << 20          # --dump-outputs: all files together
+DUMP_ARRAY_BYTES = 5 << 20         # one array; larger ones keep a fixed, evenly spaced sample of their rows
+
+
+def dump_outputs(out_dir, sc, state):
+    """--dump-outputs: what the last timed step handed its caller -- the retrieval answers, the node table the answers
+    index, the graph's records and the map -- as <out_dir>/<name>.npy in float64 (float32 for the float32 embeddings)."""
+    from holoagent_amd._lib import SceneGraph
+    arrays = {}
+    last = state.get("last")
+    if last is not None:
+        for name, a in zip(("query_idx", "query_room", "query_score"), last):
+            arrays[name] = a
+    sel = state.get("sel")
+    if sel is not None:
+        packed = np.full((len(sel), max([len(s_) for s_ in sel] + [1])), -1.0)   # (ragged: -1 pads a query's room list)
+        for q, s_ in enumerate(sel):
+            packed[q, : len(s_)] = s_
+        arrays["query_rooms_selected"] = packed
+    recs, emb = sc.nodes(embeddings=True)
+    arrays["node_records"] = np.stack([recs[f] for f in recs.dtype.names], 1)       # instance, floor, room, counter, label, n_points
+    arrays["node_embeddings"] = emb
+    g = state.get("graph")
+    if isinstance(g, SceneGraph):
+        cnt = g.counts()
+        arrays["graph_counts"] = np.array([cnt[f] for f in ("floors", "rooms", "views", "objects", "edges", "view_object_links")])
+        arrays["graph_edges"] = g.edges()
+        arrays["graph_objects"] = np.array([[o[f] for f in ("room", "instance", "label", "n_views", "best_view")] for o in g.objects()]
+                                           ).reshape(-1, 5)
+        arrays["graph_rooms"] = np.array([[r[f] for f in ("floor", "n_vertices", "n_points", "n_embeddings", "n_objects", "n_views")]
+                                          for r in g.rooms()]).reshape(-1, 6)
+    if sc.map_size():
+        xyz = sc.map_points()
+        arrays["map_points"] = xyz[np.lexsort(xyz.T[::-1])]     # (sorted by x, y, z: a sample that does not depend on the map's order)
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+        row_bytes = max(a[:1].nbytes, 1) if a.ndim else a.nbytes
+        if a.ndim and a.nbytes > DUMP_ARRAY_BYTES:
+            a = a[np.linspace(0, len(a) - 1, max(DUMP_ARRAY_BYTES // row_bytes, 1)).astype(np.int64)]
+        total += a.nbytes
+        assert total <= DUMP_MAX_BYTES
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2)
+    ap.add_argument("--steps", type=int, default=2, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=2,
                     help="untimed steps (2: the library's per-thread device allocator cache settles over the first two scenes -- a "
                          "service that builds scene after scene runs in that state)")
@@ -123,14 +176,23 @@ def main():
     ap.add_argument("--encoder-frames", type=int, default=8,
                     help="frames of the extra encoder hand-off leg (random-init ViT-B/32-shaped PyTorch-ROCm module -> features by "
                          "data_ptr() into hmsg_add_frame_features; reported beside `value`, never in it; 0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: per-kernel / roofline figures of the last timed step, the resident-index "
+                         "retrieval leg, scenes in flight, rooms handed in, the encoder hand-off leg and the CPU baseline (off: a plain run "
+                         "sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (retrieval answers, node table, graph "
+                         "records, a fixed sample of the map) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     ap.add_argument("--no-extras", action="store_true",
-                    help="only the timed steps: no CPU baseline, scenes-in-flight, rooms-handed-in or encoder hand-off legs (profiler passes)")
+                    help="with --full: no CPU baseline, scenes-in-flight, rooms-handed-in or encoder hand-off legs")
     ap.add_argument("--scene-shape", default=None,
                     help="development sizes (the simulator test): ROOMS_X,ROOMS_Z,ROOM_X_M,ROOM_Y_M,ROOM_Z_M,YAW_STEP_DEG,OBJECTS_PER_ROOM of "
                          "the synthetic building instead of configs[1]'s 4 x 2 rooms of 5 x 3 x 4 m, 10 degrees a frame, 8 objects a room")
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # `python bench.py --gpus N` (N > 1) without a launcher: become the launcher -- one process per GPU under
     # torch.distributed.run on 127.0.0.1, same arguments; rank 0's JSON line is the output.
@@ -335,6 +397,7 @@ def main():
                     sel, idx, room, score = ix.query_hier(text, np.zeros(len(text), np.int32), room_text, np.zeros(len(text), np.int32),
                                                           np.ones(len(text), np.int32), k)
                     state["gemm"] = ix.profile()
+                    state["sel"] = sel
                     ix.close()
                     return idx, room, score
                 state["last"] = T("retrieval", retrieve)
@@ -445,6 +508,7 @@ def main():
             sel, idx, room, score = g_ix.query_hier(tq, np.zeros(len(qs), np.int32), tr, fl, np.ones(len(qs), np.int32), k,
                                                     max_rooms=max(n_rooms_g, 10))
             state["gemm"] = g_ix.profile()
+            state["sel"] = sel
             state["rooms_hit"] = float(np.mean([int(ent_room[q_ent[q]]) in {gt_of[j] for j in s_} for q, s_ in zip(qs, sel)])) if len(qs) else None
             state["graph_counts"] = dict(floors=cnt["floors"], rooms=cnt["rooms"], views=cnt["views"], objects=cnt["objects"],
                                          view_object_edges=int(cnt["view_object_links"]))
@@ -498,6 +562,7 @@ def main():
                 sel, idx, room, score = ix.query_hier(tq, np.zeros(len(tq), np.int32), room_text, np.zeros(len(tq), np.int32),
                                                       np.ones(len(tq), np.int32), k)
                 state["gemm"] = ix.profile()
+                state["sel"] = sel
                 state["rooms_hit"] = float(np.mean([int(ent_room[e]) in {gt_of[j] for j in s_} for e, s_ in zip(q_ent, sel)]))
                 cnt = cg.counts()
                 state["graph_counts"] = dict(floors=cnt["floors"], rooms=cnt["rooms"], views=cnt["views"], objects=cnt["objects"],
@@ -519,6 +584,7 @@ def main():
                 sel, idx, room, score = ix.query_hier(tq, np.zeros(len(tq), np.int32), room_text, np.zeros(len(tq), np.int32),
                                                       np.ones(len(tq), np.int32), k)
                 state["gemm"] = ix.profile()
+                state["sel"] = sel
                 state["rooms_hit"] = float(np.mean([int(ent_room[e]) in {gt_of[j] for j in s_} for e, s_ in zip(q_ent, sel)]))
                 state["graph_counts"] = dict(floors=len(g.floors), rooms=len(g.rooms), views=len(g.views), objects=len(g.objects),
                                              view_object_edges=int(sum(len(v.object_ids) for v in g.views)))
@@ -531,6 +597,7 @@ def main():
                 sel, idx, room, score = ix.query_hier(tq, np.zeros(len(tq), np.int32), room_text, np.zeros(len(tq), np.int32),
                                                       np.ones(len(tq), np.int32), k)
                 state["gemm"] = ix.profile()
+                state["sel"] = sel
                 state["rooms_hit"] = float(np.mean([int(ent_room[e]) in s_ for e, s_ in zip(q_ent, sel)]))
                 ix.close()
                 return idx, room, score
@@ -550,7 +617,7 @@ def main():
     sync()
     t0 = time.perf_counter()
     for i_step in range(args.steps):
-        if i_step == args.steps - 1:
+        if args.full and i_step == args.steps - 1:
             prof_on["on"] = True
             sc.set_profiling(True)
         step()
@@ -558,11 +625,15 @@ def main():
     if use_dist:
         dist.barrier()
     dt = time.perf_counter() - t0
-    prof = sc.profile()                                           # events of the LAST timed step
-    sc.set_profiling(False)
-    prof_on["on"] = False
-    if state.get("gemm") and state["gemm"][0]:
-        prof["k_gemm_f64"] = state["gemm"]
+    prof = {}
+    if args.full:
+        prof = sc.profile()                                       # events of the LAST timed step
+        sc.set_profiling(False)
+        prof_on["on"] = False
+        if state.get("gemm") and state["gemm"][0]:
+            prof["k_gemm_f64"] = state["gemm"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sc, state)                # (before the --full legs: they reuse the scene handle)
     per_rank_fps = [F * max(args.steps, 1) / dt]
     if use_dist:
         mine = torch.tensor([dt], device=device, dtype=torch.float64)
@@ -641,7 +712,7 @@ def main():
     # all-gathered size of configs[3] (8 scenes' nodes and rooms: every query on its own scene's storey).
     resident = None
     node_table = None
-    if c_graph and not use_dist and not episode and args.resident_repeats > 0 and state.get("graph") is not None:
+    if args.full and c_graph and not use_dist and not episode and args.resident_repeats > 0 and state.get("graph") is not None:
         try:
             cg = state["graph"]
             rooms_c = cg.rooms()
@@ -792,14 +863,14 @@ def main():
 
     inflight = None
     try:
-        inflight = measure_inflight() if (not episode and not use_dist and args.inflight_steps > 0) else None
+        inflight = measure_inflight() if (args.full and not episode and not use_dist and args.inflight_steps > 0) else None
     except Exception as e:          # (an extra: it must never take the benchmark line down)
         inflight = dict(error=repr(e))
 
     # ---- extra, for continuity with rounds 1-3's line: the same scene with the rooms' 2-D regions HANDED IN and no views (their
     # `value`; A9's room embeddings / View nodes and A10's view test are then not in the step).  Two steps, never `value`.
     handed_in = None
-    if args.full_graph and not episode and not use_dist and not emu and not args.no_extras:
+    if args.full and args.full_graph and not episode and not use_dist and not emu and not args.no_extras:
         try:
             def step_rooms_given():
                 sc.reset()
@@ -830,7 +901,7 @@ def main():
     # ---- extra: the encoder hand-off leg (holoagent_amd/encoder_handoff.py): a live PyTorch-ROCm module's outputs go to the
     # library by device pointer.  A few frames on a handle of their own; never part of `value`.
     handoff = None
-    if rank == 0 and world == 1 and not emu and not episode and args.encoder_frames > 0:
+    if args.full and rank == 0 and world == 1 and not emu and not episode and args.encoder_frames > 0:
         try:
             from holoagent_amd.encoder_handoff import measure as measure_handoff
             nf = min(args.encoder_frames, F)
@@ -846,7 +917,7 @@ def main():
 
     # ---- CPU baseline: the oracle on a bounded sample of the same frames (rank 0, N=1)
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_frames > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_frames > 0:
         n = min(args.cpu_frames, F)
         h_rgb = inp["rgb"][:n].cpu().numpy()
         h_depth = inp["depth"][:n].cpu().numpy().view(np.uint16)
@@ -936,26 +1007,27 @@ def main():
                    threading=threading_note, seconds=round(t_cpu, 2))
 
     mfma_util = None
-    try:
-        import glob
-        mp = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]_pmc_mfma.json")))[-1]
-        mk = json.load(open(mp))["kernels"]
-        mj = json.load(open(mp))
+    if args.full:
         try:
-            sys.path.insert(0, os.path.join(ROOT, "scripts"))
-            from csrc_sha import csrc_sha16
-            same = mj.get("csrc_sha16") == csrc_sha16(ROOT)
+            import glob
+            mp = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]_pmc_mfma.json")))[-1]
+            mk = json.load(open(mp))["kernels"]
+            mj = json.load(open(mp))
+            try:
+                sys.path.insert(0, os.path.join(ROOT, "scripts"))
+                from csrc_sha import csrc_sha16
+                same = mj.get("csrc_sha16") == csrc_sha16(ROOT)
+            except Exception:
+                same = None
+            # (committed counters, not a measurement of this run: `same_build` says whether they were taken on the sources being timed)
+            mfma_util = {"source": "profiles/%s (offline PMC passes, same command)" % os.path.basename(mp), "same_build": same}
+            for name, key in (("k_pool_gram", "k_pool_gram"), ("k_gemm_f64", "k_gemm_f64_tiled")):
+                if key in mk and "MfmaUtil_percent" in mk[key]:
+                    mfma_util[name] = {"MfmaUtil_percent": round(mk[key]["MfmaUtil_percent"], 2),
+                                       "SQ_VALU_MFMA_BUSY_CYCLES": mk[key]["SQ_VALU_MFMA_BUSY_CYCLES"]["mean_per_launch"],
+                                       "GRBM_GUI_ACTIVE": mk[key]["GRBM_GUI_ACTIVE"]["mean_per_launch"]}
         except Exception:
-            same = None
-        # (committed counters, not a measurement of this run: `same_build` says whether they were taken on the sources being timed)
-        mfma_util = {"source": "profiles/%s (offline PMC passes, same command)" % os.path.basename(mp), "same_build": same}
-        for name, key in (("k_pool_gram", "k_pool_gram"), ("k_gemm_f64", "k_gemm_f64_tiled")):
-            if key in mk and "MfmaUtil_percent" in mk[key]:
-                mfma_util[name] = {"MfmaUtil_percent": round(mk[key]["MfmaUtil_percent"], 2),
-                                   "SQ_VALU_MFMA_BUSY_CYCLES": mk[key]["SQ_VALU_MFMA_BUSY_CYCLES"]["mean_per_launch"],
-                                   "GRBM_GUI_ACTIVE": mk[key]["GRBM_GUI_ACTIVE"]["mean_per_launch"]}
-    except Exception:
-        mfma_util = None
+            mfma_util = None
     if rank == 0:
         last = state.get("last")
         out = {
@@ -986,7 +1058,7 @@ def main():
             "graph_counts_all_ranks": state.get("graph_counts_all_ranks"),
             "graph_level": ("C ABI graph object (hmsg_graph_begin / _finish / _index)" if c_graph else "Python mirror") if args.full_graph and not episode else None,
             "graph_ms": state.get("graph_ms"),
-            "emulated": bool(emu),
+            "emulated": bool(emu), "full": bool(args.full),
             # (scene mode: the sequential fold of A6 starts on a worker thread while hmsg_fuse_frames is still producing
             #  3-D masks, so part of the merge is inside the fuse_frames stage time; HMSG_FOLD_NOPIPE=1 separates them)
             "fold_beside_fusion": (not episode) and not os.environ.get("HMSG_FOLD_NOPIPE"),
@@ -998,11 +1070,11 @@ def main():
             "retrieval_room_stage_hit_rate": state.get("rooms_hit"),
             "stage_ms_per_step": {k_: round(v / steps * 1e3, 2) for k_, v in stage.items()},
             "map_voxels": V, "nodes_local": state.get("n_nodes_local"),
-            "kernels_ms_last_step": {k_: round(v[1], 3) for k_, v in sorted(prof.items(), key=lambda kv: -kv[1][1])},
+            "kernels_ms_last_step": {k_: round(v[1], 3) for k_, v in sorted(prof.items(), key=lambda kv: -kv[1][1])} if args.full else None,
             # algorithmic bytes (FLOP for the MFMA kernels) / measured time of every instrumented kernel
             "kernels_achieved": {k_: [round(v[2] / (v[1] * 1e-3) / (1e12 if k_ in MFMA_KERNELS else 1e9), 2),
                                       "TFLOP/s" if k_ in MFMA_KERNELS else "GB/s"]
-                                 for k_, v in sorted(prof.items(), key=lambda kv: -kv[1][1]) if v[1] > 0},
+                                 for k_, v in sorted(prof.items(), key=lambda kv: -kv[1][1]) if v[1] > 0} if args.full else None,
             # MFMA utilisation of the two matrix-core kernels from the PMC passes committed under profiles/ (rocprofv3 --pmc
             # SQ_VALU_MFMA_BUSY_CYCLES / GRBM_GUI_ACTIVE ..., one counter per pass over this same command: scripts/gpu_run.sh mfma)
             "mfma_utilisation": mfma_util,

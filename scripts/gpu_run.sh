@@ -7,7 +7,7 @@
 #   foldtrace[:ENV=1,..]     rocprofv3 --kernel-trace of one scene -> scripts/fold_timeline.py: per-position kernel durations and launch gaps of a fold step
 #   foldtime[:ENV=1,..]      HMSG_DEBUG_TIMING laps of the fold without the profiler (bench.py --rooms-handed-in --steps 2)
 #   d1024                    the configs[2] line (D = 1024) with HMSG_DEBUG_TIMING laps of hmsg_query_hier
-#   bench[:args]             python bench.py <args> -> bench_<n>.json (default args: --no-extras --cpu-frames 0 --steps 3)
+#   bench[:args]             python bench.py <args> -> bench_<n>.json (default args: --full --no-extras --cpu-frames 0 --steps 3)
 #   tests[:pytest-args]      python -m pytest -m gpu -x -q <args> (default: tests)
 #   smoke                    __graft_entry__.smoke()
 #   stats                    rocprofv3 --kernel-trace --stats of bench.py --steps 2 --warmup 0 --no-extras -> kernel_stats.csv
@@ -73,7 +73,7 @@ import json; d = json.loads([l for l in open('$OUT/foldtime_$label.json').read()
       ;;
     d1024)
       cd /root/repo
-      HMSG_DEBUG_TIMING=1 python bench.py --feat-dim 1024 --cpu-frames 0 --no-extras --steps 2 --warmup 1 > $OUT/bench_d1024.json 2> $OUT/bench_d1024.err
+      HMSG_DEBUG_TIMING=1 python bench.py --full --feat-dim 1024 --cpu-frames 0 --no-extras --steps 2 --warmup 1 > $OUT/bench_d1024.json 2> $OUT/bench_d1024.err
       grep "query_hier" $OUT/bench_d1024.err | tail -n 8
       python -c "
 import json; d = json.loads([l for l in open('$OUT/bench_d1024.json').read().splitlines() if l.startswith('{')][-1]); print('d1024:', d['value'], d['stage_ms_per_step'], d['queries_per_sec'])"
@@ -81,7 +81,7 @@ import json; d = json.loads([l for l in open('$OUT/bench_d1024.json').read().spl
     bench)
       cd /root/repo
       n_bench=$((n_bench + 1))
-      python bench.py ${arg:---no-extras --cpu-frames 0 --steps 3} > $OUT/bench_$n_bench.json 2> $OUT/bench_$n_bench.err
+      python bench.py ${arg:---full --no-extras --cpu-frames 0 --steps 3} > $OUT/bench_$n_bench.json 2> $OUT/bench_$n_bench.err
       python -c "
 import json; d = json.loads([l for l in open('$OUT/bench_$n_bench.json').read().splitlines() if l.startswith('{')][-1]); print('bench $n_bench:', d['value'], d['ms_per_step'], d['stage_ms_per_step'], d.get('roofline'))"
       ;;

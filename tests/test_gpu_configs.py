@@ -309,3 +309,35 @@ def test_bench_rccl_path_with_one_rank(mode):
     assert rec["rccl_ranks"] == 1 and rec["n_gpus"] == 1 and rec["value"] > 0
     assert rec["scaling"] == ("strong" if mode == "episode" else "weak")
     assert rec["nodes_local"] > 5 and rec["queries_per_sec"] > 0
+
+
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """A plain `bench.py` run (no --full) times exactly --steps steps, reports `ms_per_step` and none of the --full legs, and
+    --dump-outputs writes what the last timed step handed its caller: float32 / float64 arrays, 64 MB at most, retrieval
+    answers that index the dumped node table."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+    env = dict(os.environ)
+    for k_ in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "HMSG_BENCH_FORCE_DIST"):
+        env.pop(k_, None)
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--frames", "96",
+                          "--queries", "64", "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-3000:]
+    rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert rec["steps"] == 2 and rec["warmup"] == 1 and rec["full"] is False and rec["unit"] == "frames/s"
+    assert abs(rec["value"] - 96 / (rec["ms_per_step"] / 1e3)) < 1e-2 * rec["value"] + 1e-3
+    for k_ in ("roofline", "cpu_baseline", "retrieval_resident", "scenes_in_flight", "rooms_handed_in", "encoder_handoff", "kernels_ms_last_step"):
+        assert rec[k_] is None, k_
+    got = {f[: -len(".npy")]: np.load(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)}
+    for name in ("query_idx", "query_room", "query_score", "query_rooms_selected", "node_records", "node_embeddings", "graph_counts",
+                 "graph_objects", "map_points"):
+        assert name in got, name
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    idx, score = got["query_idx"], got["query_score"]
+    assert idx.shape == (64, 5) and score.shape == (64, 5) and (idx >= 0).any()
+    assert idx.max() < got["node_records"].shape[0] and np.isfinite(score[idx >= 0]).all()
+    assert got["node_embeddings"].shape == (got["node_records"].shape[0], 512) and got["map_points"].shape[1] == 3
+    assert got["graph_counts"][3] == rec["graph_counts"]["objects"] == got["graph_objects"].shape[0]

@@ -1,5 +1,6 @@
 """Label vocabulary loader (holoagent_amd/label_feats.py) against the reference's get_label_feats
-(tests/golden/labels.json, made by oracle/refdrive/gen_golden_labels.py)."""
+(tests/golden/labels.json, made by oracle/refdrive/gen_golden_labels.py).  The reference's vocabulary files themselves
+(memory/hmsg/labels/*.csv, lists of names) are stored byte for byte in tests/golden/label_csvs.npz."""
 import hashlib
 import json
 import os
@@ -9,8 +10,8 @@ import pytest
 
 from holoagent_amd import label_feats as LF
 
-REF_LABELS = "/root/reference/fsr_vln/memory/hmsg/labels"
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "labels.json")
+REF_LABELS = os.path.join(os.path.dirname(__file__), "golden", "label_csvs.npz")
 
 
 def _enc(calls):
@@ -43,11 +44,12 @@ def test_registered_and_literal_vocabularies(tmp_path):
         LF.get_label_feats(_enc(calls), "SCANNET20")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_LABELS), reason="the vocabularies are data of the reference checkout")
-def test_class_lists_equal_the_reference_loader():
+def test_class_lists_equal_the_reference_loader(tmp_path):
     gold = json.load(open(GOLD))
+    files = np.load(REF_LABELS)
     for name, (csv, _) in LF.CSV_SETS.items():
-        classes = LF.read_label_csv(os.path.join(REF_LABELS, csv))
+        (tmp_path / csv).write_bytes(files[csv].tobytes())
+        classes = LF.read_label_csv(str(tmp_path / csv))
         g = gold[name]
         assert len(classes) == g["n"] and str(classes[0]) == g["first"] and str(classes[-1]) == g["last"]
         assert hashlib.sha1("\n".join(str(c) for c in classes).encode()).hexdigest() == g["sha1"]
