@@ -143,6 +143,9 @@ _SIGS = {
     "hmsg_load": (C.c_int, [C.c_char_p, C.c_int32, C.POINTER(_P)]),
     "hmsg_graph_index": (C.c_int, [_P, _P, C.POINTER(_P)]),
     "hmsg_graph_query": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
+    "hmsg_graph_name_rooms": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P]),
+    "hmsg_graph_set_room_names": (C.c_int, [_P, C.c_int32, _P]),
+    "hmsg_denoise_feats_batch": (C.c_int, [C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_double, C.c_int32, _P, _P]),
     "hmsg_kmeans": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, _P, _P, _P, _P]),
     "hmsg_room_camera_distances": (C.c_int, [_P, C.c_int32, C.c_int64, _P, _P]),
     "hmsg_object_views": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int64, _P, _P, C.c_double, C.c_double, _P, _P]),
@@ -849,6 +852,22 @@ class SceneGraph:
         nx._n_rooms = int(roff[-1])
         return nx, noff, roff, foff
 
+    def name_rooms(self, method, type_feats, type_names):
+        """hmsg_graph_name_rooms: Graph.generate_room_names(generate_method=method, default_room_types=type_names) with
+        type_feats = the types' text features; method "obj_embedding" or "view_embedding".  -> chosen type per room (-1: unchanged)."""
+        m = {"obj_embedding": ROOM_NAMES_OBJ_EMBEDDING, "view_embedding": ROOM_NAMES_VIEW_EMBEDDING}[method]
+        T = np.ascontiguousarray(np.asarray(type_feats, np.float32))
+        names, keep = self._strs(type_names)
+        assert T.ndim == 2 and len(T) == len(type_names)
+        out = np.full(max(self.counts()["rooms"], 1), -1, np.int32)
+        self._ck(self.L.c.hmsg_graph_name_rooms(self.g, m, len(T), _ptr(T), C.cast(names, _P), _ptr(out)))
+        return out[: self.counts()["rooms"]]
+
+    def set_room_names(self, names):
+        """hmsg_graph_set_room_names (Graph.set_room_names)"""
+        arr, keep = self._strs(names)
+        self._ck(self.L.c.hmsg_graph_set_room_names(self.g, len(names), C.cast(arr, _P)))
+
     def query(self, T_obj, qid, T_room, floor_id, room_mode, k, use_negatives=True, room_name_emb=None, max_rooms=None):
         """hmsg_graph_query: floor -> room(s) -> objects on the graph's own index (made on the first call)"""
         T_obj = np.ascontiguousarray(T_obj, dtype=np.float32)
@@ -865,6 +884,34 @@ class SceneGraph:
                                            None if T_room is None else _ptr(T_room), _ptr(floor_id), _ptr(room_mode), int(k), int(use_negatives), RM,
                                            _ptr(sel), _ptr(nsel), _ptr(idx), _ptr(room), _ptr(score)))
         return [sel[q, : nsel[q]].tolist() for q in range(Q)], idx, room, score
+
+
+ROOM_NAMES_OBJ_EMBEDDING, ROOM_NAMES_VIEW_EMBEDDING = 1, 2     # include/hmsg.h: HMSG_ROOM_NAMES_*
+
+
+def denoise_feats_batch(sets, eps=0.02, min_samples=2, device_id=0, lib_: "HmsgLib | None" = None):
+    """feats_denoise_dbscan (utils/graph_utils.py:682-728) of many sets at once on the device (include/hmsg.h:
+    hmsg_denoise_feats_batch).  sets: arrays [n_k, D], all float32 or all float64 (np.array of the rows, as the reference
+    takes them).  -> (representatives [K, D] in that dtype, rows of the chosen cluster per set, 0 = no cluster)."""
+    L = lib_ or lib()
+    rows = [np.asarray(s_) for s_ in sets]
+    K = len(rows)
+    f64 = any(r.dtype != np.float32 for r in rows)
+    dt = np.float64 if f64 else np.float32
+    D = next((r.reshape(len(r), -1).shape[1] for r in rows if r.size), 0)
+    rows = [r.reshape(len(r), D) if r.size else np.zeros((0, D), dt) for r in rows]
+    off = np.zeros(K + 1, np.int64)
+    off[1:] = np.cumsum([len(r) for r in rows])
+    X = np.ascontiguousarray(np.concatenate(rows).astype(dt, copy=False) if K and off[-1] else np.zeros((1, max(D, 1)), dt))
+    out = np.zeros((K, D), dt)
+    ncl = np.zeros(K, np.int32)
+    if K == 0:
+        return out, ncl
+    rc = L.c.hmsg_denoise_feats_batch(int(device_id), K, _ptr(off), _ptr(X), int(f64), int(D), float(eps), int(min_samples), _ptr(out), _ptr(ncl))
+    if rc != 0:
+        bad = [k for k in range(K) if off[k + 1] == off[k]]
+        raise HmsgError(f"hmsg_denoise_feats_batch failed ({rc})" + (f": set {bad[0]} is empty" if bad else ""))
+    return out, ncl
 
 
 def points_min_dist_2d(sets, queries, device_id=0, lib_: "HmsgLib | None" = None):

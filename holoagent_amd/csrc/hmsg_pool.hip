@@ -11,21 +11,12 @@
 // order in float32, which is what np.mean(axis=0) does on a C-contiguous [n, D] array.
 #include "hmsg_cloudops.h"
 #include "hmsg_nn.h"
+#include "hmsg_dbscan.h"
 
 #include <algorithm>
 #include <cmath>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-struct PoolSeg {            // one instance
-    long long row_base;     // first row in the concatenated feature matrix
-    long long bit_base;     // first u32 word of its adjacency bit matrix
-    int n;                  // rows (valid points)
-    int nw;                 // u32 words per row = ceil(n / 32)
-    long long tile_base;    // first Gram tile id (upper triangle, super-tile order: gram_tile_of)
-    int nt;                 // Gram tiles per side = ceil(n / GRAM_T)
-    int pad;
-};
 
 // ---- NN of the down-sampled instance points; keep dist <= max_dist (graph.py:458-460)
 __global__ void k_pool_nn(const double* __restrict__ q, long long N, NNIndex I, double max_dist, int* __restrict__ idx,
@@ -72,7 +63,6 @@ __global__ void k_pool_gather(const int* __restrict__ idx, const unsigned* __res
 // which is what bounded the kernel -- and four MFMAs share four LDS fragment reads.
 // Only tiles with tj >= ti are computed (the matrix is symmetric): the mirrored adjacency words are built
 // from the same accumulators (a lane owns one column of a 32x32 block = one mirrored row half).
-#define GRAM_T 128
 #define GRAM_SUP 8          /* tiles per side of a super-tile */
 // Tile order inside an instance: super-tiles of GRAM_SUP x GRAM_SUP tiles, super-rows top to bottom, the diagonal
 // super-tile (a triangle) first, then the ones to its right, row-major inside.  Consecutive tile numbers therefore share
@@ -428,6 +418,70 @@ __global__ void k_seg_rows(const PoolSeg* __restrict__ segs, int* __restrict__ s
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < sg.n; i += gridDim.x * blockDim.x) seg_of_row[sg.row_base + i] = blockIdx.y;
 }
 
+void pool_cluster(hipStream_t s, const PoolSeg* d_ps, long long R, int minpts, const unsigned* adj, const unsigned* ncount,
+                  const int* seg_of_row, int* label, int* seg_first, int* d_changed, int* flabel, unsigned* csize, unsigned* cfirst,
+                  unsigned long long* best, DbgLaps* laps) {
+    hipLaunchKernelGGL(k_pool_init, dim3(cdiv((size_t)R, 256)), dim3(256), 0, s, ncount, (long long)R,
+                       minpts, label, d_ps, seg_of_row, seg_first);
+    HMSG_CHECK_LAUNCH();
+    // (two rounds before the first look at the flag -- the first one is cheap and always changes something --, then one round
+    //  per look: a round over rows that no longer change costs 1.2 ms, a look 20 us.  Round 6: behind those two rounds the rows
+    //  that are still on their way are listed, and the later rounds run over the list.)
+    DevBuf<unsigned> open_list;
+    open_list.alloc((size_t)std::max<long long>(R, 1) + 1);                            // [0] the count, the rows behind it
+    const unsigned* d_list = nullptr;
+    unsigned n_open = 0;
+    static const bool list_wanted = getenv("HMSG_DEBUG_POOL_ALL_ROWS") == nullptr;   // HMSG_DEBUG_POOL_ALL_ROWS=1: every round over every row (until round 5)
+    for (int it = 0; it < 100000; ++it) {
+        HIP_TRY(hipMemsetAsync(d_changed, 0, 4, s));
+        const size_t rows = d_list ? (size_t)n_open : (size_t)R;
+        for (int rep = 0; rep < (it == 0 ? 2 : 1) && rows; ++rep) {
+            hipLaunchKernelGGL(k_pool_prop, dim3(cdiv(rows * 64, 256)), dim3(256), 0, s, adj,
+                               d_ps, seg_of_row, ncount,
+                               minpts, (long long)rows, label, d_changed, seg_first, (it == 0 && rep == 0) ? 1 : 0, d_list);
+            hipLaunchKernelGGL(k_pool_jump, dim3(cdiv(rows, 256)), dim3(256), 0, s, d_ps,
+                               seg_of_row, ncount, minpts, (long long)rows, label, d_list);
+        }
+        HMSG_CHECK_LAUNCH();
+        if (it == 0 && list_wanted) {
+            HIP_TRY(hipMemsetAsync(open_list.p, 0, 4, s));
+            hipLaunchKernelGGL(k_pool_list, dim3(cdiv((size_t)R, 256)), dim3(256), 0, s, d_ps, seg_of_row,
+                               ncount, minpts, (long long)R, label, seg_first,
+                               open_list.p + 1, open_list.p);
+            HMSG_CHECK_LAUNCH();
+            HIP_TRY(hipMemcpyAsync(&n_open, open_list.p, 4, hipMemcpyDeviceToHost, s));
+        }
+        int ch = 0;
+        HIP_TRY(hipMemcpyAsync(&ch, d_changed, 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (it == 0 && list_wanted) d_list = open_list.p + 1;
+        if (!ch) break;
+    }
+    if (laps) laps->lap("label propagation");
+    hipLaunchKernelGGL(k_pool_border, dim3(cdiv((size_t)R * 64, 256)), dim3(256), 0, s, adj,
+                       d_ps, seg_of_row, ncount, minpts,
+                       (long long)R, label, flabel, csize, cfirst);
+    hipLaunchKernelGGL(k_pool_pick, dim3(cdiv((size_t)R, 256)), dim3(256), 0, s, d_ps,
+                       seg_of_row, (long long)R, csize, cfirst, best);
+    HMSG_CHECK_LAUNCH();
+}
+
+// ---- the launches hmsg_roomnames.hip shares (hmsg_dbscan.h)
+void pool_launch_gram_f32(hipStream_t s, const float* Xn, int D, const PoolSeg* d_ps, int K, long long tiles, float eps, unsigned* adj,
+                          unsigned* ncount) {
+    hipLaunchKernelGGL(k_pool_gram, dim3((unsigned)tiles), dim3(256), 0, s, Xn, D, d_ps, K, eps, adj, ncount);
+    HMSG_CHECK_LAUNCH();
+}
+void pool_launch_seg_rows(hipStream_t s, const PoolSeg* d_ps, int K, int maxn, int* seg_of_row) {
+    hipLaunchKernelGGL(k_seg_rows, dim3(std::max(1u, std::min(cdiv(maxn, 256), 256u)), K), dim3(256), 0, s, d_ps, seg_of_row);
+    HMSG_CHECK_LAUNCH();
+}
+void pool_launch_mean_f32(hipStream_t s, const float* X, int D, const PoolSeg* d_ps, int K, const int* flabel, const unsigned* csize,
+                          const unsigned* cfirst, const unsigned long long* best, float* out) {
+    hipLaunchKernelGGL(k_pool_mean, dim3(cdiv(D, 64), K), dim3(64), 0, s, X, D, d_ps, K, flabel, csize, cfirst, best, out);
+    HMSG_CHECK_LAUNCH();
+}
+
 void hmsg_pool(hmsg_ctx* h) {
     const hmsg_config& c = h->cfg;
     hipStream_t s = h->stream;
@@ -558,49 +612,8 @@ void hmsg_pool(hmsg_ctx* h) {
                                (float)c.feat_dbscan_eps, adj.p, ncount.p);
         }
         laps.lap("k_pool_gram");
-        hipLaunchKernelGGL(k_pool_init, dim3(cdiv((size_t)R, 256)), dim3(256), 0, s, (const unsigned*)ncount.p, (long long)R,
-                           c.feat_dbscan_min, label.p, (const PoolSeg*)d_ps.p, (const int*)seg_of_row.p, seg_first.p);
-        HMSG_CHECK_LAUNCH();
-        // (two rounds before the first look at the flag -- the first one is cheap and always changes something --, then one round
-        //  per look: a round over rows that no longer change costs 1.2 ms, a look 20 us.  Round 6: behind those two rounds the rows
-        //  that are still on their way are listed, and the later rounds run over the list.)
-        DevBuf<unsigned> open_list;
-        open_list.alloc(Rn + 1);                            // [0] the count, the rows behind it
-        const unsigned* d_list = nullptr;
-        unsigned n_open = 0;
-        static const bool list_wanted = getenv("HMSG_DEBUG_POOL_ALL_ROWS") == nullptr;   // HMSG_DEBUG_POOL_ALL_ROWS=1: every round over every row (until round 5)
-        for (int it = 0; it < 100000; ++it) {
-            HIP_TRY(hipMemsetAsync(d_changed.p, 0, 4, s));
-            const size_t rows = d_list ? (size_t)n_open : (size_t)R;
-            for (int rep = 0; rep < (it == 0 ? 2 : 1) && rows; ++rep) {
-                hipLaunchKernelGGL(k_pool_prop, dim3(cdiv(rows * 64, 256)), dim3(256), 0, s, (const unsigned*)adj.p,
-                                   (const PoolSeg*)d_ps.p, (const int*)seg_of_row.p, (const unsigned*)ncount.p,
-                                   c.feat_dbscan_min, (long long)rows, label.p, d_changed.p, (const int*)seg_first.p, (it == 0 && rep == 0) ? 1 : 0, d_list);
-                hipLaunchKernelGGL(k_pool_jump, dim3(cdiv(rows, 256)), dim3(256), 0, s, (const PoolSeg*)d_ps.p,
-                                   (const int*)seg_of_row.p, (const unsigned*)ncount.p, c.feat_dbscan_min, (long long)rows, label.p, d_list);
-            }
-            HMSG_CHECK_LAUNCH();
-            if (it == 0 && list_wanted) {
-                HIP_TRY(hipMemsetAsync(open_list.p, 0, 4, s));
-                hipLaunchKernelGGL(k_pool_list, dim3(cdiv((size_t)R, 256)), dim3(256), 0, s, (const PoolSeg*)d_ps.p, (const int*)seg_of_row.p,
-                                   (const unsigned*)ncount.p, c.feat_dbscan_min, (long long)R, (const int*)label.p, (const int*)seg_first.p,
-                                   open_list.p + 1, open_list.p);
-                HMSG_CHECK_LAUNCH();
-                HIP_TRY(hipMemcpyAsync(&n_open, open_list.p, 4, hipMemcpyDeviceToHost, s));
-            }
-            int ch = 0;
-            HIP_TRY(hipMemcpyAsync(&ch, d_changed.p, 4, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            if (it == 0 && list_wanted) d_list = open_list.p + 1;
-            if (!ch) break;
-        }
-        laps.lap("label propagation");
-        hipLaunchKernelGGL(k_pool_border, dim3(cdiv((size_t)R * 64, 256)), dim3(256), 0, s, (const unsigned*)adj.p,
-                           (const PoolSeg*)d_ps.p, (const int*)seg_of_row.p, (const unsigned*)ncount.p, c.feat_dbscan_min,
-                           (long long)R, (const int*)label.p, flabel.p, csize.p, cfirst.p);
-        hipLaunchKernelGGL(k_pool_pick, dim3(cdiv((size_t)R, 256)), dim3(256), 0, s, (const PoolSeg*)d_ps.p,
-                           (const int*)seg_of_row.p, (long long)R, (const unsigned*)csize.p, (const unsigned*)cfirst.p, best.p);
-        HMSG_CHECK_LAUNCH();
+        pool_cluster(s, (const PoolSeg*)d_ps.p, (long long)R, c.feat_dbscan_min, (const unsigned*)adj.p, (const unsigned*)ncount.p,
+                     (const int*)seg_of_row.p, label.p, seg_first.p, d_changed.p, flabel.p, csize.p, cfirst.p, best.p, &laps);
     }
     laps.lap("border + pick");
     hmsg_dump("pool_ds", ds.p, (size_t)P * 24, s);

@@ -10,6 +10,7 @@
 // assembly is no longer Python.  The KMeans fits of a storey's rooms run on host threads between hmsg_graph_begin (right
 // after hmsg_finalize_map) and hmsg_graph_finish (after hmsg_pool_instances): beside the fusion and the merge fold.
 #include "hmsg_common.h"
+#include "hmsg_dbscan.h"
 
 #include <dirent.h>
 #include <sys/stat.h>
@@ -1576,6 +1577,122 @@ int hmsg_graph_query(hmsg_graph_t* g, const double* room_name_emb, int32_t Q, in
                                    out_score);
     if (rc != HMSG_OK) g->err = hmsg_index_last_error(g->ix);
     return rc;
+}
+
+/* Graph.generate_room_names (graph.py:2146-2187) on the graph object: "obj_embedding" (Room.infer_room_type_from_objects, room.py:237-308)
+ * or "view_embedding" (Room.infer_room_type_from_view_embedding, room.py:131-172) -- hmsg_roomnames.hip.  All rooms are named in one
+ * batch, and only once every room has an answer (a room without objects fails the whole call, as the reference's loop raises there). */
+int hmsg_graph_name_rooms(hmsg_graph_t* g, int32_t method, int32_t n_types, const float* type_feats, const char* const* type_names,
+                          int32_t* type_of_room) {
+    if (!g) return HMSG_ERR_INVALID;
+    return gguard(g, [&] {
+        HMSG_REQUIRE(g->finished && !g->failed, HMSG_ERR_INVALID, "hmsg_graph_name_rooms: the graph is not finished");
+        HMSG_REQUIRE(method == HMSG_ROOM_NAMES_OBJ_EMBEDDING || method == HMSG_ROOM_NAMES_VIEW_EMBEDDING, HMSG_ERR_INVALID,
+                     "hmsg_graph_name_rooms: unknown method (\"label\" asks an LLM: not on the device)");
+        HMSG_REQUIRE(n_types >= 1 && type_feats && type_names, HMSG_ERR_INVALID, "hmsg_graph_name_rooms: no room types");
+        for (int t = 0; t < n_types; ++t) HMSG_REQUIRE(type_names[t] != nullptr, HMSG_ERR_INVALID, "hmsg_graph_name_rooms: a type without a name");
+        const int R = (int)g->rooms.size(), D = g->D;
+        std::vector<int32_t> type((size_t)std::max(R, 1), -1);
+        if (R > 0) {
+            HMSG_REQUIRE(D > 0, HMSG_ERR_INVALID, "hmsg_graph_name_rooms: the graph has no embeddings");
+            HIP_TRY(hipSetDevice(g->h ? g->h->cfg.device_id : g->device));
+            if (g->h) HIP_TRY(hipStreamSynchronize(g->h->stream));
+            hipStream_t s = nullptr;
+            DevBuf<float> d_T;
+            d_T.alloc((size_t)n_types * D);
+            HIP_TRY(hipMemcpyAsync(d_T.p, type_feats, (size_t)n_types * D * 4, hipMemcpyHostToDevice, s));
+            if (method == HMSG_ROOM_NAMES_OBJ_EMBEDDING) {
+                std::vector<long long> off(1, 0);
+                for (const GRoom& rm : g->rooms) {
+                    HMSG_REQUIRE(!rm.objects.empty(), HMSG_ERR_INVALID,
+                                 "hmsg_graph_name_rooms: room " + rm.id + " has no objects (feats_denoise_dbscan of an empty array raises); no room was renamed");
+                    off.push_back(off.back() + (long long)rm.objects.size());
+                }
+                const long long N = off.back();
+                const bool f64 = g->loaded;
+                DevBuf<char> X, rep;
+                X.alloc((size_t)N * D * (f64 ? 8 : 4));
+                rep.alloc((size_t)R * D * (f64 ? 8 : 4));
+                if (f64) {                                            // json.load's float64 rows (object.py:88)
+                    std::vector<double> h((size_t)N * D);
+                    size_t at = 0;
+                    for (const GRoom& rm : g->rooms)
+                        for (int o : rm.objects) {
+                            const GObject& ob = g->objects[(size_t)o];
+                            HMSG_REQUIRE((int)ob.emb.size() == D, HMSG_ERR_INVALID, "hmsg_graph_name_rooms: object " + ob.id + " was saved without an embedding");
+                            memcpy(&h[at], ob.emb.data(), (size_t)D * 8);
+                            at += (size_t)D;
+                        }
+                    HIP_TRY(hipMemcpyAsync(X.p, h.data(), h.size() * 8, hipMemcpyHostToDevice, s));
+                } else if (g->merged) {                               // Room.merge_objects' mean embeddings (host float32)
+                    std::vector<float> h((size_t)N * D);
+                    size_t at = 0;
+                    for (const GRoom& rm : g->rooms)
+                        for (int o : rm.objects) {
+                            memcpy(&h[at], g->objects[(size_t)o].emb32.data(), (size_t)D * 4);
+                            at += (size_t)D;
+                        }
+                    HIP_TRY(hipMemcpyAsync(X.p, h.data(), h.size() * 4, hipMemcpyHostToDevice, s));
+                } else {                                              // the pooled features, gathered in HBM
+                    std::vector<int> rows;
+                    rows.reserve((size_t)N);
+                    for (const GRoom& rm : g->rooms)
+                        for (int o : rm.objects) rows.push_back(g->objects[(size_t)o].instance);
+                    rn_gather_rows_f32(s, g->h->inst_feats.p, rows, D, (float*)X.p);
+                }
+                rn_denoise(s, X.p, f64, D, off, 0.02, 2, rep.p, nullptr);
+                DevBuf<int> d_type;
+                d_type.alloc((size_t)R);
+                rn_choose(s, rep.p, f64, R, D, d_T.p, n_types, d_type.p);
+                HIP_TRY(hipMemcpyAsync(type.data(), d_type.p, (size_t)R * 4, hipMemcpyDeviceToHost, s));
+                HIP_TRY(hipStreamSynchronize(s));
+            } else {
+                std::vector<long long> voff(1, 0);
+                for (const GRoom& rm : g->rooms) voff.push_back(voff.back() + rm.n_emb);
+                const long long NV = voff.back();
+                if (NV > 0) {
+                    const bool f64 = g->loaded;
+                    DevBuf<char> V;
+                    V.alloc((size_t)NV * D * (f64 ? 8 : 4));
+                    size_t at = 0;
+                    for (const GRoom& rm : g->rooms) {
+                        const size_t n = (size_t)rm.n_emb * D;
+                        if (!n) continue;
+                        HIP_TRY(hipMemcpyAsync(V.p + at, f64 ? (const void*)rm.emb64.data() : (const void*)rm.emb.data(), n * (f64 ? 8 : 4),
+                                               hipMemcpyHostToDevice, s));
+                        at += n * (f64 ? 8 : 4);
+                    }
+                    DevBuf<int> d_vt;
+                    d_vt.alloc((size_t)NV);
+                    rn_choose(s, V.p, f64, NV, D, d_T.p, n_types, d_vt.p);
+                    rn_vote(s, d_vt.p, voff, n_types, type.data());
+                }
+            }
+        }
+        for (int r = 0; r < R; ++r)                                   // (a room without views keeps its name: room.py:153-155)
+            if (type[(size_t)r] >= 0) g->rooms[(size_t)r].name = type_names[type[(size_t)r]];
+        if (type_of_room)
+            for (int r = 0; r < R; ++r) type_of_room[r] = type[(size_t)r];
+        if (g->ix) {                                                  // label mode answers from the names: the next query re-indexes
+            hmsg_index_destroy(g->ix);
+            g->ix = nullptr;
+        }
+    });
+}
+
+/* Graph.set_room_names (graph.py:2129-2144) */
+int hmsg_graph_set_room_names(hmsg_graph_t* g, int32_t n, const char* const* names) {
+    if (!g) return HMSG_ERR_INVALID;
+    return gguard(g, [&] {
+        HMSG_REQUIRE(n == (int32_t)g->rooms.size(), HMSG_ERR_INVALID, "hmsg_graph_set_room_names: The length of room_names should be the same as the number of rooms in the graph");
+        HMSG_REQUIRE(n == 0 || names, HMSG_ERR_INVALID, "hmsg_graph_set_room_names: no names");
+        for (int r = 0; r < n; ++r) HMSG_REQUIRE(names[r] != nullptr, HMSG_ERR_INVALID, "hmsg_graph_set_room_names: a NULL name");
+        for (int r = 0; r < n; ++r) g->rooms[(size_t)r].name = names[r];
+        if (g->ix) {
+            hmsg_index_destroy(g->ix);
+            g->ix = nullptr;
+        }
+    });
 }
 
 }  // extern "C"

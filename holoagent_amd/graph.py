@@ -296,6 +296,21 @@ class Room:    # graph/room.py:15-60, 309-374
         self.name = default_room_types[int(np.argmax(cnt))]
         return self.name
 
+    def infer_room_type_from_objects(self, infer_method="label", default_room_types=None, text_feats=None, lib=None, represent=None):
+        """room.py:237-308.  "obj_embedding": feats_denoise_dbscan of the objects' embeddings on the device (hmsg_denoise_feats_batch;
+        `represent` = an already computed representative), then argmax(represent . text_feats^T).  "label" asks an LLM."""
+        if infer_method == "label":
+            raise NotImplementedError('infer_room_type_from_objects(infer_method="label") asks an LLM for the room type '
+                                      '(llm_utils.infer_room_type_from_object_list_chat): not available here')
+        if infer_method == "obj_embedding":
+            assert default_room_types, "default_room_types can not be None if infer_method is 'embedding'"
+            if represent is None:
+                from ._lib import denoise_feats_batch
+                represent = denoise_feats_batch([np.array([o.embedding for o in self.objects])], lib_=lib)[0][0]
+            sim_mat = np.dot(np.asarray(represent).reshape((1, -1)), np.asarray(text_feats).T)
+            self.name = default_room_types[int(np.argmax(sim_mat))]
+        return self.name
+
     def save(self, path, lib=None):
         """room.py:309-337 (lib: through the C ABI, see Floor.save)"""
         if lib is not None:
@@ -1379,14 +1394,31 @@ class Graph:
 
     # ------------------------------------------------------------------ room names: graph.py:2129-2187
     def generate_room_names(self, generate_method="view_embedding", default_room_types=None):
+        """"obj_embedding": every room's feats_denoise_dbscan in ONE device batch (hmsg_denoise_feats_batch; a room without objects
+        raises before any room is renamed, as sklearn does in the reference's loop); "label" asks an LLM (NotImplementedError);
+        otherwise the view-embedding vote."""
         types = list(default_room_types or [])
         tf = self.get_text_feats_multiple_templates(types)
+        if generate_method == "obj_embedding":
+            assert default_room_types is not None, "You should provide a list of default room types"
+            from ._lib import denoise_feats_batch
+            reps, _ = denoise_feats_batch([np.array([o.embedding for o in r.objects]) for r in self.rooms], lib_=self.L)
+            for r, rep in zip(self.rooms, reps):
+                r.infer_room_type_from_objects("obj_embedding", types, tf, represent=rep)
+            return
+        if generate_method == "label":
+            for r in self.rooms:
+                r.infer_room_type_from_objects("label", types, tf)
         for r in self.rooms:
             r.infer_room_type_from_view_embedding(types, tf)
 
     def set_room_names(self, room_names):
+        """graph.py:2129-2144 (the room centre = the mean of its vertices)"""
+        assert len(room_names) == len(self.rooms), \
+            "The length of room_names should be the same as the number of rooms in the graph"
         for r, n in zip(self.rooms, room_names):
             r.name = n
+            r.room_center_pos = np.mean(r.vertices, axis=0)
 
     # ------------------------------------------------------------------ A12 queries
     def _node_index(self):

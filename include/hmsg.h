@@ -545,6 +545,41 @@ int hmsg_graph_query(hmsg_graph_t* g, const double* room_name_emb, int32_t Q, in
                      const float* T_room, const int32_t* floor_id, const int32_t* room_mode, int32_t k, int32_t use_negatives,
                      int32_t max_rooms, int32_t* out_sel, int32_t* out_nsel, int32_t* out_idx, int32_t* out_room, double* out_score);
 
+/* ---- room names: the step between hmsg_load and a label-mode query in the reference's query applications
+ * (load_hmsg_graph; generate_room_names(generate_method="obj_embedding", default_room_types=[...]); query_hierarchy_protected_icra).
+ *   hmsg_graph_name_rooms  Graph.generate_room_names (graph.py:2146-2187) for n_types room types: type_feats f32 [n_types][D] = the
+ *        text features of the type names (get_text_feats_multiple_templates(default_room_types)), type_names [n_types].
+ *          HMSG_ROOM_NAMES_OBJ_EMBEDDING   Room.infer_room_type_from_objects(infer_method="obj_embedding") (room.py:237-308):
+ *              feats_denoise_dbscan (utils/graph_utils.py:682-728: eps 0.02, min_samples 2, cosine) of the room's object embeddings
+ *              (float64 on a loaded graph, the float32 pooled features on a built one), then the first arg-max of
+ *              represent . type_feats^T.  A room without objects: HMSG_ERR_INVALID naming the room (sklearn raises on an empty
+ *              array) and no room is renamed.
+ *          HMSG_ROOM_NAMES_VIEW_EMBEDDING  Room.infer_room_type_from_view_embedding (room.py:131-172): per view embedding the
+ *              arg-max over the types, the majority vote (ties: the smallest type id); a room without views keeps its name.
+ *        type_of_room [rooms] (optional) receives the chosen type per room in hmsg_graph_get_rooms order, -1 where the name was
+ *        left unchanged.  The new names show in hmsg_graph_get_rooms, hmsg_graph_to_json and hmsg_save; the graph's query index is
+ *        dropped, so that the next hmsg_graph_query makes it again with the room_name_emb it is given.
+ *        Label mode from C: the text feature of a room's name is the type table's row of its type, so
+ *            room_name_emb[r][d] = (double)type_feats[type_of_room[r]][d]
+ *        for every room with type_of_room[r] >= 0 (a room whose name was left unchanged needs the feature of its own name).
+ *   hmsg_graph_set_room_names  Graph.set_room_names (graph.py:2129-2144, the applications' "human_assign" mode): n must be the
+ *        number of rooms (the reference asserts it); the room centre the reference also stores is not part of the graph object.
+ *   hmsg_denoise_feats_batch  feats_denoise_dbscan (utils/graph_utils.py:682-728, sklearn 1.7.2 semantics) of n_sets sets at once:
+ *        set k = rows set_off[k] .. set_off[k + 1] of feats [.][dim] (f32, or f64 when feats_is_f64), set_off host int64
+ *        [n_sets + 1], no set empty (HMSG_ERR_INVALID: sklearn raises).  Rows are L2-normalised (zero rows stay zero),
+ *        d = 1 - x.y clipped to [0, 2] with a zero diagonal, neighbours iff d <= eps, core rows have >= min_samples neighbours
+ *        (themselves included).  out [n_sets][dim] in the input dtype: the mean of the largest cluster's rows (ties: the
+ *        cluster that appears first in row order, Counter.most_common), added in row order and divided by their number as
+ *        np.mean(axis=0) does; with no cluster the mean of all rows.  n_in_cluster (host int32 [n_sets], optional): rows of
+ *        that cluster, 0 = no cluster.  feats / out: host or device pointers. */
+#define HMSG_ROOM_NAMES_OBJ_EMBEDDING 1
+#define HMSG_ROOM_NAMES_VIEW_EMBEDDING 2
+int hmsg_graph_name_rooms(hmsg_graph_t* g, int32_t method, int32_t n_types, const float* type_feats, const char* const* type_names,
+                          int32_t* type_of_room);
+int hmsg_graph_set_room_names(hmsg_graph_t* g, int32_t n, const char* const* names);
+int hmsg_denoise_feats_batch(int32_t device_id, int32_t n_sets, const int64_t* set_off, const void* feats, int32_t feats_is_f64, int32_t dim,
+                             double eps, int32_t min_samples, void* out, int32_t* n_in_cluster);
+
 /* ---- A12: retrieval over a node table (graph.py:3056-3162 query_hmsg_object and the GEMV of
  * query_hmsg_room / query_floor).  A table is N node embeddings (f64, as after load_hmsg_graph:
  * object.py:88-89, or f32 right after build) with a parent (room) id per node. */
