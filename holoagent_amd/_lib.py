@@ -157,6 +157,10 @@ _SIGS = {
     "hmsg_crop_resize_batch": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, C.c_double, C.c_int32, _P, _P, _P]),
     "hmsg_save_objects": (C.c_int, [_P, C.c_char_p, C.c_int64, _P, C.c_int32]),
     "hmsg_graph_allgather_index": (C.c_int, [_P, _P, _P, C.POINTER(_P), _P, _P, _P]),
+    "hmsg_graph_query_sharded": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P,
+                                           _P, _P, _P, _P, _P]),
+    "hmsg_graphs_query": (C.c_int, [C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P,
+                                    _P, _P, _P, _P, _P]),
     "hmsg_comm_send": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32]),
     "hmsg_comm_recv": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32]),
     "hmsg_merge_tree_sharded": (C.c_int, [_P, _P, C.c_int32, C.POINTER(C.c_int32)]),
@@ -884,6 +888,73 @@ class SceneGraph:
                                            None if T_room is None else _ptr(T_room), _ptr(floor_id), _ptr(room_mode), int(k), int(use_negatives), RM,
                                            _ptr(sel), _ptr(nsel), _ptr(idx), _ptr(room), _ptr(score)))
         return [sel[q, : nsel[q]].tolist() for q in range(Q)], idx, room, score
+
+    def query_sharded(self, comm: "Comm", T_obj, qid, T_room, floor_id, room_mode, k, use_negatives=True, room_name_emb=None, max_rooms=None):
+        """hmsg_graph_query_sharded: one call per rank with the same queries; the answer of hmsg_query_hier on the concatenated tables,
+        on every rank, with no table gathered.  -> (sel, idx, room, score, node_off, room_off, floor_off), offsets [world + 1]."""
+        rn = None if room_name_emb is None else np.ascontiguousarray(np.asarray(room_name_emb, np.float64))
+        if max_rooms is None:       # max(rooms of ALL ranks, 10), as the concatenated index's query_hier: the header exchange alone (Q = 0)
+            roff = np.zeros(comm.world + 1, np.int64)
+            self._ck(self.L.c.hmsg_graph_query_sharded(self.g, comm.h, None if rn is None else _ptr(rn), 0, 1, None, None, None, None, None, 1,
+                                                       int(use_negatives), 1, None, None, None, None, None, None, _ptr(roff), None))
+            max_rooms = max(int(roff[-1]), 10)
+        a = _sharded_args(T_obj, qid, T_room, floor_id, room_mode, k, max_rooms, comm.world)
+        self._ck(self.L.c.hmsg_graph_query_sharded(self.g, comm.h, None if rn is None else _ptr(rn), *a["args"], int(use_negatives),
+                                                   *a["outs"]))
+        return a["result"]()
+
+
+def _sharded_args(T_obj, qid, T_room, floor_id, room_mode, k, max_rooms, n):
+    """the query arguments and output arrays of hmsg_graph_query_sharded / hmsg_graphs_query (use_negatives goes between them)"""
+    T_obj = np.ascontiguousarray(T_obj, dtype=np.float32)
+    Q, Cn, D = T_obj.shape
+    T_room = None if T_room is None else np.ascontiguousarray(T_room, dtype=np.float32)
+    qid = np.ascontiguousarray(qid, dtype=np.int32)
+    floor_id = np.ascontiguousarray(floor_id, dtype=np.int32)
+    room_mode = np.ascontiguousarray(room_mode, dtype=np.int32)
+    RM, k = int(max_rooms), int(k)
+    sel, nsel = np.empty((Q, RM), np.int32), np.zeros((Q,), np.int32)
+    idx, room, score = np.empty((Q, k), np.int32), np.empty((Q, k), np.int32), np.empty((Q, k), np.float64)
+    noff, roff, foff = (np.zeros(n + 1, np.int64) for _ in range(3))
+    keep = (T_obj, T_room, qid, floor_id, room_mode)
+    args = (Q, Cn, _ptr(T_obj), _ptr(qid), None if T_room is None else _ptr(T_room), _ptr(floor_id), _ptr(room_mode), k)
+    outs = (RM, _ptr(sel), _ptr(nsel), _ptr(idx), _ptr(room), _ptr(score), _ptr(noff), _ptr(roff), _ptr(foff))
+    return dict(keep=keep, args=args, outs=outs,
+                result=lambda: ([sel[q, : nsel[q]].tolist() for q in range(Q)], idx, room, score, noff, roff, foff))
+
+
+def query_graphs(graphs, room_name_embs, T_obj, qid, T_room, floor_id, room_mode, k, use_negatives=True, max_rooms=None):
+    """hmsg_graphs_query: the sharded query over several SceneGraphs held by this process on one device (a multi-building service):
+    the answer of hmsg_query_hier on the concatenated tables, with no concatenated table.  room_name_embs: one f64 [R_i, D] per graph,
+    or None (no label mode).  -> (sel, idx, room, score, node_off, room_off, floor_off), offsets [len(graphs) + 1]."""
+    graphs = list(graphs)
+    n = len(graphs)
+    assert n >= 1
+    L = graphs[0].L
+    if max_rooms is None:
+        max_rooms = max(sum(g.counts()["rooms"] for g in graphs), 10)
+    a = _sharded_args(T_obj, qid, T_room, floor_id, room_mode, k, max_rooms, n)
+    gs = (_P * n)(*[g.g for g in graphs])
+    rns = None
+    if room_name_embs is not None:
+        rn = [None if r is None else np.ascontiguousarray(np.asarray(r, np.float64)) for r in room_name_embs]
+        assert len(rn) == n
+        rns = (_P * n)(*[None if r is None else r.ctypes.data for r in rn])
+    rc = L.c.hmsg_graphs_query(n, C.cast(gs, _P), None if rns is None else C.cast(rns, _P), *a["args"], int(use_negatives), *a["outs"])
+    if rc != 0:
+        raise HmsgError(L.c.hmsg_graph_last_error(graphs[0].g).decode() + f" (rc={rc})")
+    return a["result"]()
+
+
+def sharded_query_bytes(world, Q, k, rooms, floors, floor_rooms, label=True, view=False):
+    """bytes ONE rank receives per hmsg_graph_query_sharded call (include/hmsg.h): its header, room and candidate all-gathers, its own
+    slots included; summed over the ranks the traffic is about `world` times this.  rooms / floors / floor_rooms: the largest count of
+    any rank."""
+    a16 = lambda b: (b + 15) // 16 * 16
+    R, F, FR = max(rooms, 1), max(floors, 1), max(floor_rooms, 1)
+    room = (a16(Q * R * 8) if label else 0) + (a16(Q * R * 8) if view else 0) + a16(4 * (F + 1)) + a16(4 * FR) + 2 * a16(4 * R)
+    cand = a16(Q * 2 * k * 24) + a16(Q * 4)
+    return world * (128 + room + cand)
 
 
 ROOM_NAMES_OBJ_EMBEDDING, ROOM_NAMES_VIEW_EMBEDDING = 1, 2     # include/hmsg.h: HMSG_ROOM_NAMES_*

@@ -16,6 +16,7 @@
 
 #include <algorithm>
 
+#include <functional>
 #include <mutex>
 
 // (device code is not linked across translation units: the two small kernels this file needs are stated here)
@@ -98,11 +99,13 @@ void rccl_try(int rc, const char* what) {
 
 }  // namespace
 
+#define HMSG_COMM_HDR_BYTES 128
 struct hmsg_comm {
     rcclComm_t comm = nullptr;
     int rank = 0, world = 1, device = 0;
     std::string err;
     unsigned* flag = nullptr;       // 4 bytes of HBM for the ranks' agreement (made with the communicator: agreeing must not need an allocation)
+    char* hdr = nullptr;            // [world][HMSG_COMM_HDR_BYTES] of HBM for the sharded query's header exchange (the same reason)
 };
 
 namespace {
@@ -193,6 +196,7 @@ int hmsg_comm_create(const uint8_t* id, int32_t rank, int32_t world, int32_t dev
         memcpy(uid.internal, id, sizeof(uid.internal));
         rccl_try(rccl().CommInitRank(&c->comm, world, uid, rank), "ncclCommInitRank");
         HIP_TRY(hipMalloc((void**)&c->flag, 64));
+        HIP_TRY(hipMalloc((void**)&c->hdr, (size_t)world * HMSG_COMM_HDR_BYTES));
     });
     if (rc != HMSG_OK) {
         delete c;
@@ -206,6 +210,7 @@ void hmsg_comm_destroy(hmsg_comm_t* c) {
     if (!c) return;
     if (c->comm) (void)rccl().CommDestroy(c->comm);
     if (c->flag) (void)hipFree(c->flag);
+    if (c->hdr) (void)hipFree(c->hdr);
     delete c;
 }
 
@@ -360,6 +365,36 @@ void hmsg_comm_allgather_bytes(hmsg_ctx* h, hmsg_comm* c, const void* mine, size
 int hmsg_comm_rank(const hmsg_comm* c) { return c->rank; }
 int hmsg_comm_world(const hmsg_comm* c) { return c->world; }
 void hmsg_comm_set_error(hmsg_comm* c, const std::string& e) { c->err = e; }
+int hmsg_comm_device(const hmsg_comm* c) { return c->device; }
+// (hmsg_query_sharded.hip) local_phase_then_agree for another translation unit (no communicator at all: f runs, what it throws
+// passes through); an all-gather of `slot_bytes` per rank IN PLACE on the device: buf = [world][slot_bytes] with this rank's slot
+// filled (ncclAllGather from buf + rank * slot_bytes; no communicator: the identity); and the header exchange: `bytes` (at most
+// HMSG_COMM_HDR_BYTES) of this rank's host words -> every rank's, through the buffer made with the communicator (no allocation)
+void hmsg_comm_local_phase_then_agree(hmsg_comm* c, hipStream_t s, const char* what, const std::function<void()>& f) {
+    if (!c) {
+        f();
+        return;
+    }
+    local_phase_then_agree(c, s, what, f);
+}
+void hmsg_comm_allgather_header(hmsg_comm* c, const void* mine, size_t bytes, void* all, hipStream_t s) {
+    if (bytes > HMSG_COMM_HDR_BYTES) throw hmsg_error{HMSG_ERR_INVALID, "hmsg_comm_allgather_header: header too long"};
+    if (!c->comm) {
+        memcpy(all, mine, bytes);
+        return;
+    }
+    HIP_TRY(hipMemcpyAsync(c->hdr + (size_t)c->rank * HMSG_COMM_HDR_BYTES, mine, bytes, hipMemcpyHostToDevice, s));
+    rccl_try(rccl().AllGather(c->hdr + (size_t)c->rank * HMSG_COMM_HDR_BYTES, c->hdr, HMSG_COMM_HDR_BYTES, RCCL_INT8, c->comm, s), "ncclAllGather (header)");
+    std::vector<char> h((size_t)c->world * HMSG_COMM_HDR_BYTES);
+    HIP_TRY(hipMemcpyAsync(h.data(), c->hdr, h.size(), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int r = 0; r < c->world; ++r) memcpy((char*)all + (size_t)r * bytes, h.data() + (size_t)r * HMSG_COMM_HDR_BYTES, bytes);
+}
+void hmsg_comm_allgather_inplace(hmsg_comm* c, void* buf, size_t slot_bytes, hipStream_t s) {
+    if (!c->comm || !slot_bytes) return;
+    char* b = (char*)buf;
+    rccl_try(rccl().AllGather(b + (size_t)c->rank * slot_bytes, b, slot_bytes, RCCL_INT8, c->comm, s), "ncclAllGather (sharded query)");
+}
 
 extern "C" {
 

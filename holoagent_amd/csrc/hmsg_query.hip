@@ -15,51 +15,10 @@
 // MI355X design: the table stays in HBM as float64; all Q x C text rows are scored against ALL nodes by
 // one f64-MFMA GEMM (v_mfma_f64_16x16x4_f64), then one workgroup per query walks its candidate rooms
 // (CSR room -> nodes) and keeps an exact top-k.
-#include "hmsg_common.h"
+#include "hmsg_query.h"
 
 #include <algorithm>
 #include <chrono>
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-struct hmsg_index {
-    int device = 0;
-    int D = 0;
-    long long N = 0;
-    int n_rooms = 0;
-    hipStream_t stream = nullptr;
-    std::string err;
-    DevBuf<double> E;            // [N][D]
-    DevBuf<int> room_of;         // [N]
-    DevBuf<int> room_off;        // [n_rooms + 1]   CSR room -> nodes (ascending node index)
-    DevBuf<int> room_nodes;      // [N]
-    std::vector<int> h_room_cnt;
-    DevBuf<double> T64, S;       // scratch: text rows in f64, similarity matrix
-    DevBuf<float> Tf;
-    DevBuf<int> d_qid, d_roff, d_rooms, d_oidx, d_oroom;
-    DevBuf<double> d_oscore;
-    // the hierarchy above the nodes (hmsg_index_set_hierarchy): floors -> rooms, room name / view embeddings
-    bool have_hier = false;
-    int n_floors = 0, h_rooms = 0;
-    long long n_views = 0;
-    DevBuf<double> room_name_emb;   // [n_rooms][D]  CLIP text embedding of the room's name (label mode)
-    DevBuf<double> view_emb;        // [n_views][D]  room.embeddings (view mode)
-    DevBuf<int> view_off;           // [n_rooms + 1]
-    DevBuf<int> room_key;           // [n_rooms]     int(room_id.split("_")[-1]): what the view mode returns
-    DevBuf<int> floor_room_off;     // [n_floors + 1]
-    DevBuf<int> floor_rooms;        // rooms of floor f in floors[f].rooms order (global room ids)
-    DevBuf<double> S_room, S_view;  // scratch
-    DevBuf<float> Tr;
-    DevBuf<double> Tr64;
-    DevBuf<int> d_floor, d_mode, d_sel, d_nsel, d_err;
-    // hmsg_query_hier: the per-query words in (floor | mode | qid) and every result out (score | sel | nsel | err | idx | room) travel as
-    // ONE packed copy each way through pinned memory (round 5: three pageable uploads and six pageable read-backs per call)
-    PinnedBuf<int> h_qin;
-    DevBuf<int> d_qin;
-    PinnedBuf<char> h_qout;
-    DevBuf<char> d_qout;
-    Prof prof;                   // live timing of the GEMM (hmsg_index_set_profiling)
-};
 
 __global__ void k_f32_to_f64(const float* __restrict__ a, double* __restrict__ b, size_t n) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -440,17 +399,45 @@ void gemm(hmsg_index* ix, const double* A, int M, double* S, const double* B = n
         B = ix->E.p;
         N = ix->N;
     }
-    if (M >= 64 && N >= 64) {
-        const long long tiles = (long long)((M + GT - 1) / GT) * ((N + GT - 1) / GT);
+    if (M >= 64 && N >= 64) {                // (the tiled kernel: timed when profiling is on)
         ProfScope ps(ix->prof, ix->stream, "k_gemm_f64", 2.0 * (double)M * (double)N * (double)ix->D);
-        hipLaunchKernelGGL(k_gemm_f64_tiled, dim3((unsigned)tiles), dim3(256), 0, ix->stream, A, B, M, N, ix->D, S);
-        HMSG_CHECK_LAUNCH();
+        hmsg_gemm_f64(A, M, B, N, ix->D, S, ix->stream);
         return;
     }
-    long long tiles = (long long)((M + 15) / 16) * ((N + 15) / 16);
-    hipLaunchKernelGGL(k_gemm_f64, dim3(cdiv((size_t)tiles, 4)), dim3(256), 0, ix->stream, A, B, M, N, ix->D, S);
+    hmsg_gemm_f64(A, M, B, N, ix->D, S, ix->stream);
+}
+}  // namespace
+
+void hmsg_gemm_f64(const double* A, int M, const double* B, long long N, int D, double* S, hipStream_t s) {
+    if (M <= 0 || N <= 0) return;
+    if (M >= 64 && N >= 64) {
+        const long long tiles = (long long)((M + GT - 1) / GT) * ((N + GT - 1) / GT);
+        hipLaunchKernelGGL(k_gemm_f64_tiled, dim3((unsigned)tiles), dim3(256), 0, s, A, B, M, N, D, S);
+    } else {
+        const long long tiles = (long long)((M + 15) / 16) * ((N + 15) / 16);
+        hipLaunchKernelGGL(k_gemm_f64, dim3(cdiv((size_t)tiles, 4)), dim3(256), 0, s, A, B, M, N, D, S);
+    }
     HMSG_CHECK_LAUNCH();
 }
+
+hmsg_index* hmsg_index_create_rooms_only(int device, int D) {
+    hmsg_index* ix = new hmsg_index();
+    ix->device = device;
+    ix->D = D;
+    try {
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking));
+        ix->room_off.alloc(1);
+        const int zero = 0;
+        HIP_TRY(hipMemcpy(ix->room_off.p, &zero, 4, hipMemcpyHostToDevice));
+    } catch (...) {
+        hmsg_index_destroy(ix);
+        throw;
+    }
+    return ix;
+}
+
+namespace {
 void text_to_f64(hmsg_index* ix, const float* T, size_t n) {
     ix->T64.ensure(n);
     const float* src = T;

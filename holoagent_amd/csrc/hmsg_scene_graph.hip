@@ -11,6 +11,7 @@
 // after hmsg_finalize_map) and hmsg_graph_finish (after hmsg_pool_instances): beside the fusion and the merge fold.
 #include "hmsg_common.h"
 #include "hmsg_dbscan.h"
+#include "hmsg_query.h"
 
 #include <dirent.h>
 #include <sys/stat.h>
@@ -87,6 +88,9 @@ struct GObject {
 
 }  // namespace
 
+struct hmsg_shard_ws;                       // (hmsg_query_sharded.hip)
+void hmsg_shard_ws_free(hmsg_shard_ws* w);
+
 struct hmsg_graph {
     hmsg_ctx* h = nullptr;                  // built graphs: the scene (object clouds and features stay in HBM); NULL after hmsg_load
     int device = 0, D = 0;
@@ -111,10 +115,16 @@ struct hmsg_graph {
     bool failed = false;                    // hmsg_graph_finish threw half way: views / objects are partly appended -- the graph only accepts hmsg_graph_destroy
     double t_begin_ms = 0, t_finish_ms = 0, t_kmeans_wait_ms = 0;
     hmsg_index_t* ix = nullptr;             // hmsg_graph_query's index (made on first use)
+    hmsg_index_t* shard_ix = nullptr;       // the graph as a shard of hmsg_graph_query_sharded / hmsg_graphs_query: its own index, made
+                                            // without room names (they come with every call); the levels above the nodes only for a
+                                            // graph without objects.  hmsg_graph_query's `ix` is never touched by that path.
+    hmsg_shard_ws* shard_ws = nullptr;      // that path's scratch, kept between calls (hmsg_query_sharded.hip)
     ~hmsg_graph() {
         for (auto& t : workers)
             if (t.joinable()) t.join();
         if (ix) hmsg_index_destroy(ix);
+        if (shard_ix) hmsg_index_destroy(shard_ix);
+        if (shard_ws) hmsg_shard_ws_free(shard_ws);
     }
 };
 
@@ -1389,69 +1399,96 @@ int hmsg_load(const char* dir, int32_t device_id, hmsg_graph_t** out) {
     return HMSG_OK;
 }
 
+}  // extern "C"
+
+namespace {
+// hmsg_graph_index; rooms_only: the levels above the nodes into an index without a node table (a graph without objects)
+void graph_make_index(hmsg_graph* g, const double* room_name_emb, bool rooms_only, hmsg_index_t** out) {
+    HMSG_REQUIRE(g->finished, HMSG_ERR_INVALID, "hmsg_graph_index: the graph is not finished");
+    HMSG_REQUIRE(rooms_only || !g->objects.empty(), HMSG_ERR_INVALID, "hmsg_graph_index: a graph without objects");
+    hmsg_index_t* ix = nullptr;
+    const int D = g->D;
+    if (rooms_only) {
+        ix = hmsg_index_create_rooms_only(g->device, D);
+    } else if (!g->loaded && !g->merged) {
+        need(hmsg_index_from_nodes(g->h, &ix), g->h, "hmsg_index_from_nodes");
+    } else if (g->merged && !g->loaded) {
+        // merged objects are no rows of the scene's node table any more: the table of the graph's own objects
+        std::vector<float> emb(g->objects.size() * (size_t)D);
+        std::vector<int32_t> room(g->objects.size());
+        for (size_t k = 0; k < g->objects.size(); ++k) {
+            memcpy(&emb[k * (size_t)D], g->objects[k].emb32.data(), (size_t)D * 4);
+            room[k] = g->objects[k].room;
+        }
+        if (hmsg_index_create(g->device, D, (int64_t)g->objects.size(), emb.data(), 0, room.data(), &ix) != HMSG_OK)
+            throw hmsg_error{HMSG_ERR_INVALID, "hmsg_index_create failed"};
+    } else {
+        std::vector<double> emb(g->objects.size() * (size_t)D);
+        std::vector<int32_t> room(g->objects.size());
+        for (size_t k = 0; k < g->objects.size(); ++k) {
+            HMSG_REQUIRE((int)g->objects[k].emb.size() == D, HMSG_ERR_INVALID, "hmsg_graph_index: object " + g->objects[k].id + " was saved without an embedding");
+            memcpy(&emb[k * (size_t)D], g->objects[k].emb.data(), (size_t)D * 8);
+            room[k] = g->objects[k].room;
+        }
+        if (hmsg_index_create(g->device, D, (int64_t)g->objects.size(), emb.data(), 1, room.data(), &ix) != HMSG_OK)
+            throw hmsg_error{HMSG_ERR_INVALID, "hmsg_index_create failed"};
+    }
+    const int R = (int)g->rooms.size();
+    std::vector<int32_t> fro(1, 0), fr, key((size_t)R);
+    for (auto& fl : g->floors) {
+        for (int r : fl.rooms) fr.push_back(r);
+        fro.push_back((int32_t)fr.size());
+    }
+    std::vector<int64_t> voff(1, 0);
+    std::vector<double> vemb;
+    for (int r = 0; r < R; ++r) {
+        const GRoom& rm = g->rooms[(size_t)r];
+        const size_t us = rm.id.rfind('_');
+        key[(size_t)r] = atoi(rm.id.c_str() + (us == std::string::npos ? 0 : us + 1));
+        if (g->loaded) vemb.insert(vemb.end(), rm.emb64.begin(), rm.emb64.end());
+        else
+            for (float x : rm.emb) vemb.push_back((double)x);
+        voff.push_back(voff.back() + rm.n_emb);
+    }
+    const int rc = hmsg_index_set_hierarchy(ix, R, (int32_t)g->floors.size(), fro.data(), fr.data(), room_name_emb, voff.data(), vemb.empty() ? nullptr : vemb.data(),
+                                            key.data());
+    if (rc != HMSG_OK) {
+        std::string e = hmsg_index_last_error(ix);
+        hmsg_index_destroy(ix);
+        throw hmsg_error{rc, "hmsg_index_set_hierarchy: " + e};
+    }
+    *out = ix;
+}
+}  // namespace
+
+extern "C" {
+
 /* the retrieval index of the graph with its upper levels resident (Graph._hier_index of the mirror): object embeddings (gathered
  * on the device for a built graph, the saved float64 rows for a loaded one), floors -> rooms, the rooms' view embeddings,
  * room_key = int(room_id.split("_")[-1]); room_name_emb f64 [rooms][D] or NULL (no label mode) */
 int hmsg_graph_index(hmsg_graph_t* g, const double* room_name_emb, hmsg_index_t** out) {
     if (!g || !out) return HMSG_ERR_INVALID;
     *out = nullptr;
-    return gguard(g, [&] {
-        HMSG_REQUIRE(g->finished, HMSG_ERR_INVALID, "hmsg_graph_index: the graph is not finished");
-        HMSG_REQUIRE(!g->objects.empty(), HMSG_ERR_INVALID, "hmsg_graph_index: a graph without objects");
-        hmsg_index_t* ix = nullptr;
-        const int D = g->D;
-        if (!g->loaded && !g->merged) {
-            need(hmsg_index_from_nodes(g->h, &ix), g->h, "hmsg_index_from_nodes");
-        } else if (g->merged && !g->loaded) {
-            // merged objects are no rows of the scene's node table any more: the table of the graph's own objects
-            std::vector<float> emb(g->objects.size() * (size_t)D);
-            std::vector<int32_t> room(g->objects.size());
-            for (size_t k = 0; k < g->objects.size(); ++k) {
-                memcpy(&emb[k * (size_t)D], g->objects[k].emb32.data(), (size_t)D * 4);
-                room[k] = g->objects[k].room;
-            }
-            if (hmsg_index_create(g->device, D, (int64_t)g->objects.size(), emb.data(), 0, room.data(), &ix) != HMSG_OK)
-                throw hmsg_error{HMSG_ERR_INVALID, "hmsg_index_create failed"};
-        } else {
-            std::vector<double> emb(g->objects.size() * (size_t)D);
-            std::vector<int32_t> room(g->objects.size());
-            for (size_t k = 0; k < g->objects.size(); ++k) {
-                HMSG_REQUIRE((int)g->objects[k].emb.size() == D, HMSG_ERR_INVALID, "hmsg_graph_index: object " + g->objects[k].id + " was saved without an embedding");
-                memcpy(&emb[k * (size_t)D], g->objects[k].emb.data(), (size_t)D * 8);
-                room[k] = g->objects[k].room;
-            }
-            if (hmsg_index_create(g->device, D, (int64_t)g->objects.size(), emb.data(), 1, room.data(), &ix) != HMSG_OK)
-                throw hmsg_error{HMSG_ERR_INVALID, "hmsg_index_create failed"};
-        }
-        const int R = (int)g->rooms.size();
-        std::vector<int32_t> fro(1, 0), fr, key((size_t)R);
-        for (auto& fl : g->floors) {
-            for (int r : fl.rooms) fr.push_back(r);
-            fro.push_back((int32_t)fr.size());
-        }
-        std::vector<int64_t> voff(1, 0);
-        std::vector<double> vemb;
-        for (int r = 0; r < R; ++r) {
-            const GRoom& rm = g->rooms[(size_t)r];
-            const size_t us = rm.id.rfind('_');
-            key[(size_t)r] = atoi(rm.id.c_str() + (us == std::string::npos ? 0 : us + 1));
-            if (g->loaded) vemb.insert(vemb.end(), rm.emb64.begin(), rm.emb64.end());
-            else
-                for (float x : rm.emb) vemb.push_back((double)x);
-            voff.push_back(voff.back() + rm.n_emb);
-        }
-        const int rc = hmsg_index_set_hierarchy(ix, R, (int32_t)g->floors.size(), fro.data(), fr.data(), room_name_emb, voff.data(), vemb.empty() ? nullptr : vemb.data(),
-                                                key.data());
-        if (rc != HMSG_OK) {
-            std::string e = hmsg_index_last_error(ix);
-            hmsg_index_destroy(ix);
-            throw hmsg_error{rc, "hmsg_index_set_hierarchy: " + e};
-        }
-        *out = ix;
-    });
+    return gguard(g, [&] { graph_make_index(g, room_name_emb, false, out); });
 }
 
 }  // extern "C"
+
+// (hmsg_query_sharded.hip) the graph as one shard of the sharded query: its own resident index, made on first use WITHOUT room
+// names (the sharded calls pass them every time) -- for a graph without objects one with the levels above the nodes only; the
+// index of hmsg_graph_query stays as that call makes it.  Throws what makes the graph no shard (not finished, failed half way, no
+// embedding length).  *n_floor_rooms: the length of the floors' room lists.
+hmsg_index_t* hmsg_graph_shard_index(hmsg_graph* g, int* n_floor_rooms) {
+    *n_floor_rooms = 0;
+    for (auto& fl : g->floors) *n_floor_rooms += (int)fl.rooms.size();
+    HMSG_REQUIRE(g->finished && !g->failed, HMSG_ERR_INVALID, "hmsg_graph_query_sharded: a graph built by hmsg_graph_finish or loaded by hmsg_load");
+    HMSG_REQUIRE(g->D > 0, HMSG_ERR_INVALID, "hmsg_graph_query_sharded: the graph has no embeddings (D unknown)");
+    if (!g->shard_ix) graph_make_index(g, nullptr, g->objects.empty(), &g->shard_ix);
+    return g->shard_ix;
+}
+hmsg_shard_ws*& hmsg_graph_shard_ws(hmsg_graph* g) { return g->shard_ws; }
+int hmsg_graph_device(const hmsg_graph* g) { return g->device; }
+void hmsg_graph_set_error(hmsg_graph* g, const std::string& e) { g->err = e; }
 // (hmsg_comm.hip)
 struct hmsg_comm;
 void hmsg_comm_allgather_bytes(hmsg_ctx* h, hmsg_comm* c, const void* mine, size_t my_bytes, std::vector<std::vector<char>>& all);

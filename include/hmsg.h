@@ -671,6 +671,44 @@ int hmsg_merge_tree_sharded(hmsg_t* h, hmsg_comm_t* c, int32_t total_frames, int
  * exact, float32 sums up to summation order) and the voxel features refreshed.  After hmsg_fuse_frames, before pooling. */
 int hmsg_allreduce_feature_sums(hmsg_t* h, hmsg_comm_t* c);
 
+/* ---- the sharded query (scene per GPU): hmsg_query_hier over several scene graphs whose tables stay where they are.
+ * Contract: for the same queries the answer is, bit for bit, what hmsg_query_hier returns on ONE index over the concatenated tables
+ * (the index hmsg_graph_allgather_index makes for built graphs) -- out_sel, out_nsel, out_idx, out_room and the float64 out_score, every
+ * room mode, floor -1 or any global floor id, use_negatives 0 / 1, any k, and HMSG_ERR_INVALID where hmsg_query_hier raises (a room
+ * without view embeddings in view mode; a view key that is no position of the list; the outputs are written first, as there).
+ * Global ids, in shard order 0 .. n-1 (= rank order): node = node_off[s] + local node, room = room_off[s] + local room, floor =
+ * floor_off[s] + local floor (offsets [n + 1], optional).  Shards may be built graphs (hmsg_graph_finish), loaded graphs (hmsg_load) or
+ * a mix; a graph without objects takes part with its rooms.  Every table is float64 in HBM on its own shard: each graph keeps its own
+ * resident index for this path (made on the first call, without room names -- they come with every call; the index hmsg_graph_query
+ * makes and caches is not touched) and its scratch, both freed with the graph.
+ * room_name_emb: the shard's rooms [R_local][D] f64 (host or device) or NULL; when any query is in label mode it must be given on every
+ * shard -- a shard without it makes every shard return HMSG_ERR_INVALID.
+ * max_rooms: the capacity of out_sel [Q][max_rooms]; hmsg_query_hier's callers pass max(rooms of the concatenated table, 10), and
+ * the same here gives the same sel (a smaller value cuts sel, the same way on both).  Q = 0 reads no query array: the call is the
+ * header exchange alone and fills the offsets, e.g. room_off[n] to size max_rooms.
+ *   hmsg_graph_query_sharded  one call per rank, every rank with the same queries; every rank receives the whole answer.  The first
+ *        exchange carries every rank's own preconditions (arguments, graph finished, label mode with room_name_emb, D) and its query
+ *        arguments (Q, C, k, max_rooms, use_negatives, a hash of the floor ids and room modes): a rank that fails them, or differs, makes
+ *        every rank return HMSG_ERR_INVALID -- nobody is left waiting -- and every rank-local phase after it ends in an agreement (a 4-byte
+ *        all-reduce).  With c from hmsg_comm_create(NULL, 0, 1, ...) (one rank, no communicator) it equals hmsg_graph_query.
+ *        What ONE rank receives per call (its own slot included; summed over W ranks about W times this), R = the largest room count of
+ *        a rank, F / FR its floor count / floor-list length:
+ *          the header all-gather   W x 128 bytes;
+ *          the room all-gather     W x [Q*R*8 per room row kind in use (label names; views: the best view per room) + 4*(F + 1 + FR + 2R)],
+ *                                  each section rounded up to 16 bytes;
+ *          the candidate all-gather  W x [Q*2k*24 + Q*4] (k plain + k negative-filtered records, and a count, per query),
+ *        plus the 4-byte agreements.  No table is gathered: a changed, reloaded or added scene changes nothing on the other ranks.
+ *   hmsg_graphs_query  the same answer for n graphs held by this process on ONE device (a multi-building service): no communicator,
+ *        each shard writes its slots of the exchange in place on one stream. */
+int hmsg_graph_query_sharded(hmsg_graph_t* g, hmsg_comm_t* c, const double* room_name_emb, int32_t Q, int32_t C, const float* T_obj,
+                             const int32_t* qid, const float* T_room, const int32_t* floor_id, const int32_t* room_mode, int32_t k,
+                             int32_t use_negatives, int32_t max_rooms, int32_t* out_sel, int32_t* out_nsel, int32_t* out_idx, int32_t* out_room,
+                             double* out_score, int64_t* node_off, int64_t* room_off, int64_t* floor_off);
+int hmsg_graphs_query(int32_t n, hmsg_graph_t* const* graphs, const double* const* room_name_embs, int32_t Q, int32_t C, const float* T_obj,
+                      const int32_t* qid, const float* T_room, const int32_t* floor_id, const int32_t* room_mode, int32_t k, int32_t use_negatives,
+                      int32_t max_rooms, int32_t* out_sel, int32_t* out_nsel, int32_t* out_idx, int32_t* out_room, double* out_score,
+                      int64_t* node_off, int64_t* room_off, int64_t* floor_off);
+
 
 #ifdef __cplusplus
 }
