@@ -65,20 +65,9 @@ bool hmsg_resolve_ties(hmsg_ctx* h, TieBuf& tb, int* target) {
 
 namespace {
 
-bool is_device_ptr(const void* p) {
-    hipPointerAttribute_t a;
-    memset(&a, 0, sizeof(a));
-    hipError_t e = hipPointerGetAttributes(&a, p);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return a.type == hipMemoryTypeDevice;
-}
-
 void copy_in(void* dst, const void* src, size_t bytes, hipStream_t s) {
     if (!bytes) return;
-    HIP_TRY(hipMemcpyAsync(dst, src, bytes, is_device_ptr(src) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(dst, src, bytes, hmsg_is_device_ptr(src) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
 }
 
 template <typename F>
@@ -322,7 +311,7 @@ int hmsg_add_frames(hmsg_t* h, int32_t n, const uint8_t* rgb, const uint16_t* de
         HMSG_REQUIRE(!h->map_ready, HMSG_ERR_INVALID, "hmsg_add_frames after hmsg_finalize_map");
         HMSG_REQUIRE(!h->frames_released, HMSG_ERR_INVALID, "hmsg_add_frames: the frame store was released (hmsg_reset first)");
         double Kh[9];
-        if (is_device_ptr(K)) {
+        if (hmsg_is_device_ptr(K)) {
             HIP_TRY(hipMemcpy(Kh, K, sizeof(Kh), hipMemcpyDeviceToHost));
         } else {
             memcpy(Kh, K, sizeof(Kh));
@@ -408,7 +397,7 @@ int hmsg_add_frame_features(hmsg_t* h, int32_t first, int32_t n, int32_t M, cons
         // per-frame mask counts (host copy kept: the 3-D mask store holds nmask[f] clouds for frame f)
         std::vector<int> nm((size_t)n, M);
         if (n_masks) {
-            if (is_device_ptr(n_masks)) {
+            if (hmsg_is_device_ptr(n_masks)) {
                 HIP_TRY(hipMemcpy(nm.data(), n_masks, (size_t)n * 4, hipMemcpyDeviceToHost));
             } else {
                 memcpy(nm.data(), n_masks, (size_t)n * 4);
@@ -425,7 +414,7 @@ int hmsg_add_frame_features(hmsg_t* h, int32_t first, int32_t n, int32_t M, cons
             h->n_feat_frames += n;
             return;
         }
-        const bool dev = is_device_ptr(masks);
+        const bool dev = hmsg_is_device_ptr(masks);
         const int chunk = dev ? n : std::max(1, (int)(((size_t)512 << 20) / ((size_t)M * HW)));
         DevBuf<unsigned char> st_m;
         DevBuf<float> st_f;
@@ -438,7 +427,7 @@ int hmsg_add_frame_features(hmsg_t* h, int32_t first, int32_t n, int32_t M, cons
                 HIP_TRY(hipMemcpyAsync(st_m.p, dm, (size_t)nc * M * HW, hipMemcpyHostToDevice, h->stream));
                 dm = st_m.p;
             }
-            if (!is_device_ptr(F_g) || !is_device_ptr(F_masked) || !is_device_ptr(F_crop)) {
+            if (!hmsg_is_device_ptr(F_g) || !hmsg_is_device_ptr(F_masked) || !hmsg_is_device_ptr(F_crop)) {
                 st_f.ensure((size_t)nc * (2 * M + 1) * D);
                 float* g = st_f.p;
                 float* fm = g + (size_t)nc * D;
@@ -527,9 +516,9 @@ int hmsg_get_feature_sums(const hmsg_t* hc, float* sum, uint32_t* counter) {
         const size_t n = (size_t)h->V * h->cfg.feat_dim;
         // (on the handle's own stream -- ordered behind whatever produced the sums -- and complete before the call returns:
         //  the caller's stream has no ordering against ours)
-        if (sum && n) HIP_TRY(hipMemcpyAsync(sum, h->sum.p, n * 4, is_device_ptr(sum) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+        if (sum && n) HIP_TRY(hipMemcpyAsync(sum, h->sum.p, n * 4, hmsg_is_device_ptr(sum) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
         if (counter && h->V)
-            HIP_TRY(hipMemcpyAsync(counter, h->cnt.p, (size_t)h->V * 4, is_device_ptr(counter) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(hipMemcpyAsync(counter, h->cnt.p, (size_t)h->V * 4, hmsg_is_device_ptr(counter) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
     });
 }
@@ -621,7 +610,7 @@ int hmsg_get_instance_points(const hmsg_t* hc, double* xyz) {
     return guard(h, [&] {
         HMSG_REQUIRE((h->merged || h->tree_partial) && xyz, HMSG_ERR_INVALID, "hmsg_merge_instances not run");
         if (h->inst.total) {
-            if (is_device_ptr(xyz)) {
+            if (hmsg_is_device_ptr(xyz)) {
                 HIP_TRY(hipMemcpyAsync(xyz, h->inst.pts.p, (size_t)h->inst.total * 24, hipMemcpyDeviceToDevice, h->stream));
                 HIP_TRY(hipStreamSynchronize(h->stream));
             } else

@@ -349,6 +349,16 @@ inline void upload_pinned(void* dst_dev, const void* src_pinned, size_t bytes, h
     hipLaunchKernelGGL(k_upload16, dim3((unsigned)std::max<size_t>(1, std::min<size_t>((n16 + 255) / 256, 16))), dim3(256), 0, s, (const uint4*)src_pinned,
                        (uint4*)dst_dev, n16, (unsigned)(bytes % 16));
 }
+// whether p is device memory (a host pointer, registered or not, is not); leaves no sticky error behind
+inline bool hmsg_is_device_ptr(const void* p) {
+    hipPointerAttribute_t a;
+    memset(&a, 0, sizeof(a));
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    return a.type == hipMemoryTypeDevice;
+}
 struct SpinWait {
     hipEvent_t ev = nullptr;
     ~SpinWait() {

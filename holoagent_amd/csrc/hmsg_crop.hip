@@ -133,16 +133,6 @@ __global__ void __launch_bounds__(256) k_crop_resize(const unsigned char* __rest
     }
 }
 
-bool crop_is_device_ptr(const void* p) {
-    hipPointerAttribute_t a;
-    memset(&a, 0, sizeof(a));
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return a.type == hipMemoryTypeDevice;
-}
-
 // numpy slice [a : a + n) of an axis of length L, a >= 0, n > 0
 inline void clip_slice(long long a, long long n, int L, int& start, int& len) {
     const long long s = std::min<long long>(a, L), e = std::min<long long>(a + n, L);
@@ -207,19 +197,19 @@ extern "C" int hmsg_crop_resize_batch(int32_t device_id, int32_t H, int32_t W, c
             DevBuf<CropRect> d_rects;
             const unsigned char* p_img = image;
             const unsigned char* p_seg = segs;
-            if (!crop_is_device_ptr(image)) {
+            if (!hmsg_is_device_ptr(image)) {
                 d_img.alloc(img_bytes);
                 HIP_TRY(hipMemcpyAsync(d_img.p, image, img_bytes, hipMemcpyHostToDevice, s));
                 p_img = d_img.p;
             }
-            if (out_masked && !crop_is_device_ptr(segs)) {
+            if (out_masked && !hmsg_is_device_ptr(segs)) {
                 d_seg.alloc(seg_bytes);
                 HIP_TRY(hipMemcpyAsync(d_seg.p, segs, seg_bytes, hipMemcpyHostToDevice, s));
                 p_seg = d_seg.p;
             }
             unsigned char* p_plain = out_plain;
             unsigned char* p_masked = out_masked;
-            const bool plain_host = out_plain && !crop_is_device_ptr(out_plain), masked_host = out_masked && !crop_is_device_ptr(out_masked);
+            const bool plain_host = out_plain && !hmsg_is_device_ptr(out_plain), masked_host = out_masked && !hmsg_is_device_ptr(out_masked);
             if (plain_host) {
                 d_plain.alloc(crop_bytes * M);
                 p_plain = d_plain.p;

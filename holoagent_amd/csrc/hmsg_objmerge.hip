@@ -32,16 +32,6 @@ __device__ __forceinline__ float om_dist2(float x, float y, float z, float qx, f
     return d < 0.f ? 0.f : d;
 }
 
-bool om_device_ptr(const void* p) {
-    hipPointerAttribute_t a;
-    memset(&a, 0, sizeof(a));
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return a.type == hipMemoryTypeDevice;
-}
-
 struct OmTask {             // count the points of cloud x that have a point of cloud y within the radius
     long long x0, y0;       // first points (in the points buffer)
     int nx, ny;
@@ -165,7 +155,7 @@ void hmsg_pair_overlaps(hmsg_ctx* h, const double* points, const long long* star
         }
     const double* dpts = points;
     DevBuf<double> up;
-    if (!om_device_ptr(points)) {               // host clouds: the span the pairs touch goes up once
+    if (!hmsg_is_device_ptr(points)) {               // host clouds: the span the pairs touch goes up once
         up.alloc((size_t)std::max<long long>(hi - lo, 1) * 3);
         HIP_TRY(hipMemcpyAsync(up.p, points + (size_t)lo * 3, (size_t)(hi - lo) * 24, hipMemcpyHostToDevice, s));
         dpts = up.p - (size_t)lo * 3;

@@ -1,6 +1,7 @@
 // The resident retrieval index (hmsg_query.hip) as the other translation units that work on it see it: the sharded query
-// (hmsg_query_sharded.hip) runs its stages on every shard's own index.  Device code is not linked across translation units,
-// so what is shared here is host-side: the struct and the float64 GEMM dispatch.
+// (hmsg_query_sharded.hip) runs its stages on every shard's own index.  Shared here is the host side of a query: the struct, the
+// float64 GEMM dispatch, and what hmsg_query_hier and the sharded query do alike around their kernels (argument scan, text rows,
+// packed words in, packed results out).  The device-side rules both instantiate are in hmsg_query_rules.h.
 #pragma once
 #include "hmsg_common.h"
 
@@ -35,7 +36,6 @@ struct hmsg_index {
     DevBuf<double> S_room, S_view;  // scratch
     DevBuf<float> Tr;
     DevBuf<double> Tr64;
-    DevBuf<int> d_floor, d_mode, d_sel, d_nsel, d_err;
     // hmsg_query_hier: the per-query words in (floor | mode | qid) and every result out (score | sel | nsel | err | idx | room) travel as
     // ONE packed copy each way through pinned memory (round 5: three pageable uploads and six pageable read-backs per call)
     PinnedBuf<int> h_qin;
@@ -52,3 +52,39 @@ struct hmsg_index {
 void hmsg_gemm_f64(const double* A, int M, const double* B, long long N, int D, double* S, hipStream_t s);
 // an index without a node table, for hmsg_index_set_hierarchy only: a shard whose rooms hold no object (hmsg_query_sharded.hip)
 hmsg_index* hmsg_index_create_rooms_only(int device, int D);
+
+// ---- the host side of a coarse-to-fine query, shared by hmsg_query_hier and the sharded query ----
+// `who` is the caller's message prefix ("hmsg_query_hier", "hmsg_graph_query_sharded").
+
+// what the Q room modes / floor ids ask for
+struct QueryScan {
+    bool need_label = false, need_view = false;     // a query in label mode (1) / a view mode (2, 3)
+    bool in_range = true;                           // every mode in 0..3, every floor id >= -1
+    int max_floor = -1;
+};
+QueryScan hmsg_query_scan(int Q, const int* room_mode, const int* floor_id);
+// the failed precondition of a query with this scan on tables with n_floors floors, or "" (n_floors < 0: not known yet)
+std::string hmsg_query_precondition(const char* who, const QueryScan& sc, int n_floors, bool have_room_text, bool have_room_names);
+// n float32 text rows values (host or device) -> dst as float64, through tmp when they come from the host
+void hmsg_text_rows_to_f64(hipStream_t s, const float* src, size_t n, DevBuf<float>& tmp, DevBuf<double>& dst);
+// the per-query words, packed for one upload: h_words [floor Q | mode Q | qid Q].  Returns whether qid is device memory: then its
+// third is left out, and the caller copies qid there on the device once the words are up.
+bool hmsg_query_pack_words(int* h_words, int Q, const int* floor_id, const int* room_mode, const int* qid);
+// every result of a query as ONE packed buffer: [score f64 Q*k | sel Q*max_rooms | nsel Q | err Q | idx Q*k | room Q*k]
+struct QueryOut {
+    int Q, k, max_rooms;
+    size_t o_sel, o_nsel, o_err, o_idx, o_room, bytes;
+    QueryOut(int Q_, int k_, int max_rooms_)
+        : Q(Q_), k(k_), max_rooms(max_rooms_), o_sel((size_t)Q_ * k_ * 8), o_nsel(o_sel + (size_t)Q_ * max_rooms_ * 4), o_err(o_nsel + (size_t)Q_ * 4),
+          o_idx(o_err + (size_t)Q_ * 4), o_room(o_idx + (size_t)Q_ * k_ * 4), bytes(o_room + (size_t)Q_ * k_ * 4) {}
+    double* score(char* base) const { return (double*)base; }
+    int* sel(char* base) const { return (int*)(base + o_sel); }
+    int* nsel(char* base) const { return (int*)(base + o_nsel); }
+    int* err(char* base) const { return (int*)(base + o_err); }
+    int* idx(char* base) const { return (int*)(base + o_idx); }
+    int* room(char* base) const { return (int*)(base + o_room); }
+    // The results into the caller's arrays (host memory, or device memory -- the reference's callers take numpy arrays) from the
+    // device buffer d and its host copy h, then the room stage's verdict: throws when a query's err word is set.
+    void give(const char* who, hipStream_t s, const char* d, const char* h, double* out_score, int* out_sel, int* out_nsel, int* out_idx,
+              int* out_room) const;
+};

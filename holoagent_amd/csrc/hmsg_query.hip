@@ -16,6 +16,7 @@
 // one f64-MFMA GEMM (v_mfma_f64_16x16x4_f64), then one workgroup per query walks its candidate rooms
 // (CSR room -> nodes) and keeps an exact top-k.
 #include "hmsg_query.h"
+#include "hmsg_query_rules.h"
 
 #include <algorithm>
 #include <chrono>
@@ -126,151 +127,74 @@ __global__ void __launch_bounds__(256) k_gemm_f64_tiled(const double* __restrict
         }
 }
 
-#define QK_MAX 64
-struct TopK {
-    double s[QK_MAX];
-    int pos[QK_MAX];
-    int node[QK_MAX];
-    int room[QK_MAX];
-    int n;
-};
-// (score desc, candidate position asc)
-__device__ __forceinline__ bool better(double s1, int p1, double s2, int p2) { return s1 > s2 || (s1 == s2 && p1 < p2); }
-
-// One workgroup per query.  Thread-private candidates are reduced through LDS by repeated arg-best
-// selection (k is small), which keeps the result exact and deterministic.
+// One workgroup per query: the exact top k (hmsg_query_rules.h) of the nodes of the query's rooms, in room order then node order.
 __global__ void __launch_bounds__(256) k_query_topk(const double* __restrict__ S, long long N, int C, const int* __restrict__ qid,
                                                     const int* __restrict__ q_room_off, const int* __restrict__ q_rooms,
                                                     const int* __restrict__ room_off, const int* __restrict__ room_nodes,
                                                     int n_rooms, int k, int use_neg, int* __restrict__ out_idx,
                                                     int* __restrict__ out_room, double* __restrict__ out_score) {
-    __shared__ double sh_s[256];
-    __shared__ int sh_p[256];
+    __shared__ double sh_s[128];
+    __shared__ long long sh_k[128];
     __shared__ int sh_any;
-    __shared__ double last_s[2];
-    __shared__ int last_p[2];
     const int q = blockIdx.x, tid = threadIdx.x;
     const int myq = qid[q];
     const double* Sq = S + (size_t)q * C * N;
+    const int* rq = q_rooms + q_room_off[q];
+    const int nq = q_room_off[q + 1] - q_room_off[q];
+    // this thread's nodes of the query's rooms: f(key, node)
+    auto each_node = [&](auto&& f) {
+        for (int j = 0; j < nq; ++j) {
+            const int r = rq[j];
+            if (r < 0 || r >= n_rooms) continue;
+            const int b = room_off[r], e = room_off[r + 1];
+            for (int t = b + tid; t < e; t += 256) f(qkey(j, t - b), room_nodes[t]);
+        }
+    };
     if (tid == 0) sh_any = 0;
     __syncthreads();
     // pass 0: does any candidate have arg-max class == query class?
     if (use_neg) {
-        int pos0 = 0;
         int any = 0;
-        for (int j = q_room_off[q]; j < q_room_off[q + 1]; ++j) {
-            int r = q_rooms[j];
-            if (r < 0 || r >= n_rooms) continue;
-            int b = room_off[r], e = room_off[r + 1];
-            for (int t = b + tid; t < e; t += 256) {
-                int node = room_nodes[t];
-                int cls = 0;
-                double mx = Sq[node];
-                for (int c = 1; c < C; ++c) {
-                    double v = Sq[(size_t)c * N + node];
-                    if (v > mx) {
-                        mx = v;
-                        cls = c;
-                    }
-                }
-                any |= (cls == myq);
-            }
-            pos0 += e - b;
-        }
+        each_node([&](long long, int node) { any |= argmax_class_is(Sq, N, C, node, myq) ? 1 : 0; });
         if (any) sh_any = 1;
     }
     __syncthreads();
     const bool filtered = use_neg && sh_any;
-    // k rounds of "best candidate worse than the previous pick"
-    if (tid == 0) {
-        last_s[0] = 1e308;
-        last_p[0] = -1;
-    }
-    __syncthreads();
-    for (int round = 0; round < k; ++round) {
-        const double ls = last_s[0];
-        const int lp = last_p[0];
-        double bs = -1e308;
-        int bp = 0x7fffffff;
-        int pos0 = 0;
-        for (int j = q_room_off[q]; j < q_room_off[q + 1]; ++j) {
-            int r = q_rooms[j];
-            if (r < 0 || r >= n_rooms) continue;
-            int b = room_off[r], e = room_off[r + 1];
-            for (int t = b + tid; t < e; t += 256) {
-                int node = room_nodes[t];
-                int pos = pos0 + (t - b);
-                double sc = Sq[(size_t)myq * N + node];
-                if (filtered) {
-                    int cls = 0;
-                    double mx = Sq[node];
-                    for (int c = 1; c < C; ++c) {
-                        double v = Sq[(size_t)c * N + node];
-                        if (v > mx) {
-                            mx = v;
-                            cls = c;
-                        }
-                    }
-                    if (cls != myq) continue;
-                }
-                // strictly after the previous pick in (score desc, pos asc) order
-                bool after = lp < 0 || sc < ls || (sc == ls && pos > lp);
-                if (after && better(sc, pos, bs, bp)) {
-                    bs = sc;
-                    bp = pos;
-                }
-            }
-            pos0 += e - b;
-        }
-        sh_s[tid] = bs;
-        sh_p[tid] = bp;
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if (tid < o && better(sh_s[tid + o], sh_p[tid + o], sh_s[tid], sh_p[tid])) {
-                sh_s[tid] = sh_s[tid + o];
-                sh_p[tid] = sh_p[tid + o];
-            }
-            __syncthreads();
-        }
-        if (tid == 0) {
-            int pos = sh_p[0];
-            int oi = -1, orr = -1;
-            double os = 0.0;
-            if (pos != 0x7fffffff) {
-                // position -> (room, node)
-                int pos0b = 0;
-                for (int j = q_room_off[q]; j < q_room_off[q + 1]; ++j) {
-                    int r = q_rooms[j];
-                    if (r < 0 || r >= n_rooms) continue;
-                    int cnt = room_off[r + 1] - room_off[r];
-                    if (pos < pos0b + cnt) {
-                        oi = room_nodes[room_off[r] + pos - pos0b];
-                        orr = r;
-                        break;
-                    }
-                    pos0b += cnt;
-                }
-                os = sh_s[0];
-            }
-            out_idx[(size_t)q * k + round] = oi;
-            out_room[(size_t)q * k + round] = orr;
-            out_score[(size_t)q * k + round] = os;
-            last_s[0] = sh_s[0];
-            last_p[0] = pos == 0x7fffffff ? 0x7ffffffe : pos;
-        }
-        __syncthreads();
-    }
+    pick_top_k<256>(
+        k, sh_s, sh_k,
+        [&](auto&& offer) {
+            each_node([&](long long key, int node) {
+                if (!filtered || argmax_class_is(Sq, N, C, node, myq)) offer(Sq[(size_t)myq * N + node], key);
+            });
+        },
+        [&](int round, double s, long long key, bool) {
+            if (tid != 0) return;
+            const size_t o = (size_t)q * k + round;
+            const int r = key != QKEY_NONE ? rq[qkey_j(key)] : -1;
+            out_idx[o] = r >= 0 ? room_nodes[room_off[r] + qkey_place(key)] : -1;
+            out_room[o] = r;
+            out_score[o] = r >= 0 ? s : 0.0;
+        });
 }
 
-// query_hmsg_room (graph.py:3164-3272), one workgroup per query.  rooms_list = self.rooms (floor -1) or floors[f].rooms.
-//   mode 1 (label, :3204-3232): similarity of the room text with every room NAME of the list; every room within 1e-3 of
-//        the best one, in list order; the numbers returned are positions in rooms_list.
-//   mode 2 / 3 (view embeddings, :3247-3272): per room the largest similarity over its view embeddings; rooms sorted by
-//        it, descending (Python's sorted: stable, ties keep the list order); the first 5 (mode 2) or 10 (mode 3); the
-//        numbers returned are int(room_id.split("_")[-1]) -- which the caller then uses as positions in rooms_list.
-//   mode 0: no room stage (every room of the list, in order).
-// The selected numbers go to sel[q][0 .. nsel[q]); the object stage searches rooms_list[number] in that order
-// (query_hmsg_object :3099-3110); a number that is no position of rooms_list raises IndexError there: err[q] = 1.
+// the room level of one index, as room_select sees it for query q
+struct IndexRooms {
+    const double *S_room, *S_view;       // this query's rows
+    const int *view_off, *keys, *list;   // list: the floor's rooms, or NULL for all rooms in order
+    int L;
+    bool bad_floor;
+    __device__ int room_at(int i) const { return list ? list[i] : i; }
+    __device__ double name_sim(int i) const { return S_room[room_at(i)]; }
+    __device__ double view_max(int i) const {
+        const int r = room_at(i);
+        double mx = -1e308;
+        for (int v = view_off[r]; v < view_off[r + 1]; ++v) mx = fmax(mx, S_view[v]);
+        return mx;
+    }
+    __device__ bool has_views(int i) const { return view_off[room_at(i) + 1] != view_off[room_at(i)]; }
+    __device__ int room_key(int r) const { return keys[r]; }
+};
+// The room selection (hmsg_query_rules.h) over the index's own tables, one workgroup per query.
 __global__ void __launch_bounds__(256) k_room_select(int n_rooms, int n_floors, const double* __restrict__ S_room,
                                                      const double* __restrict__ S_view, long long n_views,
                                                      const int* __restrict__ view_off, const int* __restrict__ room_key,
@@ -278,88 +202,16 @@ __global__ void __launch_bounds__(256) k_room_select(int n_rooms, int n_floors, 
                                                      const int* __restrict__ floor_id, const int* __restrict__ mode, int max_sel,
                                                      int* __restrict__ sel, int* __restrict__ nsel, int* __restrict__ q_rooms,
                                                      int* __restrict__ err) {
-    const int q = blockIdx.x, tid = threadIdx.x;
-    const int f = floor_id[q], m = mode[q];
-    __shared__ int s_bad;
-    if (tid == 0) s_bad = (f >= n_floors) ? 1 : 0;
-    __syncthreads();
-    const int L = f < 0 ? n_rooms : (s_bad ? 0 : floor_room_off[f + 1] - floor_room_off[f]);
-    auto room_at = [&](int i) { return f < 0 ? i : floor_rooms[floor_room_off[f] + i]; };
-    __shared__ double s_red[256];
-    int* my_sel = sel + (size_t)q * max_sel;
-    if (m == 1) {
-        double best = -1e308;
-        for (int i = tid; i < L; i += 256) best = fmax(best, S_room[(size_t)q * n_rooms + room_at(i)]);
-        s_red[tid] = best;
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if (tid < o) s_red[tid] = fmax(s_red[tid], s_red[tid + o]);
-            __syncthreads();
-        }
-        best = s_red[0];
-        if (tid == 0) {                                         // (a handful of rooms: in list order)
-            int n = 0;
-            for (int i = 0; i < L && n < max_sel; ++i)
-                if (fabs(S_room[(size_t)q * n_rooms + room_at(i)] - best) < 1e-3) my_sel[n++] = i;
-            nsel[q] = n;
-        }
-    } else if (m == 2 || m == 3) {
-        // per room: max over its views (np.argmax takes the first maximum; only the value matters here)
-        __shared__ double s_max[1024];
-        __shared__ unsigned char s_taken[1024];
-        const int Lc = min(L, 1024);
-        for (int i = tid; i < Lc; i += 256) {
-            const int r = room_at(i);
-            double mx = -1e308;
-            for (int v = view_off[r]; v < view_off[r + 1]; ++v) mx = fmax(mx, S_view[(size_t)q * n_views + v]);
-            s_max[i] = mx;
-            s_taken[i] = 0;
-            if (view_off[r + 1] == view_off[r]) s_bad = 1;      // np.stack([]) raises
-        }
-        __syncthreads();
-        if (tid == 0) {
-            if (L > 1024) s_bad = 1;
-            // graph.py:3259-3264: `{int(room_id.split("_")[-1]): v for ... in sorted(...)}` -- rooms "0_2" and "1_2" (floor -1 on
-            // a multi-storey graph) collapse into ONE key, which keeps the place of its first (best) occurrence; the first
-            // 5 / 10 UNIQUE keys are returned.
-            const int want = m == 2 ? 5 : 10;
-            int n = 0;
-            for (int taken = 0; taken < Lc && n < want && n < max_sel; ++taken) {   // selection sort of the top few, first index wins ties
-                int bi = -1;
-                double bv = -1e308;
-                for (int i = 0; i < Lc; ++i)
-                    if (!s_taken[i] && (bi < 0 || s_max[i] > bv)) {
-                        bi = i;
-                        bv = s_max[i];
-                    }
-                s_taken[bi] = 1;
-                const int key = room_key[room_at(bi)];
-                bool seen = false;
-                for (int j = 0; j < n; ++j) seen = seen || my_sel[j] == key;
-                if (!seen) my_sel[n++] = key;
-            }
-            nsel[q] = n;
-        }
-    } else if (tid == 0) {
-        int n = 0;
-        for (int i = 0; i < L && n < max_sel; ++i) my_sel[n++] = i;
-        nsel[q] = n;
-    }
-    __syncthreads();
-    // positions of rooms_list -> room ids for the object stage
-    if (tid == 0) {
-        const int n = nsel[q];
-        for (int j = 0; j < max_sel; ++j) {
-            int r = -1;
-            if (j < n) {
-                const int pos = my_sel[j];
-                if (pos < 0 || pos >= L) s_bad = 1;
-                else r = room_at(pos);
-            }
-            q_rooms[(size_t)q * max_sel + j] = r;
-        }
-        err[q] = s_bad;
-    }
+    const int q = blockIdx.x, f = floor_id[q];
+    IndexRooms src;
+    src.S_room = S_room + (size_t)q * n_rooms;
+    src.S_view = S_view + (size_t)q * n_views;
+    src.view_off = view_off;
+    src.keys = room_key;
+    src.bad_floor = f >= n_floors;
+    src.list = f < 0 || src.bad_floor ? nullptr : floor_rooms + floor_room_off[f];
+    src.L = f < 0 ? n_rooms : (src.bad_floor ? 0 : floor_room_off[f + 1] - floor_room_off[f]);
+    room_select(src, mode[q], max_sel, sel + (size_t)q * max_sel, nsel + q, q_rooms + (size_t)q * max_sel, err + q);
 }
 __global__ void k_fill_offsets(int* off, int n, int stride) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -383,15 +235,6 @@ int iguard(hmsg_index* ix, F&& fn) {
         ix->err = "unknown error";
         return HMSG_ERR_INVALID;
     }
-}
-bool dev_ptr(const void* p) {
-    hipPointerAttribute_t a;
-    memset(&a, 0, sizeof(a));
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return a.type == hipMemoryTypeDevice;
 }
 // S[M][N] = A[M][D] . B[N][D]^T  (B = the node table unless given)
 void gemm(hmsg_index* ix, const double* A, int M, double* S, const double* B = nullptr, long long N = -1) {
@@ -437,19 +280,63 @@ hmsg_index* hmsg_index_create_rooms_only(int device, int D) {
     return ix;
 }
 
-namespace {
-void text_to_f64(hmsg_index* ix, const float* T, size_t n) {
-    ix->T64.ensure(n);
-    const float* src = T;
-    if (!dev_ptr(T)) {
-        ix->Tf.ensure(n);
-        h2d_bounce(ix->Tf.p, T, n * 4, ix->stream);
-        src = ix->Tf.p;
+QueryScan hmsg_query_scan(int Q, const int* room_mode, const int* floor_id) {
+    QueryScan sc;
+    for (int q = 0; q < Q; ++q) {
+        sc.in_range = sc.in_range && room_mode[q] >= 0 && room_mode[q] <= 3 && floor_id[q] >= -1;
+        sc.need_label |= room_mode[q] == 1;
+        sc.need_view |= room_mode[q] >= 2;
+        sc.max_floor = std::max(sc.max_floor, floor_id[q]);
     }
-    hipLaunchKernelGGL(k_f32_to_f64, dim3(cdiv(n, 256)), dim3(256), 0, ix->stream, src, ix->T64.p, n);
+    return sc;
+}
+std::string hmsg_query_precondition(const char* who, const QueryScan& sc, int n_floors, bool have_room_text, bool have_room_names) {
+    const std::string w = std::string(who) + ": ";
+    if (!sc.in_range || (n_floors >= 0 && sc.max_floor >= n_floors)) return w + "bad floor id / room mode";
+    if ((sc.need_label || sc.need_view) && !have_room_text) return w + "room text rows missing";
+    if (sc.need_label && !have_room_names) return w + "label mode without room name embeddings";
+    return "";
+}
+void hmsg_text_rows_to_f64(hipStream_t s, const float* src, size_t n, DevBuf<float>& tmp, DevBuf<double>& dst) {
+    dst.ensure(n);
+    if (!hmsg_is_device_ptr(src)) {
+        tmp.ensure(n);
+        h2d_bounce(tmp.p, src, n * 4, s);
+        src = tmp.p;
+    }
+    hipLaunchKernelGGL(k_f32_to_f64, dim3(cdiv(n, 256)), dim3(256), 0, s, src, dst.p, n);
     HMSG_CHECK_LAUNCH();
 }
-}  // namespace
+bool hmsg_query_pack_words(int* h_words, int Q, const int* floor_id, const int* room_mode, const int* qid) {
+    memcpy(h_words, floor_id, (size_t)Q * 4);
+    memcpy(h_words + Q, room_mode, (size_t)Q * 4);
+    const bool qid_dev = hmsg_is_device_ptr(qid);
+    if (!qid_dev) memcpy(h_words + 2 * (size_t)Q, qid, (size_t)Q * 4);
+    return qid_dev;
+}
+void QueryOut::give(const char* who, hipStream_t s, const char* d, const char* h, double* out_score, int* out_sel, int* out_nsel, int* out_idx,
+                    int* out_room) const {
+    bool any_dev = false;
+    auto one = [&](void* dst, size_t off, size_t n) {
+        if (hmsg_is_device_ptr(dst)) {
+            HIP_TRY(hipMemcpyAsync(dst, d + off, n, hipMemcpyDeviceToDevice, s));
+            any_dev = true;
+        } else {
+            memcpy(dst, h + off, n);
+        }
+    };
+    one(out_score, 0, (size_t)Q * k * 8);
+    one(out_sel, o_sel, (size_t)Q * max_rooms * 4);
+    one(out_nsel, o_nsel, (size_t)Q * 4);
+    one(out_idx, o_idx, (size_t)Q * k * 4);
+    one(out_room, o_room, (size_t)Q * k * 4);
+    if (any_dev) HIP_TRY(hipStreamSynchronize(s));
+    const int* herr = (const int*)(h + o_err);
+    for (int q = 0; q < Q; ++q)
+        HMSG_REQUIRE(!herr[q], HMSG_ERR_INVALID,
+                     std::string(who) + ": a query's room stage failed like the reference would (a room without view embeddings, or a "
+                                        "view-mode room number that is no position of the floor's room list)");
+}
 
 extern "C" {
 
@@ -467,19 +354,19 @@ int hmsg_index_create(int32_t device_id, int32_t dim, int64_t n, const void* emb
         ix->E.alloc((size_t)n * dim);
         const size_t cnt = (size_t)n * dim;
         if (emb_is_f64) {
-            if (dev_ptr(emb)) HIP_TRY(hipMemcpyAsync(ix->E.p, emb, cnt * 8, hipMemcpyDeviceToDevice, ix->stream));
+            if (hmsg_is_device_ptr(emb)) HIP_TRY(hipMemcpyAsync(ix->E.p, emb, cnt * 8, hipMemcpyDeviceToDevice, ix->stream));
             else h2d_bounce(ix->E.p, emb, cnt * 8, ix->stream);
         } else {
             DevBuf<float> tmp;
             tmp.alloc(cnt);
-            if (dev_ptr(emb)) HIP_TRY(hipMemcpyAsync(tmp.p, emb, cnt * 4, hipMemcpyDeviceToDevice, ix->stream));
+            if (hmsg_is_device_ptr(emb)) HIP_TRY(hipMemcpyAsync(tmp.p, emb, cnt * 4, hipMemcpyDeviceToDevice, ix->stream));
             else h2d_bounce(tmp.p, emb, cnt * 4, ix->stream);
             hipLaunchKernelGGL(k_f32_to_f64, dim3(cdiv(cnt, 256)), dim3(256), 0, ix->stream, (const float*)tmp.p, ix->E.p, cnt);
             HMSG_CHECK_LAUNCH();
             HIP_TRY(hipStreamSynchronize(ix->stream));
         }
         std::vector<int> rooms((size_t)n);
-        if (dev_ptr(room_of_node)) {
+        if (hmsg_is_device_ptr(room_of_node)) {
             HIP_TRY(hipMemcpy(rooms.data(), room_of_node, (size_t)n * 4, hipMemcpyDeviceToHost));
         } else {
             memcpy(rooms.data(), room_of_node, (size_t)n * 4);
@@ -555,11 +442,11 @@ int hmsg_query_objects(hmsg_index_t* ix, int32_t Q, int32_t C, const float* T, c
                      "hmsg_query_objects: bad argument");
         if (Q == 0) return;
         const size_t nT = (size_t)Q * C * ix->D;
-        text_to_f64(ix, T, nT);
+        hmsg_text_rows_to_f64(ix->stream, T, nT, ix->Tf, ix->T64);
         ix->S.ensure((size_t)Q * C * ix->N);
         gemm(ix, ix->T64.p, Q * C, ix->S.p);
         std::vector<int> hoff(Q + 1);
-        if (dev_ptr(room_off)) {
+        if (hmsg_is_device_ptr(room_off)) {
             HIP_TRY(hipMemcpy(hoff.data(), room_off, (size_t)(Q + 1) * 4, hipMemcpyDeviceToHost));
         } else {
             memcpy(hoff.data(), room_off, (size_t)(Q + 1) * 4);
@@ -572,9 +459,9 @@ int hmsg_query_objects(hmsg_index_t* ix, int32_t Q, int32_t C, const float* T, c
         ix->d_oidx.ensure((size_t)Q * k);
         ix->d_oroom.ensure((size_t)Q * k);
         ix->d_oscore.ensure((size_t)Q * k);
-        HIP_TRY(hipMemcpyAsync(ix->d_qid.p, qid, (size_t)Q * 4, dev_ptr(qid) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ix->stream));
+        HIP_TRY(hipMemcpyAsync(ix->d_qid.p, qid, (size_t)Q * 4, hmsg_is_device_ptr(qid) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ix->stream));
         HIP_TRY(hipMemcpyAsync(ix->d_roff.p, hoff.data(), (size_t)(Q + 1) * 4, hipMemcpyHostToDevice, ix->stream));
-        if (nr) HIP_TRY(hipMemcpyAsync(ix->d_rooms.p, rooms, (size_t)nr * 4, dev_ptr(rooms) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ix->stream));
+        if (nr) HIP_TRY(hipMemcpyAsync(ix->d_rooms.p, rooms, (size_t)nr * 4, hmsg_is_device_ptr(rooms) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ix->stream));
         hipLaunchKernelGGL(k_query_topk, dim3(Q), dim3(256), 0, ix->stream, (const double*)ix->S.p, ix->N, C, (const int*)ix->d_qid.p,
                            (const int*)ix->d_roff.p, (const int*)ix->d_rooms.p, (const int*)ix->room_off.p,
                            (const int*)ix->room_nodes.p, ix->n_rooms, k, use_negatives, ix->d_oidx.p, ix->d_oroom.p, ix->d_oscore.p);
@@ -615,14 +502,14 @@ int hmsg_index_set_hierarchy(hmsg_index_t* ix, int32_t n_rooms, int32_t n_floors
         if (nfr) HIP_TRY(hipMemcpyAsync(ix->floor_rooms.p, floor_rooms, (size_t)nfr * 4, hipMemcpyHostToDevice, ix->stream));
         if (room_name_emb) {
             ix->room_name_emb.alloc((size_t)std::max(R, 1) * ix->D);
-            if (dev_ptr(room_name_emb)) HIP_TRY(hipMemcpyAsync(ix->room_name_emb.p, room_name_emb, (size_t)R * ix->D * 8, hipMemcpyDeviceToDevice, ix->stream));
+            if (hmsg_is_device_ptr(room_name_emb)) HIP_TRY(hipMemcpyAsync(ix->room_name_emb.p, room_name_emb, (size_t)R * ix->D * 8, hipMemcpyDeviceToDevice, ix->stream));
             else h2d_bounce(ix->room_name_emb.p, room_name_emb, (size_t)R * ix->D * 8, ix->stream);
         } else {
             ix->room_name_emb.release();
         }
         ix->view_emb.alloc((size_t)std::max<long long>(NV, 1) * ix->D);
         if (NV) {
-            if (dev_ptr(view_emb)) HIP_TRY(hipMemcpyAsync(ix->view_emb.p, view_emb, (size_t)NV * ix->D * 8, hipMemcpyDeviceToDevice, ix->stream));
+            if (hmsg_is_device_ptr(view_emb)) HIP_TRY(hipMemcpyAsync(ix->view_emb.p, view_emb, (size_t)NV * ix->D * 8, hipMemcpyDeviceToDevice, ix->stream));
             else h2d_bounce(ix->view_emb.p, view_emb, (size_t)NV * ix->D * 8, ix->stream);
         }
         HIP_TRY(hipStreamSynchronize(ix->stream));
@@ -651,70 +538,43 @@ int hmsg_query_hier(hmsg_index_t* ix, int32_t Q, int32_t C, const float* T_obj, 
             fprintf(stderr, "[hmsg query_hier] %-22s %.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t_prev).count());
             t_prev = t;
         };
-        std::vector<int> hm((size_t)Q), hf((size_t)Q);
-        memcpy(hm.data(), room_mode, (size_t)Q * 4);
-        memcpy(hf.data(), floor_id, (size_t)Q * 4);
-        bool need_label = false, need_view = false;
-        for (int q = 0; q < Q; ++q) {
-            HMSG_REQUIRE(hm[q] >= 0 && hm[q] <= 3 && hf[q] >= -1 && hf[q] < ix->n_floors, HMSG_ERR_INVALID, "hmsg_query_hier: bad floor id / room mode");
-            need_label |= hm[q] == 1;
-            need_view |= hm[q] >= 2;
-        }
-        HMSG_REQUIRE(!(need_label || need_view) || T_room, HMSG_ERR_INVALID, "hmsg_query_hier: room text rows missing");
-        HMSG_REQUIRE(!need_label || ix->room_name_emb.p, HMSG_ERR_INVALID, "hmsg_query_hier: label mode without room name embeddings");
+        const QueryScan sc = hmsg_query_scan(Q, room_mode, floor_id);
+        const bool need_label = sc.need_label, need_view = sc.need_view;
+        const std::string why = hmsg_query_precondition("hmsg_query_hier", sc, ix->n_floors, T_room != nullptr, ix->room_name_emb.p != nullptr);
+        HMSG_REQUIRE(why.empty(), HMSG_ERR_INVALID, why);
         // room stage: similarities of the room text with the room names / the view embeddings (float64 MFMA GEMM)
         ix->S_room.ensure((size_t)Q * std::max(R, 1));
         ix->S_view.ensure((size_t)Q * std::max<long long>(ix->n_views, 1));
         if (need_label || need_view) {
-            const size_t nT = (size_t)Q * ix->D;
-            ix->Tr64.ensure(nT);
-            const float* src = T_room;
-            if (!dev_ptr(T_room)) {
-                ix->Tr.ensure(nT);
-                h2d_bounce(ix->Tr.p, T_room, nT * 4, ix->stream);
-                src = ix->Tr.p;
-            }
-            hipLaunchKernelGGL(k_f32_to_f64, dim3(cdiv(nT, 256)), dim3(256), 0, ix->stream, src, ix->Tr64.p, nT);
-            HMSG_CHECK_LAUNCH();
+            hmsg_text_rows_to_f64(ix->stream, T_room, (size_t)Q * ix->D, ix->Tr, ix->Tr64);
             if (need_label) gemm(ix, ix->Tr64.p, Q, ix->S_room.p, ix->room_name_emb.p, R);
             if (need_view && ix->n_views) gemm(ix, ix->Tr64.p, Q, ix->S_view.p, ix->view_emb.p, ix->n_views);
         }
         lap("room text + room GEMM");
         // per-query words: one packed upload from pinned memory
-        const bool qid_dev = dev_ptr(qid);
         ix->h_qin.ensure((size_t)Q * 3 + 4);
         ix->d_qin.ensure((size_t)Q * 3 + 4);
-        memcpy(ix->h_qin.p, hf.data(), (size_t)Q * 4);
-        memcpy(ix->h_qin.p + Q, hm.data(), (size_t)Q * 4);
-        if (!qid_dev) memcpy(ix->h_qin.p + 2 * (size_t)Q, qid, (size_t)Q * 4);
+        const bool qid_dev = hmsg_query_pack_words(ix->h_qin.p, Q, floor_id, room_mode, qid);
         upload_pinned(ix->d_qin.p, ix->h_qin.p, (((size_t)Q * 3 + 3) / 4) * 16, ix->stream);
         int* const d_floor = ix->d_qin.p;
         int* const d_mode = ix->d_qin.p + Q;
         int* const d_qid = ix->d_qin.p + 2 * (size_t)Q;
         if (qid_dev) HIP_TRY(hipMemcpyAsync(d_qid, qid, (size_t)Q * 4, hipMemcpyDeviceToDevice, ix->stream));
-        // results: one packed buffer [score f64 Q*k | sel Q*max_rooms | nsel Q | err Q | idx Q*k | room Q*k]
-        const size_t o_sel = (size_t)Q * k * 8, o_nsel = o_sel + (size_t)Q * max_rooms * 4, o_err = o_nsel + (size_t)Q * 4,
-                     o_idx = o_err + (size_t)Q * 4, o_room = o_idx + (size_t)Q * k * 4, out_bytes = o_room + (size_t)Q * k * 4;
-        ix->d_qout.ensure(out_bytes);
-        ix->h_qout.ensure(out_bytes);
-        double* const d_oscore = (double*)ix->d_qout.p;
-        int* const d_sel = (int*)(ix->d_qout.p + o_sel);
-        int* const d_nsel = (int*)(ix->d_qout.p + o_nsel);
-        int* const d_err = (int*)(ix->d_qout.p + o_err);
-        int* const d_oidx = (int*)(ix->d_qout.p + o_idx);
-        int* const d_oroom = (int*)(ix->d_qout.p + o_room);
+        const QueryOut out(Q, k, max_rooms);
+        ix->d_qout.ensure(out.bytes);
+        ix->h_qout.ensure(out.bytes);
+        char* const d_out = ix->d_qout.p;
         ix->d_rooms.ensure((size_t)Q * max_rooms);
         ix->d_roff.ensure((size_t)Q + 1);
         hipLaunchKernelGGL(k_room_select, dim3(Q), dim3(256), 0, ix->stream, R, ix->n_floors, (const double*)ix->S_room.p,
                            (const double*)ix->S_view.p, ix->n_views, (const int*)ix->view_off.p, (const int*)ix->room_key.p,
                            (const int*)ix->floor_room_off.p, (const int*)ix->floor_rooms.p, (const int*)d_floor,
-                           (const int*)d_mode, max_rooms, d_sel, d_nsel, ix->d_rooms.p, d_err);
+                           (const int*)d_mode, max_rooms, out.sel(d_out), out.nsel(d_out), ix->d_rooms.p, out.err(d_out));
         hipLaunchKernelGGL(k_fill_offsets, dim3(cdiv((size_t)Q + 1, 256)), dim3(256), 0, ix->stream, ix->d_roff.p, Q, max_rooms);
         HMSG_CHECK_LAUNCH();
         lap("room select");
         // object stage on the rooms the room stage picked, in that order
-        const size_t nT = (size_t)Q * C * ix->D;
-        text_to_f64(ix, T_obj, nT);
+        hmsg_text_rows_to_f64(ix->stream, T_obj, (size_t)Q * C * ix->D, ix->Tf, ix->T64);
         lap("object text upload");
         ix->S.ensure((size_t)Q * C * ix->N);
         lap("S alloc");
@@ -722,33 +582,13 @@ int hmsg_query_hier(hmsg_index_t* ix, int32_t Q, int32_t C, const float* T_obj, 
         lap("object GEMM");
         hipLaunchKernelGGL(k_query_topk, dim3(Q), dim3(256), 0, ix->stream, (const double*)ix->S.p, ix->N, C, (const int*)d_qid,
                            (const int*)ix->d_roff.p, (const int*)ix->d_rooms.p, (const int*)ix->room_off.p,
-                           (const int*)ix->room_nodes.p, ix->n_rooms, k, use_negatives, d_oidx, d_oroom, d_oscore);
+                           (const int*)ix->room_nodes.p, ix->n_rooms, k, use_negatives, out.idx(d_out), out.room(d_out), out.score(d_out));
         HMSG_CHECK_LAUNCH();
         lap("top-k");
-        HIP_TRY(hipMemcpyAsync(ix->h_qout.p, ix->d_qout.p, out_bytes, hipMemcpyDeviceToHost, ix->stream));
+        HIP_TRY(hipMemcpyAsync(ix->h_qout.p, d_out, out.bytes, hipMemcpyDeviceToHost, ix->stream));
         HIP_TRY(hipStreamSynchronize(ix->stream));
-        const int* const herr = (const int*)(ix->h_qout.p + o_err);
-        // (results into the caller's arrays: host memory, or device memory -- the reference's callers take numpy arrays)
-        bool any_dev = false;
-        auto give = [&](void* dst, size_t off, size_t bytes) {
-            if (dev_ptr(dst)) {
-                HIP_TRY(hipMemcpyAsync(dst, ix->d_qout.p + off, bytes, hipMemcpyDeviceToDevice, ix->stream));
-                any_dev = true;
-            } else {
-                memcpy(dst, ix->h_qout.p + off, bytes);
-            }
-        };
-        give(out_score, 0, (size_t)Q * k * 8);
-        give(out_sel, o_sel, (size_t)Q * max_rooms * 4);
-        give(out_nsel, o_nsel, (size_t)Q * 4);
-        give(out_idx, o_idx, (size_t)Q * k * 4);
-        give(out_room, o_room, (size_t)Q * k * 4);
-        if (any_dev) HIP_TRY(hipStreamSynchronize(ix->stream));
+        out.give("hmsg_query_hier", ix->stream, d_out, ix->h_qout.p, out_score, out_sel, out_nsel, out_idx, out_room);
         lap("read-back");
-        for (int q = 0; q < Q; ++q)
-            HMSG_REQUIRE(!herr[(size_t)q], HMSG_ERR_INVALID,
-                         "hmsg_query_hier: a query's room stage failed like the reference would (a room without view embeddings, or a "
-                         "view-mode room number that is no position of the floor's room list)");
     });
 }
 
@@ -757,7 +597,7 @@ int hmsg_similarity(hmsg_index_t* ix, int32_t Q, const float* T, double* S) {
     return iguard(ix, [&] {
         HMSG_REQUIRE(Q >= 0 && T && S, HMSG_ERR_INVALID, "hmsg_similarity: bad argument");
         if (Q == 0) return;
-        text_to_f64(ix, T, (size_t)Q * ix->D);
+        hmsg_text_rows_to_f64(ix->stream, T, (size_t)Q * ix->D, ix->Tf, ix->T64);
         ix->S.ensure((size_t)Q * ix->N);
         gemm(ix, ix->T64.p, Q, ix->S.p);
         HIP_TRY(hipMemcpyAsync(S, ix->S.p, (size_t)Q * ix->N * 8, hipMemcpyDeviceToHost, ix->stream));

@@ -15,9 +15,9 @@
 // Each S[q][n] is the same float64 whichever GEMM kernel computed it (hmsg_query.h: hmsg_gemm_f64), so a shard's smaller table
 // scores exactly like its rows of the concatenated one.
 #include "hmsg_query.h"
+#include "hmsg_query_rules.h"
 
 #include <algorithm>
-#include <climits>
 #include <functional>
 
 // (hmsg_scene_graph.hip)
@@ -49,11 +49,6 @@ struct ShRoomLayout {
     long long o_lab, o_view, o_fro, o_fr, o_key, o_vcnt, bytes;
     int Rmax, Fmax, NFRmax;
 };
-
-__global__ void k_sh_f32_to_f64(const float* __restrict__ a, double* __restrict__ b, size_t n) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) b[i] = (double)a[i];
-}
 
 // name similarities [Q][R] -> the slot's rows [Q][Rmax]
 __global__ void k_sh_pad_rows(const double* __restrict__ src, int Q, int R, int Rmax, double* __restrict__ dst) {
@@ -89,21 +84,45 @@ __global__ void k_sh_tables(const int* __restrict__ floor_room_off, int F, const
     }
 }
 
-// The global room selection of k_room_select (hmsg_query.hip) on the gathered room-level rows, one workgroup per query.  Room r
-// (global) lives in the slot of the shard s with roff[s] <= r < roff[s + 1], as local room r - roff[s]; floor f (global) in the
-// slot of the shard with foff[s] <= f < foff[s + 1].  sel / nsel / err as k_room_select; q_rooms [Q][max_sel]: global room ids.
+// the room level of every shard's slot of the room exchange, as room_select sees it for query q.  Room r (global) lives in the slot
+// of the shard s with roff[s] <= r < roff[s + 1], as local room r - roff[s]; floor f (global) likewise by foff.
+struct ShardRooms {
+    const char* rb;
+    long long slot;
+    ShRoomLayout lay;
+    const int* roff;
+    const int *fro, *frs;                // the floor's list in its shard's slot (local room ids from room0), or NULL for all rooms in order
+    int W, q, room0, L;
+    bool bad_floor;
+    __device__ int shard_of(int r) const {
+        int s = 0;
+        while (s + 1 < W && r >= roff[s + 1]) ++s;
+        return s;
+    }
+    __device__ double row(long long off, int r) const {      // the f64 row entry of (q, global room r)
+        const int s = shard_of(r);
+        return ((const double*)(rb + (size_t)s * slot + off))[(size_t)q * lay.Rmax + (r - roff[s])];
+    }
+    __device__ int tab(long long off, int r) const {         // the int table entry of global room r
+        const int s = shard_of(r);
+        return ((const int*)(rb + (size_t)s * slot + off))[r - roff[s]];
+    }
+    __device__ int room_at(int i) const { return frs ? room0 + frs[i] : i; }
+    __device__ double name_sim(int i) const { return row(lay.o_lab, room_at(i)); }
+    __device__ double view_max(int i) const { return row(lay.o_view, room_at(i)); }      // (k_sh_view_max, on the owning shard)
+    __device__ bool has_views(int i) const { return tab(lay.o_vcnt, room_at(i)) != 0; }
+    __device__ int room_key(int r) const { return tab(lay.o_key, r); }
+};
+// The GLOBAL room selection (hmsg_query_rules.h) on the gathered room-level rows, one workgroup per query.  sel / nsel / err as
+// k_room_select; q_rooms [Q][max_sel]: global room ids.
 __global__ void __launch_bounds__(256) k_sh_room_select(const char* __restrict__ rb, long long slot, ShRoomLayout lay, int W,
                                                         const int* __restrict__ roff, const int* __restrict__ foff,
                                                         const int* __restrict__ floor_id, const int* __restrict__ mode, int max_sel,
                                                         int* __restrict__ sel, int* __restrict__ nsel, int* __restrict__ q_rooms,
                                                         int* __restrict__ err) {
-    const int q = blockIdx.x, tid = threadIdx.x;
-    const int f = floor_id[q], m = mode[q];
-    const int R_tot = roff[W], F_tot = foff[W];
-    __shared__ int s_bad;
+    const int q = blockIdx.x, f = floor_id[q];
     __shared__ int s_fs;                          // the shard of floor f
-    if (tid == 0) {
-        s_bad = (f >= F_tot) ? 1 : 0;
+    if (threadIdx.x == 0) {
         int fs = -1;
         for (int s = 0; s < W && f >= 0; ++s)
             if (f >= foff[s] && f < foff[s + 1]) fs = s;
@@ -111,134 +130,52 @@ __global__ void __launch_bounds__(256) k_sh_room_select(const char* __restrict__
     }
     __syncthreads();
     const int fs = s_fs;
-    const int* fro = fs >= 0 ? (const int*)(rb + (size_t)fs * slot + lay.o_fro) : nullptr;
-    const int* frs = fs >= 0 ? (const int*)(rb + (size_t)fs * slot + lay.o_fr) : nullptr;
-    const int lf = fs >= 0 ? f - foff[fs] : 0;
-    const int L = f < 0 ? R_tot : (fs < 0 ? 0 : fro[lf + 1] - fro[lf]);
-    auto room_at = [&](int i) { return f < 0 ? i : roff[fs] + frs[fro[lf] + i]; };
-    auto shard_of = [&](int r) {
-        int s = 0;
-        while (s + 1 < W && r >= roff[s + 1]) ++s;
-        return s;
-    };
-    auto row = [&](long long off, int r) {     // the f64 row entry of (q, global room r)
-        const int s = shard_of(r);
-        return ((const double*)(rb + (size_t)s * slot + off))[(size_t)q * lay.Rmax + (r - roff[s])];
-    };
-    auto tab = [&](long long off, int r) {     // the int table entry of global room r
-        const int s = shard_of(r);
-        return ((const int*)(rb + (size_t)s * slot + off))[r - roff[s]];
-    };
-    __shared__ double s_red[256];
-    int* my_sel = sel + (size_t)q * max_sel;
-    if (m == 1) {
-        double best = -1e308;
-        for (int i = tid; i < L; i += 256) best = fmax(best, row(lay.o_lab, room_at(i)));
-        s_red[tid] = best;
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if (tid < o) s_red[tid] = fmax(s_red[tid], s_red[tid + o]);
-            __syncthreads();
-        }
-        best = s_red[0];
-        if (tid == 0) {
-            int n = 0;
-            for (int i = 0; i < L && n < max_sel; ++i)
-                if (fabs(row(lay.o_lab, room_at(i)) - best) < 1e-3) my_sel[n++] = i;
-            nsel[q] = n;
-        }
-    } else if (m == 2 || m == 3) {
-        __shared__ double s_max[1024];
-        __shared__ unsigned char s_taken[1024];
-        const int Lc = min(L, 1024);
-        for (int i = tid; i < Lc; i += 256) {
-            const int r = room_at(i);
-            s_max[i] = row(lay.o_view, r);
-            s_taken[i] = 0;
-            if (tab(lay.o_vcnt, r) == 0) s_bad = 1;                // np.stack([]) raises
-        }
-        __syncthreads();
-        if (tid == 0) {
-            if (L > 1024) s_bad = 1;
-            const int want = m == 2 ? 5 : 10;
-            int n = 0;
-            for (int taken = 0; taken < Lc && n < want && n < max_sel; ++taken) {   // first index wins ties
-                int bi = -1;
-                double bv = -1e308;
-                for (int i = 0; i < Lc; ++i)
-                    if (!s_taken[i] && (bi < 0 || s_max[i] > bv)) {
-                        bi = i;
-                        bv = s_max[i];
-                    }
-                s_taken[bi] = 1;
-                const int key = tab(lay.o_key, room_at(bi));
-                bool seen = false;
-                for (int j = 0; j < n; ++j) seen = seen || my_sel[j] == key;
-                if (!seen) my_sel[n++] = key;
-            }
-            nsel[q] = n;
-        }
-    } else if (tid == 0) {
-        int n = 0;
-        for (int i = 0; i < L && n < max_sel; ++i) my_sel[n++] = i;
-        nsel[q] = n;
+    ShardRooms src;
+    src.rb = rb;
+    src.slot = slot;
+    src.lay = lay;
+    src.roff = roff;
+    src.W = W;
+    src.q = q;
+    src.bad_floor = f >= foff[W];
+    src.fro = src.frs = nullptr;
+    src.room0 = 0;
+    src.L = f < 0 ? roff[W] : 0;
+    if (fs >= 0) {
+        const int* fro = (const int*)(rb + (size_t)fs * slot + lay.o_fro) + (f - foff[fs]);
+        src.frs = (const int*)(rb + (size_t)fs * slot + lay.o_fr) + fro[0];
+        src.room0 = roff[fs];
+        src.L = fro[1] - fro[0];
     }
-    __syncthreads();
-    if (tid == 0) {
-        const int n = nsel[q];
-        for (int j = 0; j < max_sel; ++j) {
-            int r = -1;
-            if (j < n) {
-                const int pos = my_sel[j];
-                if (pos < 0 || pos >= L) s_bad = 1;
-                else r = room_at(pos);
-            }
-            q_rooms[(size_t)q * max_sel + j] = r;
-        }
-        err[q] = s_bad;
-    }
+    room_select(src, mode[q], max_sel, sel + (size_t)q * max_sel, nsel + q, q_rooms + (size_t)q * max_sel, err + q);
 }
 
-// (score desc, key asc)
-__device__ __forceinline__ bool sh_better(double s1, long long k1, double s2, long long k2) { return s1 > s2 || (s1 == s2 && k1 < k2); }
-
 // One shard's candidates, one workgroup per query: the nodes of the rooms of q_rooms that this shard owns (global ids in
-// [room0, room0 + n_rooms_nodes)), in sel order then node order.  Out: recs [Q][2k] (the plain top k, then the top k of the
-// candidates whose arg-max class is the query's) and cnt [Q] (how many of those there are).  Selection as k_query_topk: k rounds
-// of the best candidate strictly after the previous pick, reduced through LDS.
+// [room0, room0 + n_rooms_nodes)), in sel order then node order.  Out: recs [Q][2k] (the exact top k of hmsg_query_rules.h, then
+// the top k of the candidates whose arg-max class is the query's) and cnt [Q] (how many of those there are).
 __global__ void __launch_bounds__(256) k_sh_candidates(const double* __restrict__ S, long long N, int C, const int* __restrict__ qid,
                                                        const int* __restrict__ q_rooms, int max_sel, const int* __restrict__ room_off,
                                                        const int* __restrict__ room_nodes, int room0, int n_rooms_nodes, int node0, int k,
                                                        int use_neg, ShRec* __restrict__ recs, int* __restrict__ cnt) {
-    __shared__ double sh_s[256];
-    __shared__ long long sh_k[256];
+    __shared__ double sh_s[128];
+    __shared__ long long sh_k[128];
     __shared__ int sh_n[256];
-    __shared__ double last_s;
-    __shared__ long long last_k;
     const int q = blockIdx.x, tid = threadIdx.x;
     const int myq = qid[q];
     const double* Sq = S + (size_t)q * C * N;
     const int* rq = q_rooms + (size_t)q * max_sel;
-    auto argmax_is_q = [&](int node) {
-        int cls = 0;
-        double mx = Sq[node];
-        for (int c = 1; c < C; ++c) {
-            const double v = Sq[(size_t)c * N + node];
-            if (v > mx) {
-                mx = v;
-                cls = c;
-            }
-        }
-        return cls == myq;
-    };
-    // the count of filtered candidates
-    int mine = 0;
-    if (use_neg)
+    // this thread's nodes of the query's rooms held here: f(key, node)
+    auto each_node = [&](auto&& f) {
         for (int j = 0; j < max_sel; ++j) {
             const int lr = rq[j] - room0;
             if (rq[j] < 0 || lr < 0 || lr >= n_rooms_nodes) continue;
-            for (int t = room_off[lr] + tid; t < room_off[lr + 1]; t += 256) mine += argmax_is_q(room_nodes[t]) ? 1 : 0;
+            const int b = room_off[lr];
+            for (int t = b + tid; t < room_off[lr + 1]; t += 256) f(qkey(j, t - b), room_nodes[t]);
         }
+    };
+    // the count of filtered candidates
+    int mine = 0;
+    if (use_neg) each_node([&](long long, int node) { mine += argmax_class_is(Sq, N, C, node, myq) ? 1 : 0; });
     sh_n[tid] = mine;
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) {
@@ -246,92 +183,43 @@ __global__ void __launch_bounds__(256) k_sh_candidates(const double* __restrict_
         __syncthreads();
     }
     if (tid == 0) cnt[q] = sh_n[0];
-    __syncthreads();
     ShRec* out = recs + (size_t)q * 2 * k;
     for (int list = 0; list < 2; ++list) {
         const bool filtered = list == 1;
-        if (tid == 0) {
-            last_s = 1e308;
-            last_k = -1;
-        }
-        __syncthreads();
-        for (int round = 0; round < k; ++round) {
-            const double ls = last_s;
-            const long long lk = last_k;
-            double bs = -1e308;
-            long long bk = LLONG_MAX;
-            int bn = -1;
-            if (!filtered || use_neg)
-                for (int j = 0; j < max_sel; ++j) {
-                    const int lr = rq[j] - room0;
-                    if (rq[j] < 0 || lr < 0 || lr >= n_rooms_nodes) continue;
-                    const int b = room_off[lr];
-                    for (int t = b + tid; t < room_off[lr + 1]; t += 256) {
-                        const int node = room_nodes[t];
-                        const long long key = ((long long)j << 32) | (long long)(t - b);
-                        const double sc = Sq[(size_t)myq * N + node];
-                        if (filtered && !argmax_is_q(node)) continue;
-                        const bool after = lk < 0 || sc < ls || (sc == ls && key > lk);
-                        if (after && sh_better(sc, key, bs, bk)) {
-                            bs = sc;
-                            bk = key;
-                            bn = node;
-                        }
-                    }
-                }
-            sh_s[tid] = bs;
-            sh_k[tid] = bk;
-            sh_n[tid] = bn;
-            __syncthreads();
-            for (int o = 128; o > 0; o >>= 1) {
-                if (tid < o && sh_better(sh_s[tid + o], sh_k[tid + o], sh_s[tid], sh_k[tid])) {
-                    sh_s[tid] = sh_s[tid + o];
-                    sh_k[tid] = sh_k[tid + o];
-                    sh_n[tid] = sh_n[tid + o];
-                }
-                __syncthreads();
-            }
-            if (tid == 0) {
-                ShRec rec;
-                if (sh_k[0] != LLONG_MAX) {
-                    rec.s = sh_s[0];
-                    rec.key = sh_k[0];
-                    rec.node = node0 + sh_n[0];
-                    rec.room = rq[(int)(sh_k[0] >> 32)];
-                    last_s = sh_s[0];
-                    last_k = sh_k[0];
-                } else {
-                    rec.s = 0.0;
-                    rec.key = LLONG_MAX;
-                    rec.node = -1;
-                    rec.room = -1;
-                    last_s = -1e308;            // (nothing is after "no candidate")
-                    last_k = LLONG_MAX;
+        pick_top_k<256>(
+            k, sh_s, sh_k,
+            [&](auto&& offer) {
+                if (filtered && !use_neg) return;
+                each_node([&](long long key, int node) {
+                    if (!filtered || argmax_class_is(Sq, N, C, node, myq)) offer(Sq[(size_t)myq * N + node], key);
+                });
+            },
+            [&](int round, double s, long long key, bool) {
+                if (tid != 0) return;
+                ShRec rec{0.0, QKEY_NONE, -1, -1};
+                if (key != QKEY_NONE) {
+                    rec.s = s;
+                    rec.key = key;
+                    rec.room = rq[qkey_j(key)];
+                    rec.node = node0 + room_nodes[room_off[rec.room - room0] + qkey_place(key)];
                 }
                 out[(size_t)list * k + round] = rec;
-            }
-            __syncthreads();
-        }
+            });
     }
 }
 
 // The shards' lists into the answer, one wave per query: the filtered lists when negatives are on and any shard counted a
-// filtered candidate (k_query_topk's `filtered`), else the plain ones; k rounds of the best record after the previous pick.
+// filtered candidate (k_query_topk's `filtered`), else the plain ones; the exact top k of the W * k records.
 __global__ void __launch_bounds__(64) k_sh_merge(const char* __restrict__ cb, long long slot, long long o_cnt, int W, int Q, int k, int use_neg,
                                                  int* __restrict__ out_idx, int* __restrict__ out_room, double* __restrict__ out_score) {
-    __shared__ double sh_s[64];
-    __shared__ long long sh_k[64];
-    __shared__ int sh_i[64];
+    __shared__ double sh_s[32];
+    __shared__ long long sh_k[32];
     __shared__ int sh_list;
-    __shared__ double last_s;
-    __shared__ long long last_k;
     const int q = blockIdx.x, tid = threadIdx.x;
     if (tid == 0) {
         long long total = 0;
         for (int s = 0; s < W; ++s) total += ((const int*)(cb + (size_t)s * slot + o_cnt))[q];
         sh_list = (use_neg && total > 0) ? 1 : 0;
-        last_s = 1e308;
-        last_k = -1;
     }
     __syncthreads();
     const int list = sh_list;
@@ -339,66 +227,32 @@ __global__ void __launch_bounds__(64) k_sh_merge(const char* __restrict__ cb, lo
         const int s = i / k, r = i % k;
         return ((const ShRec*)(cb + (size_t)s * slot))[((size_t)q * 2 + list) * k + r];
     };
-    for (int round = 0; round < k; ++round) {
-        const double ls = last_s;
-        const long long lk = last_k;
-        double bs = -1e308;
-        long long bk = LLONG_MAX;
-        int bi = -1;
-        for (int i = tid; i < W * k; i += 64) {
-            const ShRec c = rec(i);
-            if (c.key == LLONG_MAX) continue;
-            const bool after = lk < 0 || c.s < ls || (c.s == ls && c.key > lk);
-            if (after && sh_better(c.s, c.key, bs, bk)) {
-                bs = c.s;
-                bk = c.key;
-                bi = i;
+    int bi = -1;                                  // this thread's best record of the round
+    pick_top_k<64>(
+        k, sh_s, sh_k,
+        [&](auto&& offer) {
+            for (int i = tid; i < W * k; i += 64) {
+                const ShRec c = rec(i);
+                if (c.key != QKEY_NONE && offer(c.s, c.key)) bi = i;
             }
-        }
-        sh_s[tid] = bs;
-        sh_k[tid] = bk;
-        sh_i[tid] = bi;
-        __syncthreads();
-        for (int o = 32; o > 0; o >>= 1) {
-            if (tid < o && sh_better(sh_s[tid + o], sh_k[tid + o], sh_s[tid], sh_k[tid])) {
-                sh_s[tid] = sh_s[tid + o];
-                sh_k[tid] = sh_k[tid + o];
-                sh_i[tid] = sh_i[tid + o];
-            }
-            __syncthreads();
-        }
-        if (tid == 0) {
+        },
+        [&](int round, double, long long key, bool mine) {
             const size_t o = (size_t)q * k + round;
-            if (sh_i[0] >= 0) {
-                const ShRec c = rec(sh_i[0]);
+            if (mine) {
+                const ShRec c = rec(bi);
                 out_idx[o] = c.node;
                 out_room[o] = c.room;
                 out_score[o] = c.s;
-                last_s = c.s;
-                last_k = c.key;
-            } else {
+            } else if (tid == 0 && key == QKEY_NONE) {
                 out_idx[o] = -1;
                 out_room[o] = -1;
                 out_score[o] = 0.0;
-                last_s = -1e308;
-                last_k = LLONG_MAX;
             }
-        }
-        __syncthreads();
-    }
+        });
 }
 
 namespace {
 
-bool sh_dev_ptr(const void* p) {
-    hipPointerAttribute_t a;
-    memset(&a, 0, sizeof(a));
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return a.type == hipMemoryTypeDevice;
-}
 long long al16(long long b) { return (b + 15) & ~15ll; }
 
 }  // namespace
@@ -451,17 +305,8 @@ long long words_hash(const int* a, int n, unsigned long long h) {     // FNV-1a 
 // only (the offsets).
 void run_sharded(std::vector<Shard>& local, const std::vector<std::string>& pre, int W, int first, hmsg_comm* c, hipStream_t st, const Query& a) {
     const int Q = a.Q, C = a.C, k = a.k, RM = a.max_rooms;
-    std::vector<int> hm((size_t)Q), hf((size_t)Q);
-    if (Q) {
-        memcpy(hm.data(), a.room_mode, (size_t)Q * 4);
-        memcpy(hf.data(), a.floor_id, (size_t)Q * 4);
-    }
-    bool need_label = false, need_view = false, args_ok = true;
-    for (int q = 0; q < Q; ++q) {
-        args_ok = args_ok && hm[(size_t)q] >= 0 && hm[(size_t)q] <= 3 && hf[(size_t)q] >= -1;
-        need_label |= hm[(size_t)q] == 1;
-        need_view |= hm[(size_t)q] >= 2;
-    }
+    const QueryScan sc = hmsg_query_scan(Q, a.room_mode, a.floor_id);
+    const bool need_label = sc.need_label, need_view = sc.need_view;
     // 1. the header exchange = the agreement on every shard's preconditions and on the query arguments (before any payload collective;
     //    through a buffer made with the communicator: agreeing needs no allocation)
     std::vector<long long> meta((size_t)W * M_WORDS, 0);
@@ -469,9 +314,8 @@ void run_sharded(std::vector<Shard>& local, const std::vector<std::string>& pre,
     for (size_t i = 0; i < local.size(); ++i) {
         long long* m = &meta[(size_t)(first + i) * M_WORDS];
         why[i] = pre[i];
-        if (why[i].empty() && !args_ok) why[i] = "hmsg_graph_query_sharded: bad floor id / room mode";
-        if (why[i].empty() && (need_label || need_view) && !a.T_room) why[i] = "hmsg_graph_query_sharded: room text rows missing";
-        if (why[i].empty() && need_label && !local[i].names) why[i] = "hmsg_graph_query_sharded: label mode without room name embeddings";
+        // (the floors of all shards are not known before the exchange: the floor ids are checked against them after it)
+        if (why[i].empty()) why[i] = hmsg_query_precondition("hmsg_graph_query_sharded", sc, -1, a.T_room != nullptr, local[i].names != nullptr);
         m[M_OK] = why[i].empty() ? 1 : 0;
         m[M_Q] = Q;
         m[M_C] = C;
@@ -480,7 +324,7 @@ void run_sharded(std::vector<Shard>& local, const std::vector<std::string>& pre,
         m[M_NEG] = a.use_neg != 0;
         m[M_LABEL] = need_label;
         m[M_VIEW] = need_view;
-        m[M_HASH] = words_hash(hm.data(), Q, words_hash(hf.data(), Q, 1469598103934665603ull));
+        m[M_HASH] = words_hash(a.room_mode, Q, words_hash(a.floor_id, Q, 1469598103934665603ull));
         if (!why[i].empty()) continue;
         hmsg_index* ix = local[i].ix;
         m[M_N] = ix->N;
@@ -526,7 +370,8 @@ void run_sharded(std::vector<Shard>& local, const std::vector<std::string>& pre,
         if (a.floor_off) a.floor_off[s] = foff[(size_t)s];
     }
     if (Q == 0) return;
-    for (int q = 0; q < Q; ++q) HMSG_REQUIRE(hf[(size_t)q] < foff[(size_t)W], HMSG_ERR_INVALID, "hmsg_graph_query_sharded: bad floor id / room mode");
+    const std::string why_floor = hmsg_query_precondition("hmsg_graph_query_sharded", sc, foff[(size_t)W], true, true);
+    HMSG_REQUIRE(why_floor.empty(), HMSG_ERR_INVALID, why_floor);
     // slot layouts of the two payload exchanges
     const long long rows = (long long)Q * lay.Rmax * 8;
     lay.o_lab = 0;
@@ -537,19 +382,14 @@ void run_sharded(std::vector<Shard>& local, const std::vector<std::string>& pre,
     lay.o_vcnt = lay.o_key + al16((long long)lay.Rmax * 4);
     lay.bytes = lay.o_vcnt + al16((long long)lay.Rmax * 4);
     const long long c_cnt = al16((long long)Q * 2 * k * (long long)sizeof(ShRec)), c_bytes = c_cnt + al16((long long)Q * 4);
-    // results: [score f64 Q*k | sel Q*max_rooms | nsel Q | err Q | idx Q*k | room Q*k]
-    const size_t o_sel = (size_t)Q * k * 8, o_nsel = o_sel + (size_t)Q * RM * 4, o_err = o_nsel + (size_t)Q * 4, o_idx = o_err + (size_t)Q * 4,
-                 o_room = o_idx + (size_t)Q * k * 4, out_bytes = o_room + (size_t)Q * k * 4;
+    const QueryOut out(Q, k, RM);
     hmsg_shard_ws& G = *local[0].ws;              // the exchange's buffers
     int *d_floor = nullptr, *d_mode = nullptr, *d_qid = nullptr, *d_roff = nullptr, *d_foff = nullptr;
     // 2. the local room and object stages of every shard held here
     hmsg_comm_local_phase_then_agree(c, st, "hmsg_graph_query_sharded", [&] {
         // per-query words and offsets: one upload (floor | mode | qid | roff | foff)
-        const bool qid_dev = sh_dev_ptr(a.qid);
         std::vector<int> qin((size_t)Q * 3 + 2 * ((size_t)W + 1));
-        memcpy(qin.data(), hf.data(), (size_t)Q * 4);
-        memcpy(qin.data() + Q, hm.data(), (size_t)Q * 4);
-        if (!qid_dev) memcpy(qin.data() + 2 * (size_t)Q, a.qid, (size_t)Q * 4);
+        const bool qid_dev = hmsg_query_pack_words(qin.data(), Q, a.floor_id, a.room_mode, a.qid);
         memcpy(qin.data() + 3 * (size_t)Q, roff.data(), ((size_t)W + 1) * 4);
         memcpy(qin.data() + 3 * (size_t)Q + W + 1, foff.data(), ((size_t)W + 1) * 4);
         G.qin.ensure(qin.size());
@@ -560,22 +400,12 @@ void run_sharded(std::vector<Shard>& local, const std::vector<std::string>& pre,
         d_roff = G.qin.p + 3 * (size_t)Q;
         d_foff = d_roff + W + 1;
         if (qid_dev) HIP_TRY(hipMemcpyAsync(d_qid, a.qid, (size_t)Q * 4, hipMemcpyDeviceToDevice, st));
-        G.out.ensure(out_bytes);
+        G.out.ensure(out.bytes);
         G.room.ensure((size_t)W * (size_t)lay.bytes);
         G.cand.ensure((size_t)W * (size_t)c_bytes);
         G.qrooms.ensure((size_t)Q * RM);
-        auto to_f64 = [&](const float* src, size_t n, DevBuf<float>& tmp, DevBuf<double>& dst) {
-            dst.ensure(n);
-            if (!sh_dev_ptr(src)) {
-                tmp.ensure(n);
-                h2d_bounce(tmp.p, src, n * 4, st);
-                src = tmp.p;
-            }
-            hipLaunchKernelGGL(k_sh_f32_to_f64, dim3(cdiv(n, 256)), dim3(256), 0, st, src, dst.p, n);
-            HMSG_CHECK_LAUNCH();
-        };
-        to_f64(a.T_obj, (size_t)Q * C * D, G.Tf, G.T64);
-        if (need_label || need_view) to_f64(a.T_room, (size_t)Q * D, G.Trf, G.Tr64);
+        hmsg_text_rows_to_f64(st, a.T_obj, (size_t)Q * C * D, G.Tf, G.T64);
+        if (need_label || need_view) hmsg_text_rows_to_f64(st, a.T_room, (size_t)Q * D, G.Trf, G.Tr64);
         for (size_t i = 0; i < local.size(); ++i) {
             Shard& sh = local[i];
             hmsg_shard_ws& L = *sh.ws;
@@ -584,7 +414,7 @@ void run_sharded(std::vector<Shard>& local, const std::vector<std::string>& pre,
             char* slot = G.room.p + (size_t)(first + i) * (size_t)lay.bytes;
             if (need_label && R) {
                 const double* names = sh.names;
-                if (!sh_dev_ptr(names)) {
+                if (!hmsg_is_device_ptr(names)) {
                     L.names.ensure((size_t)R * D);
                     h2d_bounce(L.names.p, names, (size_t)R * D * 8, st);
                     names = L.names.p;
@@ -613,15 +443,12 @@ void run_sharded(std::vector<Shard>& local, const std::vector<std::string>& pre,
             }
         }
     });
-    int* const d_sel = (int*)(G.out.p + o_sel);
-    int* const d_nsel = (int*)(G.out.p + o_nsel);
-    int* const d_err = (int*)(G.out.p + o_err);
     // 3. room rows + tables of every shard to every shard
     if (c) hmsg_comm_allgather_inplace(c, G.room.p, (size_t)lay.bytes, st);
     // 4. the global room selection, the same on every rank; every shard's candidates in the rooms it owns
     hmsg_comm_local_phase_then_agree(c, st, "hmsg_graph_query_sharded", [&] {
         hipLaunchKernelGGL(k_sh_room_select, dim3(Q), dim3(256), 0, st, (const char*)G.room.p, lay.bytes, lay, W, (const int*)d_roff,
-                           (const int*)d_foff, (const int*)d_floor, (const int*)d_mode, RM, d_sel, d_nsel, G.qrooms.p, d_err);
+                           (const int*)d_foff, (const int*)d_floor, (const int*)d_mode, RM, out.sel(G.out.p), out.nsel(G.out.p), G.qrooms.p, out.err(G.out.p));
         HMSG_CHECK_LAUNCH();
         for (size_t i = 0; i < local.size(); ++i) {
             hmsg_index* ix = local[i].ix;
@@ -635,32 +462,13 @@ void run_sharded(std::vector<Shard>& local, const std::vector<std::string>& pre,
     });
     // 5. the candidates to every shard; the merge (no collective follows: what fails from here on fails on its own rank only)
     if (c) hmsg_comm_allgather_inplace(c, G.cand.p, (size_t)c_bytes, st);
-    hipLaunchKernelGGL(k_sh_merge, dim3(Q), dim3(64), 0, st, (const char*)G.cand.p, c_bytes, c_cnt, W, Q, k, a.use_neg, (int*)(G.out.p + o_idx),
-                       (int*)(G.out.p + o_room), (double*)G.out.p);
+    hipLaunchKernelGGL(k_sh_merge, dim3(Q), dim3(64), 0, st, (const char*)G.cand.p, c_bytes, c_cnt, W, Q, k, a.use_neg, out.idx(G.out.p),
+                       out.room(G.out.p), out.score(G.out.p));
     HMSG_CHECK_LAUNCH();
-    std::vector<char> h_out(out_bytes);
-    HIP_TRY(hipMemcpyAsync(h_out.data(), G.out.p, out_bytes, hipMemcpyDeviceToHost, st));
+    std::vector<char> h_out(out.bytes);
+    HIP_TRY(hipMemcpyAsync(h_out.data(), G.out.p, out.bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    bool any_dev = false;
-    auto give = [&](void* dst, size_t off, size_t bytes) {
-        if (sh_dev_ptr(dst)) {
-            HIP_TRY(hipMemcpyAsync(dst, G.out.p + off, bytes, hipMemcpyDeviceToDevice, st));
-            any_dev = true;
-        } else {
-            memcpy(dst, h_out.data() + off, bytes);
-        }
-    };
-    give(a.out_score, 0, (size_t)Q * k * 8);
-    give(a.out_sel, o_sel, (size_t)Q * RM * 4);
-    give(a.out_nsel, o_nsel, (size_t)Q * 4);
-    give(a.out_idx, o_idx, (size_t)Q * k * 4);
-    give(a.out_room, o_room, (size_t)Q * k * 4);
-    if (any_dev) HIP_TRY(hipStreamSynchronize(st));
-    const int* herr = (const int*)(h_out.data() + o_err);
-    for (int q = 0; q < Q; ++q)
-        HMSG_REQUIRE(!herr[q], HMSG_ERR_INVALID,
-                     "hmsg_graph_query_sharded: a query's room stage failed like the reference would (a room without view embeddings, or a "
-                     "view-mode room number that is no position of the floor's room list)");
+    out.give("hmsg_graph_query_sharded", st, G.out.p, h_out.data(), a.out_score, a.out_sel, a.out_nsel, a.out_idx, a.out_room);
 }
 
 template <typename F>

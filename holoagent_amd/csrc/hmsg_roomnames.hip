@@ -176,16 +176,6 @@ __global__ void k_rn_gather_f32(const float* __restrict__ src, const int* __rest
     dst[t] = src[(size_t)row[t / D] * D + t % D];
 }
 
-bool rn_device_ptr(const void* p) {
-    hipPointerAttribute_t a;
-    memset(&a, 0, sizeof(a));
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return a.type == hipMemoryTypeDevice;
-}
-
 }  // namespace
 
 void rn_denoise(hipStream_t s, const void* X, bool f64, int D, const std::vector<long long>& off, double eps, int min_samples, void* out,
@@ -327,12 +317,12 @@ extern "C" int hmsg_denoise_feats_batch(int32_t device_id, int32_t n_sets, const
         hipStream_t s = nullptr;
         DevBuf<char> d_in, d_out;
         const void* X = src;
-        if (!rn_device_ptr(src)) {
+        if (!hmsg_is_device_ptr(src)) {
             d_in.alloc(in_bytes);
             HIP_TRY(hipMemcpyAsync(d_in.p, src, in_bytes, hipMemcpyHostToDevice, s));
             X = d_in.p;
         }
-        const bool out_dev = rn_device_ptr(out);
+        const bool out_dev = hmsg_is_device_ptr(out);
         if (!out_dev) d_out.alloc(out_bytes);
         rn_denoise(s, X, feats_is_f64 != 0, dim, off, eps, min_samples, out_dev ? out : (void*)d_out.p, n_in_cluster);
         if (!out_dev) HIP_TRY(hipMemcpyAsync(out, d_out.p, out_bytes, hipMemcpyDeviceToHost, s));
