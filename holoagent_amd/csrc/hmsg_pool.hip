@@ -482,51 +482,17 @@ void pool_launch_mean_f32(hipStream_t s, const float* X, int D, const PoolSeg* d
     HMSG_CHECK_LAUNCH();
 }
 
-void hmsg_pool(hmsg_ctx* h) {
-    const hmsg_config& c = h->cfg;
-    hipStream_t s = h->stream;
-    HMSG_REQUIRE(h->merged, HMSG_ERR_INVALID, "hmsg_pool_instances: run hmsg_merge_instances first");
-    const int K = (int)h->inst.off.size() - 1;
-    const int D = c.feat_dim;
-    h->inst_feats.alloc((size_t)std::max(K, 1) * D);
-    if (K == 0) {
-        h->pooled = true;
-        return;
-    }
-    CloudOps ops;
-    ops.s = s;
-    DbgLaps laps("pool", s);
-    // (a) voxel_down_sample(voxel_size) of every instance (graph.py:456)
-    std::vector<SegDesc> segs(K);
-    for (int k = 0; k < K; ++k) {
-        segs[k].pt_base = h->inst.off[k];
-        segs[k].n = (int)(h->inst.off[k + 1] - h->inst.off[k]);
-    }
-    ops.bounds(h->inst.pts.p, segs);
-    DevBuf<double> ds;
-    ds.alloc((size_t)std::max<long long>(h->inst.total, 1) * 3);
-    std::vector<int> dn;
-    const long long P = ops.voxel_down_sample(h->inst.pts.p, segs, c.voxel_size, ds.p, dn);
-    laps.lap("voxel_down_sample");
-    // (b) nearest map voxel, dist <= 0.8
-    DevBuf<int> idx;
-    DevBuf<unsigned> valid, pos;
-    idx.alloc((size_t)std::max<long long>(P, 1));
-    valid.alloc((size_t)std::max<long long>(P, 1));
+// The rows behind the nearest-voxel step: idx[i] / valid[i] (device) for the P down-sampled points of K instances, dn[k] of them
+// in instance k, in instance order.  Valid rows are packed (scan of `valid` -> pos, the instances' row offsets hpos -> PoolSeg),
+// gathered from the feature table `feats` ([.][D], device) with nan_to_num, and every instance goes through the cosine DBSCAN and the
+// mean over its largest cluster -> out (device, [K][D]); an instance without a valid row gives zeros.
+static void pool_rows(hipStream_t s, DevBuf<unsigned>& scan_tmp, Prof* prof, DbgLaps& laps, const int* idx, const unsigned* valid,
+                      long long P, const std::vector<int>& dn, const float* feats, int D, double eps, int minpts, float* out) {
+    const int K = (int)dn.size();
+    DevBuf<unsigned> pos;
     pos.alloc((size_t)std::max<long long>(P, 1));
-    if (P) {
-        TieBuf ties;
-        for (;;) {
-            ties.prepare(s);
-            hipLaunchKernelGGL(k_pool_nn, dim3(cdiv((size_t)P, 256)), dim3(256), 0, s, (const double*)ds.p, P, hmsg_nn_index(h),
-                               c.pool_max_dist, idx.p, valid.p, ties.list());
-            HMSG_CHECK_LAUNCH();
-            if (hmsg_resolve_ties(h, ties, idx.p)) break;     // bit-equal ties answered like cKDTree (hmsg_ckdtree.h)
-        }
-    }
-    laps.lap("nearest map voxel");
     unsigned long long R = 0;   // total valid rows
-    if (P) hmsg_scan_u32(valid.p, pos.p, (size_t)P, s, ops.scan_tmp, &R);
+    if (P) hmsg_scan_u32(valid, pos.p, (size_t)P, s, scan_tmp, &R);
     // rows per instance = pos at the instance boundaries
     std::vector<long long> pstart(K + 1, 0);
     for (int k = 0; k < K; ++k) pstart[k + 1] = pstart[k] + dn[k];
@@ -599,35 +565,131 @@ void hmsg_pool(hmsg_ctx* h) {
     best.zero(s);
     laps.lap("row offsets + buffers");
     if (R) {
-        hipLaunchKernelGGL(k_pool_gather, dim3(cdiv((size_t)P * 64, 256)), dim3(256), 0, s, (const int*)idx.p,
-                           (const unsigned*)valid.p, (const unsigned*)pos.p, P, (const float*)h->feats.p, D, X.p, Xn.p);
+        hipLaunchKernelGGL(k_pool_gather, dim3(cdiv((size_t)P * 64, 256)), dim3(256), 0, s, idx,
+                           valid, (const unsigned*)pos.p, P, feats, D, X.p, Xn.p);
         hipLaunchKernelGGL(k_seg_rows, dim3(std::max(1u, std::min(cdiv(maxn, 256), 256u)), K), dim3(256), 0, s,
                            (const PoolSeg*)d_ps.p, seg_of_row.p);
         laps.lap("gather + normalise");
         {
             double flop = 0;
             for (auto& g : ps) flop += (double)g.n * ((double)g.n + 1.0) * D;   // unique pairs x 2 FLOP x D
-            ProfScope psc(h->prof, s, "k_pool_gram", flop);
+            ProfScope psc(prof, s, "k_pool_gram", flop);
             hipLaunchKernelGGL(k_pool_gram, dim3((unsigned)tiles), dim3(256), 0, s, (const float*)Xn.p, D, (const PoolSeg*)d_ps.p, K,
-                               (float)c.feat_dbscan_eps, adj.p, ncount.p);
+                               (float)eps, adj.p, ncount.p);
         }
         laps.lap("k_pool_gram");
-        pool_cluster(s, (const PoolSeg*)d_ps.p, (long long)R, c.feat_dbscan_min, (const unsigned*)adj.p, (const unsigned*)ncount.p,
+        pool_cluster(s, (const PoolSeg*)d_ps.p, (long long)R, minpts, (const unsigned*)adj.p, (const unsigned*)ncount.p,
                      (const int*)seg_of_row.p, label.p, seg_first.p, d_changed.p, flabel.p, csize.p, cfirst.p, best.p, &laps);
     }
     laps.lap("border + pick");
-    hmsg_dump("pool_ds", ds.p, (size_t)P * 24, s);
-    hmsg_dump("pool_idx", idx.p, (size_t)P * 4, s);
-    hmsg_dump("pool_valid", valid.p, (size_t)P * 4, s);
     hmsg_dump("pool_ncount", ncount.p, (size_t)R * 4, s);
     hmsg_dump("pool_flabel", flabel.p, (size_t)R * 4, s);
     hmsg_dump("pool_label", label.p, (size_t)R * 4, s);
     hmsg_dump("pool_segs", d_ps.p, (size_t)K * sizeof(PoolSeg), s);
     hipLaunchKernelGGL(k_pool_mean, dim3(cdiv(D, 64), K), dim3(64), 0, s, (const float*)X.p, D, (const PoolSeg*)d_ps.p, K,
                        (const int*)flabel.p, (const unsigned*)csize.p, (const unsigned*)cfirst.p,
-                       (const unsigned long long*)best.p, h->inst_feats.p);
+                       (const unsigned long long*)best.p, out);
     HMSG_CHECK_LAUNCH();
     HIP_TRY(hipStreamSynchronize(s));
     laps.lap("k_pool_mean");
+}
+
+void hmsg_pool(hmsg_ctx* h) {
+    const hmsg_config& c = h->cfg;
+    hipStream_t s = h->stream;
+    HMSG_REQUIRE(h->merged, HMSG_ERR_INVALID, "hmsg_pool_instances: run hmsg_merge_instances first");
+    const int K = (int)h->inst.off.size() - 1;
+    const int D = c.feat_dim;
+    h->inst_feats.alloc((size_t)std::max(K, 1) * D);
+    if (K == 0) {
+        h->pooled = true;
+        return;
+    }
+    CloudOps ops;
+    ops.s = s;
+    DbgLaps laps("pool", s);
+    // (a) voxel_down_sample(voxel_size) of every instance (graph.py:456)
+    std::vector<SegDesc> segs(K);
+    for (int k = 0; k < K; ++k) {
+        segs[k].pt_base = h->inst.off[k];
+        segs[k].n = (int)(h->inst.off[k + 1] - h->inst.off[k]);
+    }
+    ops.bounds(h->inst.pts.p, segs);
+    DevBuf<double> ds;
+    ds.alloc((size_t)std::max<long long>(h->inst.total, 1) * 3);
+    std::vector<int> dn;
+    const long long P = ops.voxel_down_sample(h->inst.pts.p, segs, c.voxel_size, ds.p, dn);
+    laps.lap("voxel_down_sample");
+    // (b) nearest map voxel, dist <= 0.8
+    DevBuf<int> idx;
+    DevBuf<unsigned> valid;
+    idx.alloc((size_t)std::max<long long>(P, 1));
+    valid.alloc((size_t)std::max<long long>(P, 1));
+    if (P) {
+        TieBuf ties;
+        for (;;) {
+            ties.prepare(s);
+            hipLaunchKernelGGL(k_pool_nn, dim3(cdiv((size_t)P, 256)), dim3(256), 0, s, (const double*)ds.p, P, hmsg_nn_index(h),
+                               c.pool_max_dist, idx.p, valid.p, ties.list());
+            HMSG_CHECK_LAUNCH();
+            if (hmsg_resolve_ties(h, ties, idx.p)) break;     // bit-equal ties answered like cKDTree (hmsg_ckdtree.h)
+        }
+    }
+    laps.lap("nearest map voxel");
+    hmsg_dump("pool_ds", ds.p, (size_t)P * 24, s);
+    hmsg_dump("pool_idx", idx.p, (size_t)P * 4, s);
+    hmsg_dump("pool_valid", valid.p, (size_t)P * 4, s);
+    pool_rows(s, ops.scan_tmp, &h->prof, laps, idx.p, valid.p, P, dn, h->feats.p, D, c.feat_dbscan_eps, c.feat_dbscan_min, h->inst_feats.p);
     h->pooled = true;
+}
+
+// ---- test hook (include/hmsg_test.h: hmsg_test_pool_rows): pool_rows on host arrays
+extern "C" int hmsg_test_pool_rows(int32_t device_id, int32_t K, const int32_t* counts, const int32_t* idx, const uint8_t* valid,
+                                   const float* table, int64_t table_rows, int32_t dim, double eps, int32_t min_samples, float* out) {
+    if (K < 0 || (K > 0 && (!counts || !out)) || dim <= 0 || table_rows < 0 || !(eps > 0.0) || min_samples < 1) return HMSG_ERR_INVALID;
+    if (K == 0) return HMSG_OK;
+    hipStream_t s = nullptr;
+    int rc = HMSG_OK;
+    try {
+        std::vector<int> dn((size_t)K);
+        long long P = 0;
+        for (int k = 0; k < K; ++k) {
+            HMSG_REQUIRE(counts[k] >= 0, HMSG_ERR_INVALID, "negative row count");
+            dn[(size_t)k] = counts[k];
+            P += counts[k];
+        }
+        HMSG_REQUIRE(P < (1ll << 31), HMSG_ERR_UNSUPPORTED, "more than 2^31 rows");
+        HMSG_REQUIRE(P == 0 || (idx && valid && table), HMSG_ERR_INVALID, "rows without idx / valid / table");
+        std::vector<unsigned> hv((size_t)std::max<long long>(P, 1), 0u);
+        for (long long i = 0; i < P; ++i) {
+            hv[(size_t)i] = valid[i] ? 1u : 0u;
+            HMSG_REQUIRE(!valid[i] || (idx[i] >= 0 && idx[i] < table_rows), HMSG_ERR_INVALID, "a valid row points outside the table");
+        }
+        HIP_TRY(hipSetDevice(device_id));
+        HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        {
+            DevBuf<int> d_idx;
+            DevBuf<unsigned> d_valid, scan_tmp;
+            DevBuf<float> d_table, d_out;
+            d_idx.alloc((size_t)std::max<long long>(P, 1));
+            d_valid.alloc((size_t)std::max<long long>(P, 1));
+            d_table.alloc((size_t)std::max<long long>(table_rows, 1) * dim);
+            d_out.alloc((size_t)K * dim);
+            if (P) {
+                HIP_TRY(hipMemcpyAsync(d_idx.p, idx, (size_t)P * 4, hipMemcpyHostToDevice, s));
+                HIP_TRY(hipMemcpyAsync(d_valid.p, hv.data(), (size_t)P * 4, hipMemcpyHostToDevice, s));
+            }
+            if (table_rows) HIP_TRY(hipMemcpyAsync(d_table.p, table, (size_t)table_rows * dim * 4, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            DbgLaps laps("pool_rows", s);
+            pool_rows(s, scan_tmp, nullptr, laps, d_idx.p, d_valid.p, P, dn, d_table.p, dim, eps, min_samples, d_out.p);
+            HIP_TRY(hipMemcpyAsync(out, d_out.p, (size_t)K * dim * 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+        }
+    } catch (const hmsg_error& e) {
+        fprintf(stderr, "hmsg_test_pool_rows: %s\n", e.msg.c_str());
+        rc = e.code;
+    }
+    if (s) (void)hipStreamDestroy(s);
+    return rc;
 }

@@ -42,6 +42,14 @@ int hmsg_test_repeat_add(const double* s, const double* p, const int32_t* len, d
 int hmsg_test_ckdtree(const double* pts, int64_t n, const double* queries, int64_t nq, int64_t* out_idx,
                       int64_t* out_indices, int64_t* out_n_nodes);
 
+/* test hook: the part of hmsg_pool_instances behind the nearest-voxel step (graph.py:462-491 with feats_denoise_dbscan,
+ * utils/graph_utils.py:682-728) on host arrays.  K instances; counts[k] down-sampled points of instance k, concatenated in
+ * idx / valid: idx[i] is the row of table ([table_rows][dim] float32) point i snapped to, valid[i] != 0 keeps the point.
+ * The kept rows are gathered with nan_to_num, clustered per instance (cosine DBSCAN, eps, min_samples) and averaged over the
+ * largest cluster: out [K][dim] float32; an instance without a kept point gives zeros. */
+int hmsg_test_pool_rows(int32_t device_id, int32_t K, const int32_t* counts, const int32_t* idx, const uint8_t* valid,
+                        const float* table, int64_t table_rows, int32_t dim, double eps, int32_t min_samples, float* out);
+
 /* the caching allocator's carving of a very large parked block (the frame store of a long episode handed back before the
  * merge: its block serves the merge's arenas instead of fresh hipMallocs): parks one block of `root_gb` GB, carves
  * three requests out of it, checks that they lie inside it and are disjoint, that nothing can be freed while a piece is
