@@ -72,6 +72,10 @@ class HmsgGraphRoom(C.Structure):      # include/hmsg.h: hmsg_graph_room
                 ("n_embeddings", C.c_int32), ("n_sample_images", C.c_int32), ("n_objects", C.c_int32), ("n_views", C.c_int32)]
 
 
+class HmsgGraphView(C.Structure):      # include/hmsg.h: hmsg_graph_view
+    _fields_ = [("view", C.c_int32), ("room", C.c_int32), ("img_id", C.c_int64), ("n_objects", C.c_int32), ("reserved_", C.c_int32)]
+
+
 class HmsgError(RuntimeError):
     pass
 
@@ -143,6 +147,16 @@ _SIGS = {
     "hmsg_load": (C.c_int, [C.c_char_p, C.c_int32, C.POINTER(_P)]),
     "hmsg_graph_index": (C.c_int, [_P, _P, C.POINTER(_P)]),
     "hmsg_graph_query": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
+    "hmsg_graph_get_views": (C.c_int, [_P, _P, C.c_int64]),
+    "hmsg_graph_get_view_objects": (C.c_int, [_P, C.c_int32, _P, C.c_int64]),
+    "hmsg_graph_find_view": (C.c_int, [_P, C.c_char_p, C.c_int64, C.POINTER(C.c_int32)]),
+    "hmsg_graph_object_best_views": (C.c_int, [_P, C.c_int32, _P, _P, _P]),
+    "hmsg_graph_goal_views": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, _P, _P, _P, _P]),
+    "hmsg_graph_rematch_in_views": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "hmsg_graph_object_view_depths": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    "hmsg_index_set_views": (C.c_int, [_P, C.c_int64, _P, _P]),
+    "hmsg_rematch_in_views": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P]),
+    "hmsg_points_view_depths": (C.c_int, [C.c_int32, C.c_int64, _P, _P, _P, _P, _P, C.c_double, C.c_double, _P, _P, _P]),
     "hmsg_graph_name_rooms": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P]),
     "hmsg_graph_set_room_names": (C.c_int, [_P, C.c_int32, _P]),
     "hmsg_denoise_feats_batch": (C.c_int, [C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_double, C.c_int32, _P, _P]),
@@ -890,6 +904,69 @@ class SceneGraph:
                                            _ptr(sel), _ptr(nsel), _ptr(idx), _ptr(room), _ptr(score)))
         return [sel[q, : nsel[q]].tolist() for q in range(Q)], idx, room, score
 
+    # ---- the view level of the slow path (include/hmsg.h: Graph.query_room_obj_slow_reasoning between its VLM calls)
+    def views(self):
+        n = self.counts()["views"]
+        arr = (HmsgGraphView * max(n, 1))()
+        self._ck(self.L.c.hmsg_graph_get_views(self.g, C.cast(arr, _P), n))
+        return [dict(view=a.view, room=a.room, img_id=a.img_id, n_objects=a.n_objects) for a in arr[:n]]
+
+    def view_objects(self, view, n=None):
+        n = int(n if n is not None else self.views()[view]["n_objects"])
+        out = np.zeros(max(n, 1), np.int32)
+        self._ck(self.L.c.hmsg_graph_get_view_objects(self.g, int(view), _ptr(out), n))
+        return out[:n]
+
+    def find_view(self, img_path=None, img_id=-1):
+        """find_view_by_imgpath: by path when given, otherwise by image id; -1 when there is none"""
+        v = C.c_int32(-1)
+        self._ck(self.L.c.hmsg_graph_find_view(self.g, None if img_path is None else str(img_path).encode(), int(img_id), C.byref(v)))
+        return v.value
+
+    def object_best_views(self, objs):
+        objs = np.ascontiguousarray(objs, dtype=np.int32)
+        view, img = np.full(max(len(objs), 1), -1, np.int32), np.full(max(len(objs), 1), -1, np.int64)
+        self._ck(self.L.c.hmsg_graph_object_best_views(self.g, len(objs), _ptr(objs), _ptr(view), _ptr(img)))
+        return view[: len(objs)], img[: len(objs)]
+
+    def goal_views(self, T, floor_id, k=24):
+        """hmsg_graph_goal_views -> (img ids [Q][k], rooms [Q][k], scores [Q][k], counts [Q]); -1 / -1 / 0.0 past the count"""
+        T = np.ascontiguousarray(T, dtype=np.float32)
+        Q = len(T)
+        floor_id = np.ascontiguousarray(floor_id, dtype=np.int32)
+        assert T.ndim == 2 and floor_id.shape == (Q,)
+        img, room = np.empty((Q, k), np.int64), np.empty((Q, k), np.int32)
+        score, n = np.empty((Q, k), np.float64), np.empty((Q,), np.int32)
+        self._ck(self.L.c.hmsg_graph_goal_views(self.g, Q, _ptr(T), _ptr(floor_id), int(k), _ptr(img), _ptr(room), _ptr(score), _ptr(n)))
+        return img, room, score, n
+
+    def rematch_in_views(self, T, view, pose_inv=None, wh=None, K=None):
+        """hmsg_graph_rematch_in_views -> (object index [Q], score [Q], avg distance [Q] or None)"""
+        T = np.ascontiguousarray(T, dtype=np.float32)
+        Q = len(T)
+        view = np.ascontiguousarray(view, dtype=np.int32)
+        assert T.ndim == 2 and view.shape == (Q,)
+        obj, score = np.empty((Q,), np.int32), np.empty((Q,), np.float64)
+        Pi = dist = whp = Kp = None
+        if pose_inv is not None:
+            Pi = np.ascontiguousarray(np.asarray(pose_inv, np.float64).reshape(Q, 16))
+            whp = np.ascontiguousarray(np.broadcast_to(np.asarray(wh, np.int32), (Q, 2)))
+            Kp = np.ascontiguousarray(np.asarray(K, np.float64).reshape(9))
+            dist = np.empty((Q,), np.float64)
+        self._ck(self.L.c.hmsg_graph_rematch_in_views(self.g, Q, _ptr(T), _ptr(view), _ptr(Pi), _ptr(whp), _ptr(Kp), _ptr(obj), _ptr(score), _ptr(dist)))
+        return obj, score, dist
+
+    def object_view_depths(self, objs, pose_inv, wh, K):
+        """hmsg_graph_object_view_depths: check_object_in_view(..., return_depth=True) -> (visible bool [n], mean_depth [n])"""
+        objs = np.ascontiguousarray(objs, dtype=np.int32)
+        n = len(objs)
+        Pi = np.ascontiguousarray(np.asarray(pose_inv, np.float64).reshape(n, 16))
+        whp = np.ascontiguousarray(np.broadcast_to(np.asarray(wh, np.int32), (n, 2)))
+        Kp = np.ascontiguousarray(np.asarray(K, np.float64).reshape(9))
+        vis, md = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.float64)
+        self._ck(self.L.c.hmsg_graph_object_view_depths(self.g, n, _ptr(objs), _ptr(Pi), _ptr(whp), _ptr(Kp), _ptr(vis), _ptr(md)))
+        return vis[:n].astype(bool), md[:n]
+
     def query_sharded(self, comm: "Comm", T_obj, qid, T_room, floor_id, room_mode, k, use_negatives=True, room_name_emb=None, max_rooms=None):
         """hmsg_graph_query_sharded: one call per rank with the same queries; the answer of hmsg_query_hier on the concatenated tables,
         on every rank, with no table gathered.  -> (sel, idx, room, score, node_off, room_off, floor_off), offsets [world + 1]."""
@@ -959,6 +1036,28 @@ def sharded_query_bytes(world, Q, k, rooms, floors, floor_rooms, label=True, vie
 
 
 ROOM_NAMES_OBJ_EMBEDDING, ROOM_NAMES_VIEW_EMBEDDING = 1, 2     # include/hmsg.h: HMSG_ROOM_NAMES_*
+
+
+def points_view_depths(clouds, pose_inv, wh, K, min_visible_ratio=0.5, max_depth=10.0, device_id=0, lib_: "HmsgLib | None" = None):
+    """hmsg_points_view_depths: cloud p (float64 [n][3]) through camera p -> (avg_z_front [P] (NaN: no point in front of the camera),
+    visible bool [P], mean_depth [P] (inf as check_object_in_view returns it))"""
+    L = lib_ or lib()
+    P = len(clouds)
+    off = np.zeros(P + 1, np.int64)
+    for i, c in enumerate(clouds):
+        off[i + 1] = off[i] + len(c)
+    pts = np.ascontiguousarray(np.concatenate([np.asarray(c, np.float64).reshape(-1, 3) for c in clouds], 0)) if P else np.zeros((0, 3))
+    if not len(pts):
+        pts = np.zeros((1, 3), np.float64)
+    Pi = np.ascontiguousarray(np.asarray(pose_inv, np.float64).reshape(max(P, 0), 16))
+    whp = np.ascontiguousarray(np.broadcast_to(np.asarray(wh, np.int32), (P, 2)))
+    Kp = np.ascontiguousarray(np.asarray(K, np.float64).reshape(9))
+    avg, vis, md = np.zeros(max(P, 1), np.float64), np.zeros(max(P, 1), np.uint8), np.zeros(max(P, 1), np.float64)
+    rc = L.c.hmsg_points_view_depths(int(device_id), P, _ptr(off), _ptr(pts), _ptr(Pi), _ptr(whp), _ptr(Kp), float(min_visible_ratio), float(max_depth),
+                                     _ptr(avg), _ptr(vis), _ptr(md))
+    if rc != 0:
+        raise HmsgError(f"hmsg_points_view_depths failed ({rc})")
+    return avg[:P], vis[:P].astype(bool), md[:P]
 
 
 def denoise_feats_batch(sets, eps=0.02, min_samples=2, device_id=0, lib_: "HmsgLib | None" = None):
@@ -1294,6 +1393,24 @@ class NodeIndex:
         self._ck(self.L.c.hmsg_query_objects(self.ix, Q, Cn, _ptr(T), _ptr(qid), _ptr(off), _ptr(rooms), k,
                                              int(use_negatives), _ptr(idx), _ptr(room), _ptr(score)))
         return idx, room, score
+
+    def set_views(self, view_lists):
+        """hmsg_index_set_views: per view the node indices of its objects, in view.object_ids order"""
+        off = np.zeros(len(view_lists) + 1, np.int64)
+        for i, l in enumerate(view_lists):
+            off[i + 1] = off[i] + len(l)
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(l, np.int32).reshape(-1) for l in view_lists]) if len(view_lists) else np.zeros(0), dtype=np.int32)
+        if not len(flat):
+            flat = np.zeros(1, np.int32)
+        self._ck(self.L.c.hmsg_index_set_views(self.ix, len(view_lists), _ptr(off), _ptr(flat)))
+
+    def rematch_in_views(self, T, view):
+        """hmsg_rematch_in_views -> (node [Q] (-1: a view without objects), score [Q])"""
+        T = np.ascontiguousarray(T, dtype=np.float32)
+        view = np.ascontiguousarray(view, dtype=np.int32)
+        node, score = np.empty(len(T), np.int32), np.empty(len(T), np.float64)
+        self._ck(self.L.c.hmsg_rematch_in_views(self.ix, len(T), _ptr(T), _ptr(view), _ptr(node), _ptr(score)))
+        return node, score
 
     def similarity(self, T):
         T = np.ascontiguousarray(T, dtype=np.float32)

@@ -11,6 +11,7 @@
 // object id = (room, running counter of that room) (:1696-1700).
 #include "hmsg_common.h"
 #include "hmsg_nn.h"
+#include "hmsg_view_project.h"
 #include <chrono>
 #include "hmsg_ckdtree.h"
 
@@ -651,28 +652,17 @@ __global__ void __launch_bounds__(256) k_object_views(const double* __restrict__
     __shared__ double s_z[4];
     __shared__ int s_c[4][2];
     const ViewPair pr = pairs[blockIdx.x];
-    const double* P = pose_inv + (size_t)pr.view * 16;
-    const double W = (double)wh[(size_t)pr.view * 2], H = (double)wh[(size_t)pr.view * 2 + 1];
-    double P_[12], K_[9];
-    for (int i = 0; i < 12; ++i) P_[i] = P[i];
-    for (int i = 0; i < 9; ++i) K_[i] = Kmat[i];
+    const ViewCam cam = view_cam_load(pose_inv + (size_t)pr.view * 16, Kmat, wh + (size_t)pr.view * 2);
     int n_front = 0, n_in = 0;
     double zsum = 0.0;
     for (int k = threadIdx.x; k < pr.n; k += blockDim.x) {
-        const double* q = pts + (size_t)(pr.p0 + k) * 3;
-        const double x = q[0], y = q[1], z = q[2];
-        double c[3];
-        for (int r = 0; r < 3; ++r)
-            c[r] = fma(P_[r * 4 + 3], 1.0, fma(P_[r * 4 + 2], z, fma(P_[r * 4 + 1], y, __dmul_rn(P_[r * 4], x))));
-        if (!(c[2] > 0.0)) continue;
+        double cz;
+        const int where = view_point(cam, pts + (size_t)(pr.p0 + k) * 3, &cz);
+        if (where == VIEW_POINT_BEHIND) continue;
         ++n_front;
-        double ph[3];
-        for (int r = 0; r < 3; ++r)
-            ph[r] = fma(K_[r * 3 + 2], c[2], fma(K_[r * 3 + 1], c[1], __dmul_rn(K_[r * 3], c[0])));
-        const double u = __ddiv_rn(ph[0], ph[2]), v = __ddiv_rn(ph[1], ph[2]);
-        if (u >= 0.0 && u < W && v >= 0.0 && v < H) {
+        if (where == VIEW_POINT_INSIDE) {
             ++n_in;
-            zsum = __dadd_rn(zsum, c[2]);
+            zsum = __dadd_rn(zsum, cz);
         }
     }
     n_front = wave_sum_i32(n_front);

@@ -42,6 +42,13 @@ struct hmsg_index {
     DevBuf<int> d_qin;
     PinnedBuf<char> h_qout;
     DevBuf<char> d_qout;
+    // the view level below the rooms (hmsg_index_set_views, hmsg_query_views.hip): CSR view -> nodes in view.object_ids order
+    long long n_obj_views = -1;     // -1: not set
+    std::vector<long long> h_vo_off;
+    DevBuf<long long> vo_off;       // [n_obj_views + 1]
+    DevBuf<int> vo_nodes;
+    DevBuf<int> d_view, d_vnode;    // scratch of hmsg_rematch_in_views
+    DevBuf<double> d_vscore;
     Prof prof;                   // live timing of the GEMM (hmsg_index_set_profiling)
 };
 
@@ -49,6 +56,21 @@ struct hmsg_index {
 // kernel when M >= 64 and N >= 64, the one-wave-per-16x16-tile kernel otherwise.  Both chain the same v_mfma_f64_16x16x4_f64
 // k-steps (k = 0, 4, 8, ... from a zero accumulator; the tiled kernel adds zero products past D up to its 16-wide step), so an
 // entry S[m][n] has the same bits whichever kernel computed it and wherever its rows sit in A and B.
+// One wave's 16x16 tile of that product: the chain of v_mfma_f64_16x16x4_f64 steps k = 0, 4, 8, ... from a zero accumulator.  Lane l
+// feeds A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15] (ap / bp: the lane's row of A / B, a_ok / b_ok: whether that row
+// exists -- a missing row feeds zeros); result register r of lane l is C[row = (l >> 4) + 4 r][col = l & 15].  Every kernel that
+// must give hmsg_similarity's bits for an entry (the one-wave-per-tile GEMM, the re-match of hmsg_query_views.hip) goes through it.
+__device__ __forceinline__ f64x4 gemm_f64_tile16(const double* __restrict__ ap, bool a_ok, const double* __restrict__ bp, bool b_ok, int D) {
+    f64x4 acc = {0.0, 0.0, 0.0, 0.0};
+    const int kq = (threadIdx.x & 63) >> 4;
+    for (int k0 = 0; k0 < D; k0 += 4) {
+        const int k = k0 + kq;
+        const double a = (k < D && a_ok) ? ap[k] : 0.0;
+        const double b = (k < D && b_ok) ? bp[k] : 0.0;
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
+    }
+    return acc;
+}
 void hmsg_gemm_f64(const double* A, int M, const double* B, long long N, int D, double* S, hipStream_t s);
 // an index without a node table, for hmsg_index_set_hierarchy only: a shard whose rooms hold no object (hmsg_query_sharded.hip)
 hmsg_index* hmsg_index_create_rooms_only(int device, int D);

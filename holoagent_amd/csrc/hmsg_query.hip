@@ -43,14 +43,7 @@ __global__ void __launch_bounds__(256) k_gemm_f64(const double* __restrict__ A, 
     const long long br = n0 + (lane & 15);
     const double* ap = A + (size_t)(ar < M ? ar : M - 1) * D;
     const double* bp = B + (size_t)(br < N ? br : N - 1) * D;
-    f64x4 acc = {0.0, 0.0, 0.0, 0.0};
-    const int kq = lane >> 4;
-    for (int k0 = 0; k0 < D; k0 += 4) {
-        int k = k0 + kq;
-        double a = (k < D && ar < M) ? ap[k] : 0.0;
-        double b = (k < D && br < N) ? bp[k] : 0.0;
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
-    }
+    const f64x4 acc = gemm_f64_tile16(ap, ar < M, bp, br < N, D);
     if (!active) return;
     const long long col = n0 + (lane & 15);
     for (int r = 0; r < 4; ++r) {

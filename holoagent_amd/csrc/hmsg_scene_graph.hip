@@ -12,6 +12,7 @@
 #include "hmsg_common.h"
 #include "hmsg_dbscan.h"
 #include "hmsg_query.h"
+#include "hmsg_query_views.h"
 
 #include <dirent.h>
 #include <sys/stat.h>
@@ -119,12 +120,29 @@ struct hmsg_graph {
                                             // without room names (they come with every call); the levels above the nodes only for a
                                             // graph without objects.  hmsg_graph_query's `ix` is never touched by that path.
     hmsg_shard_ws* shard_ws = nullptr;      // that path's scratch, kept between calls (hmsg_query_sharded.hip)
+    // the view level of the slow path (hmsg_graph_goal_views, hmsg_graph_rematch_in_views, hmsg_graph_object_view_depths), each made on
+    // first use and freed with the graph
+    hmsg_goal_table* goal = nullptr;        // every sampled image's CLIP embedding, float64 in HBM
+    std::vector<std::string> goal_bad;      // per room: "" or why its rows cannot be searched (the reference asserts there, :2870)
+    std::vector<std::vector<int>> view_lists;   // per view: find_object_by_object_id of every entry of object_ids, in that order; made
+                                                // by hmsg_graph_finish / hmsg_load with the views, so the listing calls only read
+    bool views_on_index = false;            // view_lists are resident on shard_ix (hmsg_index_set_views)
+    DevBuf<double> obj_pts;                 // loaded graphs: the objects' clouds one after the other, uploaded once
+    std::vector<long long> obj_pts_off;
+    bool have_obj_pts = false;
+    hipStream_t view_stream = nullptr;      // the stream of the distance kernels
     ~hmsg_graph() {
         for (auto& t : workers)
             if (t.joinable()) t.join();
         if (ix) hmsg_index_destroy(ix);
         if (shard_ix) hmsg_index_destroy(shard_ix);
         if (shard_ws) hmsg_shard_ws_free(shard_ws);
+        if (goal) hmsg_goal_table_free(goal);
+        if (view_stream) {
+            (void)hipSetDevice(device);
+            (void)hipStreamSynchronize(view_stream);
+            (void)hipStreamDestroy(view_stream);
+        }
     }
 };
 
@@ -444,6 +462,19 @@ void join_workers(hmsg_graph* g) {
     if (!g->worker_err.empty()) throw hmsg_error{HMSG_ERR_INVALID, g->worker_err};
 }
 
+// per view: find_object_by_object_id (graph.py:2572-2576: the first object that carries the id) of every entry of view.object_ids,
+// in that order (:2968-2973; an id no object carries makes the reference assert -- it is left out here)
+void build_view_lists(hmsg_graph* g) {
+    std::map<std::string, int> obj_of_id;
+    for (size_t k = 0; k < g->objects.size(); ++k) obj_of_id.emplace(g->objects[k].id, (int)k);
+    g->view_lists.assign(g->views.size(), {});
+    for (size_t v = 0; v < g->views.size(); ++v)
+        for (auto& oid : g->views[v].object_ids) {
+            auto it = obj_of_id.find(oid);
+            if (it != obj_of_id.end()) g->view_lists[v].push_back(it->second);
+        }
+}
+
 // ---- stage 3: View nodes (:1176-1189), objects (:1582-1736), edges (:1752-1775)
 void graph_finish(hmsg_graph* g, int32_t n_labels, const float* label_feats, const char* const* label_names) {
     hmsg_ctx* h = g->h;
@@ -577,6 +608,7 @@ void graph_finish(hmsg_graph* g, int32_t n_labels, const float* label_feats, con
         throw hmsg_error{HMSG_ERR_INVALID, "hmsg_graph_edges failed"};
     g->edges.resize((size_t)ne * 2);
     laps.lap("edges");
+    build_view_lists(g);
     g->finished = true;
 }
 
@@ -1378,6 +1410,21 @@ int hmsg_load(const char* dir, int32_t device_id, hmsg_graph_t** out) {
             g->rooms[(size_t)it->second].views.push_back((int)g->views.size());
             g->views.push_back(std::move(v));
         }
+        // best_view_id / view_ids -> view indices (graph.py:2759-2765 walks self.views for the id: the first view that carries it; an
+        // id that names no view leaves best_view = None there, -1 here)
+        std::map<std::string, int> view_of_id;
+        for (size_t v = 0; v < g->views.size(); ++v) view_of_id.emplace(g->views[v].id, (int)v);
+        for (auto& o : g->objects) {
+            for (auto& vid : o.view_ids) {
+                auto it = view_of_id.find(vid);
+                if (it != view_of_id.end()) o.views.push_back(it->second);
+            }
+            if (o.have_best) {
+                auto it = view_of_id.find(o.best_view_id);
+                if (it != view_of_id.end()) o.best_view = it->second;
+            }
+        }
+        build_view_lists(g);
         // edges as load_hmsg_graph adds them: (0, floor) per floor, (floor, room) per room, (room, object) per object, (room, view)
         // per view -- the loader adds no View - Object edge
         const long long F = (long long)g->floors.size(), R = (long long)g->rooms.size(), O = (long long)g->objects.size();
@@ -1729,6 +1776,241 @@ int hmsg_graph_set_room_names(hmsg_graph_t* g, int32_t n, const char* const* nam
             hmsg_index_destroy(g->ix);
             g->ix = nullptr;
         }
+    });
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------- the view level of the slow path
+// Graph.query_room_obj_slow_reasoning (graph.py:2578-3054) between its VLM calls; the device side is hmsg_query_views.hip.
+namespace {
+void views_ready(const hmsg_graph* g, const char* who) {
+    HMSG_REQUIRE(g->finished && !g->failed, HMSG_ERR_INVALID, std::string(who) + ": a graph built by hmsg_graph_finish or loaded by hmsg_load");
+}
+int view_room(const hmsg_graph* g, const GView& v) {
+    if (v.floor < 0 || v.floor >= (int)g->floors.size()) return -1;
+    const auto& rooms = g->floors[(size_t)v.floor].rooms;
+    return v.room_in_floor >= 0 && v.room_in_floor < (int)rooms.size() ? rooms[(size_t)v.room_in_floor] : -1;
+}
+hipStream_t view_stream(hmsg_graph* g) {
+    HIP_TRY(hipSetDevice(g->device));
+    if (!g->view_stream) HIP_TRY(hipStreamCreateWithFlags(&g->view_stream, hipStreamNonBlocking));
+    return g->view_stream;
+}
+hmsg_goal_table* goal_table(hmsg_graph* g) {
+    if (g->goal) return g->goal;
+    const int R = (int)g->rooms.size();
+    int D = g->D;
+    std::vector<int> img_off(1, 0), fro(1, 0), fr;
+    std::vector<float> clip;
+    std::vector<long long> img_id;
+    g->goal_bad.assign((size_t)R, "");
+    for (int r = 0; r < R; ++r) {
+        const GRoom& rm = g->rooms[(size_t)r];
+        if (rm.n_clip > 0 && D <= 0) D = (int)(rm.clip.size() / (size_t)rm.n_clip);
+        if ((size_t)rm.n_clip != rm.sample.size())
+            g->goal_bad[(size_t)r] = "room " + rm.id + ": Number of images (" + std::to_string(rm.sample.size()) + ") != embeddings (" + std::to_string(rm.n_clip) + ")";
+        else if (rm.n_clip > 0 && rm.clip.size() != (size_t)rm.n_clip * (size_t)D)
+            g->goal_bad[(size_t)r] = "room " + rm.id + ": clip_embeddings of another length than the graph's embeddings";
+        if (g->goal_bad[(size_t)r].empty()) {
+            clip.insert(clip.end(), rm.clip.begin(), rm.clip.end());
+            img_id.insert(img_id.end(), rm.sample.begin(), rm.sample.end());
+        }
+        img_off.push_back((int)img_id.size());
+    }
+    for (auto& fl : g->floors) {
+        for (int r : fl.rooms) fr.push_back(r);
+        fro.push_back((int)fr.size());
+    }
+    g->goal = hmsg_goal_table_create(g->device, std::max(D, 1), R, img_off, clip, img_id, fro, fr);
+    return g->goal;
+}
+// the clouds of objects obj[0 .. n) as segments of one device buffer: the instance clouds in the scene's HBM for a built graph (the
+// concatenated parts after merge_objects_graph), GObject::pts uploaded once for a loaded one.  obj -1: an empty cloud.
+const double* object_clouds(hmsg_graph* g, hipStream_t s, int n, const int* obj, std::vector<long long>& seg_off, std::vector<CloudSeg>& segs) {
+    seg_off.assign(1, 0);
+    segs.clear();
+    const double* base = nullptr;
+    if (g->loaded) {
+        if (!g->have_obj_pts) {
+            g->obj_pts_off.assign(1, 0);
+            for (auto& o : g->objects) g->obj_pts_off.push_back(g->obj_pts_off.back() + (long long)(o.pts.size() / 3));
+            HIP_TRY(hipSetDevice(g->device));
+            g->obj_pts.alloc((size_t)std::max<long long>(g->obj_pts_off.back(), 1) * 3);
+            for (size_t k = 0; k < g->objects.size(); ++k)
+                if (!g->objects[k].pts.empty()) h2d_bounce(g->obj_pts.p + (size_t)g->obj_pts_off[k] * 3, g->objects[k].pts.data(), g->objects[k].pts.size() / 3 * 24, s);
+            HIP_TRY(hipStreamSynchronize(s));
+            g->have_obj_pts = true;
+        }
+        base = g->obj_pts.p;
+    } else {
+        HMSG_REQUIRE(g->h != nullptr, HMSG_ERR_INVALID, "the graph has no scene handle");
+        base = g->h->inst.pts.p;
+    }
+    for (int i = 0; i < n; ++i) {
+        if (obj[i] >= 0) {
+            const GObject& o = g->objects[(size_t)obj[i]];
+            if (g->loaded) {
+                segs.push_back(CloudSeg{g->obj_pts_off[(size_t)obj[i]], g->obj_pts_off[(size_t)obj[i] + 1] - g->obj_pts_off[(size_t)obj[i]]});
+            } else {
+                const std::vector<int> one(1, o.instance);
+                for (int part : (g->merged ? o.parts : one)) {
+                    HMSG_REQUIRE(part >= 0 && (size_t)part + 1 < g->h->inst.off.size(), HMSG_ERR_INVALID, "an object without an instance cloud");
+                    segs.push_back(CloudSeg{g->h->inst.off[(size_t)part], g->h->inst.off[(size_t)part + 1] - g->h->inst.off[(size_t)part]});
+                }
+            }
+        }
+        seg_off.push_back((long long)segs.size());
+    }
+    return base;
+}
+}  // namespace
+
+extern "C" {
+
+int hmsg_graph_get_views(hmsg_graph_t* g, hmsg_graph_view* out, int64_t capacity) {
+    if (!g) return HMSG_ERR_INVALID;
+    return gguard(g, [&] {
+        views_ready(g, "hmsg_graph_get_views");
+        HMSG_REQUIRE(capacity >= (int64_t)g->views.size() && (out || g->views.empty()), HMSG_ERR_INVALID, "hmsg_graph_get_views: capacity too small");
+        const auto& lists = g->view_lists;
+        for (size_t v = 0; v < g->views.size(); ++v) {
+            const GView& w = g->views[v];
+            hmsg_graph_view& r = out[v];
+            memset(&r, 0, sizeof r);
+            r.view = (int32_t)v;
+            r.room = view_room(g, w);
+            r.img_id = w.have_img ? (int64_t)w.img : -1;
+            r.n_objects = (int32_t)lists[v].size();
+        }
+    });
+}
+
+int hmsg_graph_get_view_objects(hmsg_graph_t* g, int32_t view, int32_t* obj, int64_t capacity) {
+    if (!g) return HMSG_ERR_INVALID;
+    return gguard(g, [&] {
+        views_ready(g, "hmsg_graph_get_view_objects");
+        HMSG_REQUIRE(view >= 0 && view < (int32_t)g->views.size(), HMSG_ERR_INVALID, "hmsg_graph_get_view_objects: view index out of range");
+        const auto& l = g->view_lists[(size_t)view];
+        HMSG_REQUIRE(l.empty() || (obj && capacity >= (int64_t)l.size()), HMSG_ERR_INVALID, "hmsg_graph_get_view_objects: capacity too small");
+        if (!l.empty()) memcpy(obj, l.data(), l.size() * 4);
+    });
+}
+
+/* find_view_by_imgpath (graph.py:2566-2570): the first view, in view order, with that path (img_path non-NULL) or that image id */
+int hmsg_graph_find_view(hmsg_graph_t* g, const char* img_path, int64_t img_id, int32_t* view) {
+    if (!g || !view) return HMSG_ERR_INVALID;
+    *view = -1;
+    return gguard(g, [&] {
+        views_ready(g, "hmsg_graph_find_view");
+        for (size_t v = 0; v < g->views.size(); ++v) {
+            const GView& w = g->views[v];
+            if (img_path ? (w.have_path && w.img_path == img_path) : (w.have_img && (int64_t)w.img == img_id)) {
+                *view = (int32_t)v;
+                break;
+            }
+        }
+    });
+}
+
+/* graph.py:2759-2765 and :2828-2831: best_object.best_view_id -> the view that carries it -> its img_id */
+int hmsg_graph_object_best_views(hmsg_graph_t* g, int32_t n, const int32_t* obj, int32_t* view, int64_t* img_id) {
+    if (!g) return HMSG_ERR_INVALID;
+    return gguard(g, [&] {
+        views_ready(g, "hmsg_graph_object_best_views");
+        HMSG_REQUIRE(n >= 0 && (n == 0 || (obj && view)), HMSG_ERR_INVALID, "hmsg_graph_object_best_views: bad argument");
+        for (int i = 0; i < n; ++i) HMSG_REQUIRE(obj[i] >= 0 && obj[i] < (int32_t)g->objects.size(), HMSG_ERR_INVALID, "hmsg_graph_object_best_views: object index out of range");
+        for (int i = 0; i < n; ++i) {
+            const int bv = g->objects[(size_t)obj[i]].best_view;
+            view[i] = bv;
+            if (img_id) img_id[i] = bv >= 0 && g->views[(size_t)bv].have_img ? (int64_t)g->views[(size_t)bv].img : -1;
+        }
+    });
+}
+
+/* graph.py:2864-2897 for Q queries at once */
+int hmsg_graph_goal_views(hmsg_graph_t* g, int32_t Q, const float* T, const int32_t* floor_id, int32_t k, int64_t* out_img, int32_t* out_room,
+                          double* out_score, int32_t* out_n) {
+    if (!g) return HMSG_ERR_INVALID;
+    return gguard(g, [&] {
+        views_ready(g, "hmsg_graph_goal_views");
+        HMSG_REQUIRE(Q >= 0 && k >= 1 && (Q == 0 || (T && floor_id && out_img && out_room && out_score && out_n)), HMSG_ERR_INVALID,
+                     "hmsg_graph_goal_views: bad argument");
+        if (Q == 0) return;
+        hmsg_goal_table* t = goal_table(g);
+        std::vector<char> seen(g->floors.size() + 1, 0);
+        for (int q = 0; q < Q; ++q) {
+            const int f = floor_id[q];
+            HMSG_REQUIRE(f >= -1 && f < (int)g->floors.size(), HMSG_ERR_INVALID, "hmsg_graph_goal_views: floor id out of range");
+            if (seen[(size_t)(f + 1)]) continue;
+            seen[(size_t)(f + 1)] = 1;
+            if (f < 0) {
+                for (auto& why : g->goal_bad) HMSG_REQUIRE(why.empty(), HMSG_ERR_INVALID, "hmsg_graph_goal_views: " + why);
+            } else {
+                for (int r : g->floors[(size_t)f].rooms) HMSG_REQUIRE(g->goal_bad[(size_t)r].empty(), HMSG_ERR_INVALID, "hmsg_graph_goal_views: " + g->goal_bad[(size_t)r]);
+            }
+        }
+        hmsg_goal_table_topk(t, Q, T, floor_id, k, (long long*)out_img, out_room, out_score, out_n);
+    });
+}
+
+/* graph.py:2962-2986 for Q (text row, view) pairs, then visualize_pcd_on_image's avg_distance (:2994-2996) of the chosen object */
+int hmsg_graph_rematch_in_views(hmsg_graph_t* g, int32_t Q, const float* T, const int32_t* view, const double* pose_inv, const int32_t* wh,
+                                const double* K, int32_t* out_obj, double* out_score, double* out_avg_distance) {
+    if (!g) return HMSG_ERR_INVALID;
+    return gguard(g, [&] {
+        views_ready(g, "hmsg_graph_rematch_in_views");
+        HMSG_REQUIRE(Q >= 0 && (Q == 0 || (T && view && out_obj && out_score)) && (!pose_inv || (wh && K && out_avg_distance)), HMSG_ERR_INVALID,
+                     "hmsg_graph_rematch_in_views: bad argument");
+        if (Q == 0) return;
+        for (int q = 0; q < Q; ++q)
+            HMSG_REQUIRE(view[q] >= 0 && view[q] < (int32_t)g->views.size(), HMSG_ERR_INVALID, "hmsg_graph_rematch_in_views: view index out of range");
+        int nfr = 0;
+        hmsg_index_t* ix = hmsg_graph_shard_index(g, &nfr);
+        if (!g->views_on_index) {
+            const auto& lists = g->view_lists;
+            std::vector<int64_t> off(1, 0);
+            std::vector<int32_t> flat;
+            for (auto& l : lists) {
+                flat.insert(flat.end(), l.begin(), l.end());
+                off.push_back((int64_t)flat.size());
+            }
+            const int rc = hmsg_index_set_views(ix, (int64_t)lists.size(), off.data(), flat.data());
+            if (rc != HMSG_OK) throw hmsg_error{rc, hmsg_index_last_error(ix)};
+            g->views_on_index = true;
+        }
+        std::vector<int32_t> h_obj((size_t)Q);
+        const int rc = hmsg_rematch_in_views(ix, Q, T, view, h_obj.data(), out_score);
+        if (rc != HMSG_OK) throw hmsg_error{rc, hmsg_index_last_error(ix)};
+        if (pose_inv) {
+            std::vector<long long> seg_off;
+            std::vector<CloudSeg> segs;
+            hipStream_t s = view_stream(g);
+            const double* base = object_clouds(g, s, Q, h_obj.data(), seg_off, segs);
+            hmsg_view_depths(s, base, Q, seg_off, segs, pose_inv, wh, K, g->prm.min_visible_ratio, g->prm.max_view_depth, out_avg_distance, nullptr,
+                             nullptr);
+        }
+        if (hmsg_is_device_ptr(out_obj)) HIP_TRY(hipMemcpy(out_obj, h_obj.data(), (size_t)Q * 4, hipMemcpyHostToDevice));
+        else memcpy(out_obj, h_obj.data(), (size_t)Q * 4);
+    });
+}
+
+/* graph.py:3011-3022: check_object_in_view(..., return_depth=True) of (object, camera) pairs */
+int hmsg_graph_object_view_depths(hmsg_graph_t* g, int32_t n, const int32_t* obj, const double* view_pose_inv, const int32_t* wh, const double* K,
+                                  uint8_t* visible, double* mean_depth) {
+    if (!g) return HMSG_ERR_INVALID;
+    return gguard(g, [&] {
+        views_ready(g, "hmsg_graph_object_view_depths");
+        HMSG_REQUIRE(n >= 0 && (n == 0 || (obj && view_pose_inv && wh && K && visible && mean_depth)), HMSG_ERR_INVALID,
+                     "hmsg_graph_object_view_depths: bad argument");
+        if (n == 0) return;
+        for (int i = 0; i < n; ++i)
+            HMSG_REQUIRE(obj[i] >= 0 && obj[i] < (int32_t)g->objects.size(), HMSG_ERR_INVALID, "hmsg_graph_object_view_depths: object index out of range");
+        hipStream_t s = view_stream(g);
+        std::vector<long long> seg_off;
+        std::vector<CloudSeg> segs;
+        const double* base = object_clouds(g, s, n, obj, seg_off, segs);
+        hmsg_view_depths(s, base, n, seg_off, segs, view_pose_inv, wh, K, g->prm.min_visible_ratio, g->prm.max_view_depth, nullptr, visible, mean_depth);
     });
 }
 

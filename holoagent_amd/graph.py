@@ -1497,6 +1497,81 @@ class Graph:
         top_idx = np.argsort(sims)[-k:][::-1]
         return img_ids[int(np.argmax(sims))], [img_ids[int(i)] for i in top_idx], sims
 
+    def find_view_by_imgpath(self, img_path):
+        """graph.py:2566-2570."""
+        for view in self.views:
+            if view.img_path == img_path:
+                return view, view.img_id
+        return None, None
+
+    def find_object_by_object_id(self, object_id):
+        """graph.py:2572-2576."""
+        for obj in self.objects:
+            if obj.object_id == object_id:
+                return obj
+        return None
+
+    def goal_views_batch(self, queries, floor_ids, top_k=24):
+        """rank_goal_views (graph.py:2864-2897) for many object queries: per query (best image id, top image ids, their
+        similarities) over the rooms of its list -- self.rooms for floor -1, floors[f].rooms otherwise.  The table of sampled-image
+        embeddings is made resident once (float64) and all text rows are scored by one float64 MFMA GEMM; the order is descending
+        score with exact ties by candidate position (include/hmsg.h: hmsg_graph_goal_views states the rule)."""
+        sig = tuple((id(r.clip_embeddings), len(r.sample_images)) for r in self.rooms)
+        if getattr(self, "_goal_sig", None) != sig:
+            if getattr(self, "_goal_index", None) is not None:
+                self._goal_index.close()
+            rows, self._goal_rows = [], []
+            for ri, room in enumerate(self.rooms):
+                assert len(room.sample_images) == len(room.clip_embeddings), \
+                    f"Number of images ({len(room.sample_images)}) != embeddings ({len(room.clip_embeddings)})"
+                self._goal_rows += [(ri, int(i)) for i in room.sample_images]
+                rows += [np.asarray(e, np.float64).reshape(-1) for e in room.clip_embeddings]
+            self._goal_index = NodeIndex(np.stack(rows), np.zeros(len(rows), np.int32), lib_=self.L) if rows else None
+            self._goal_sig = sig
+        if self._goal_index is None:
+            return [(None, [], np.zeros(0)) for _ in queries]
+        sims = self._goal_index.similarity(self.get_text_feats_multiple_templates(list(queries)))
+        gl = {r.room_id: i for i, r in enumerate(self.rooms)}
+        room_of_row = np.array([r for r, _ in self._goal_rows])
+        out = []
+        for q, f in enumerate(floor_ids):
+            order = list(range(len(self.rooms))) if f == -1 else [gl[r.room_id] for r in self.floors[f].rooms]
+            cand = np.concatenate([np.nonzero(room_of_row == r)[0] for r in order]) if order else np.zeros(0, np.int64)
+            sc = sims[q][cand]
+            top = cand[np.lexsort((np.arange(len(cand)), -sc))[: min(top_k, len(cand))]]
+            ids = [self._goal_rows[int(i)][1] for i in top]
+            out.append((ids[0] if ids else None, ids, sims[q][top]))
+        return out
+
+    def rematch_in_view(self, object_query, view_or_img_path, pose=None):
+        """The re-match of the slow path (graph.py:2962-2986) in the view the VLM chose: the object query against the embeddings of
+        view.object_ids' objects, first maximum -- on the device (hmsg_rematch_in_views).  -> (object or None for a view without
+        objects, similarity, avg_distance); avg_distance is visualize_pcd_on_image's (utils/graph_utils.py:49-70) with `pose` the
+        camera -> world pose of the view's image, None without a pose or without a point in front of the camera."""
+        from ._lib import points_view_depths
+        view = view_or_img_path
+        if isinstance(view, str):
+            view, _ = self.find_view_by_imgpath(view)
+            assert view is not None
+        ix = self._node_index()
+        sig = tuple((id(v), tuple(v.object_ids)) for v in self.views)
+        if getattr(ix, "_views_sig", None) != sig:
+            pos = {}
+            for k, o in enumerate(self.objects):
+                pos.setdefault(o.object_id, k)
+            ix.set_views([[pos[i] for i in v.object_ids if i in pos] for v in self.views])
+            ix._views_sig = sig
+        vi = next(k for k, v in enumerate(self.views) if v is view)
+        node, score = ix.rematch_in_views(self.get_text_feats_multiple_templates([object_query]), [vi])
+        if node[0] < 0:
+            return None, 0.0, None
+        obj, dist = self.objects[int(node[0])], None
+        if pose is not None:
+            avg, _, _ = points_view_depths([np.asarray(obj.pcd.points, np.float64)], [np.linalg.inv(np.asarray(pose, np.float64))], [0, 0], np.eye(3),
+                                           lib_=self.L)
+            dist = None if np.isnan(avg[0]) else float(avg[0])
+        return obj, float(score[0]), dist
+
     def _parse(self, query_instruction):
         if isinstance(query_instruction, str):
             return type(self).instruction_parser(query_instruction)

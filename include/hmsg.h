@@ -510,7 +510,7 @@ typedef struct hmsg_graph_object {
     char name[80];
     int32_t room;               /* global room index (hmsg_graph_get_rooms order) */
     int32_t instance, label;    /* hmsg_node.instance / .label; -1 for a loaded graph */
-    int32_t n_views, best_view; /* best_view: global view index, -1 none (loaded graphs: -1, the id is in hmsg_graph_to_json) */
+    int32_t n_views, best_view; /* best_view: global view index, -1 none (loaded graphs: best_view_id resolved by hmsg_load) */
 } hmsg_graph_object;
 typedef struct hmsg_graph_room {
     char room_id[32];
@@ -708,6 +708,77 @@ int hmsg_graphs_query(int32_t n, hmsg_graph_t* const* graphs, const double* cons
                       const int32_t* qid, const float* T_room, const int32_t* floor_id, const int32_t* room_mode, int32_t k, int32_t use_negatives,
                       int32_t max_rooms, int32_t* out_sel, int32_t* out_nsel, int32_t* out_idx, int32_t* out_room, double* out_score,
                       int64_t* node_off, int64_t* room_off, int64_t* floor_off);
+
+/* ---- the view level of the slow path: what Graph.query_room_obj_slow_reasoning (graph.py:2578-3054) computes between its VLM calls,
+ * on the graph object (holoagent_amd/csrc/hmsg_query_views.hip).  The caller keeps detect_object_in_image, vlm_choose,
+ * detect_and_select_best_gpt and the drawing; INTEGRATION.md maps the steps.
+ *   hmsg_graph_get_views   per view, in self.views order: its index, img_id (-1: none), room (hmsg_graph_get_rooms order, -1: none) and
+ *        the length of its object list.
+ *   hmsg_graph_get_view_objects   that list: find_object_by_object_id (graph.py:2572-2576: the first object that carries the id) of
+ *        every entry of view.object_ids, in that order (:2968-2973), as indices of hmsg_graph_get_objects; an id that no object carries
+ *        -- the reference asserts there -- is left out.
+ *   hmsg_graph_find_view   find_view_by_imgpath (graph.py:2566-2570): the first view in view order whose img_path equals img_path, or,
+ *        with img_path NULL, whose img_id equals img_id; *view = -1 when there is none.
+ *   hmsg_graph_object_best_views   graph.py:2759-2765 + :2828-2831: view[i] = the view that carries obj[i]'s best_view_id (-1: none --
+ *        the reference's best_view = None), img_id[i] (optional) its image.  hmsg_graph_object::best_view holds the same index on built
+ *        and, since hmsg_load resolves best_view_id / view_ids, on loaded graphs; an id that names no view stays -1.
+ *   hmsg_graph_goal_views   graph.py:2864-2897 for Q object texts T f32 [Q][D] (host or device) at once: the text against the CLIP
+ *        embedding of every sampled image (room.sample_images / room.clip_embeddings) of every room of the query's list -- all rooms
+ *        for floor_id[q] = -1, floors[f].rooms in that order otherwise.  The table is float64 in HBM, made on the first call and freed
+ *        with the graph; scores come from the float64 MFMA GEMM of hmsg_similarity.  out_img i64 / out_room i32 (global room index) /
+ *        out_score f64 [Q][k], out_n [Q] (host or device): the k best rows (k = 24 in the reference, any k >= 1), -1 / -1 / 0.0 past
+ *        out_n[q] = min(k, rows of the list); no sampled image at all gives out_n = 0.
+ *        ORDER: descending score; exact ties (bit-equal scores) by ascending candidate position = place of the room in the list, then
+ *        place of the image in the room.  Row 0 is therefore np.argmax(sims) (first maximum), and the rest is
+ *        np.argsort(sims)[-k:][::-1] wherever scores differ; numpy's order of bit-equal keys is undefined, so there only the set of
+ *        tied rows compares (the rule of hmsg_query_objects).
+ *        A room of the list whose sample_images and clip_embeddings differ in length: HMSG_ERR_INVALID naming the room (the
+ *        reference asserts, :2870).
+ *   hmsg_graph_rematch_in_views   graph.py:2962-2986 for Q (text row, view index) pairs: the text against the embeddings of the
+ *        view's object list in that order, the FIRST maximum (np.argmax).  out_obj [Q] (index of hmsg_graph_get_objects, -1 for a view
+ *        without objects: the reference skips it, :2974), out_score f64 [Q] -- bit for bit hmsg_similarity's entry for that (text row,
+ *        object) on the graph's index, 0.0 with -1.  With pose_inv f64 [Q][16] (world -> camera of the view's image: np.linalg.inv(pose)
+ *        as the reference makes it), wh i32 [Q][2] (image width, height) and K f64 [9]: out_avg_distance f64 [Q] =
+ *        visualize_pcd_on_image's avg_distance of the chosen object (utils/graph_utils.py:49-70: the mean camera z of its points with
+ *        z > 0; NaN where the reference returns None -- no such point, an empty cloud, out_obj -1).  pose_inv NULL: no distances.
+ *        The cloud is the object's as the graph holds it: the instance cloud in HBM on a built graph (the concatenated parts after
+ *        merge_objects_graph), the saved cloud on a loaded one (uploaded once, cached, freed with the graph).
+ *   hmsg_graph_object_view_depths   graph.py:3011-3022: check_object_in_view(w, h, K, pose_inv, points, return_depth=True)
+ *        (utils/graph_utils.py:95-157) of n (object, camera) pairs with the graph's min_visible_ratio / max_view_depth: visible u8 [n],
+ *        mean_depth f64 [n] exactly as hmsg_object_views defines them (inf where the reference returns inf).
+ * Host arrays: floor_id (hmsg_graph_goal_views), view (hmsg_graph_rematch_in_views), obj, pose_inv, wh and K are read on the host and
+ * must be host memory; only T and the outputs named "host or device" may be device pointers (the table-level hmsg_rematch_in_views also
+ * takes a device `view`).  Lifetime: on a BUILT graph hmsg_graph_rematch_in_views with pose_inv and hmsg_graph_object_view_depths read the
+ * object clouds in the scene handle's HBM, so the handle must be alive and not reset (as for hmsg_save); a LOADED graph needs none.
+ * Errors: an unfinished or failed graph (every call of this group, the listing calls included), a view / object / floor index out of
+ * range: HMSG_ERR_INVALID, text in hmsg_graph_last_error.
+ * Table level, for hosts that keep their own tables (and for tests of the kernels' edges):
+ *   hmsg_index_set_views   CSR view -> nodes of an index (view_obj_off i64 [n_views + 1] from 0, view_objs i32, in object_ids order);
+ *   hmsg_rematch_in_views  the re-match on it: T host or device, view host or device, outputs host or device;
+ *   hmsg_points_view_depths   pair p = points pts_off[p] .. pts_off[p + 1] of pts f64 [.][3] (host or device) through pose_inv [p][16],
+ *        wh [p][2], K [9] (host): avg_z_front, visible, mean_depth [n_pairs] (host, each optional).  Sums are float64 in a fixed order
+ *        (two stages, no floating-point atomics): the same input gives the same bits on every run. */
+typedef struct hmsg_graph_view {
+    int32_t view;               /* global view index (self.views order) */
+    int32_t room;               /* global room index, -1 none */
+    int64_t img_id;             /* View.img_id, -1 none */
+    int32_t n_objects;          /* length of hmsg_graph_get_view_objects' list */
+    int32_t reserved_;
+} hmsg_graph_view;
+int hmsg_graph_get_views(hmsg_graph_t* g, hmsg_graph_view* out, int64_t capacity);
+int hmsg_graph_get_view_objects(hmsg_graph_t* g, int32_t view, int32_t* obj, int64_t capacity);
+int hmsg_graph_find_view(hmsg_graph_t* g, const char* img_path, int64_t img_id, int32_t* view);
+int hmsg_graph_object_best_views(hmsg_graph_t* g, int32_t n, const int32_t* obj, int32_t* view, int64_t* img_id);
+int hmsg_graph_goal_views(hmsg_graph_t* g, int32_t Q, const float* T, const int32_t* floor_id, int32_t k, int64_t* out_img, int32_t* out_room,
+                          double* out_score, int32_t* out_n);
+int hmsg_graph_rematch_in_views(hmsg_graph_t* g, int32_t Q, const float* T, const int32_t* view, const double* pose_inv, const int32_t* wh,
+                                const double* K, int32_t* out_obj, double* out_score, double* out_avg_distance);
+int hmsg_graph_object_view_depths(hmsg_graph_t* g, int32_t n, const int32_t* obj, const double* view_pose_inv, const int32_t* wh, const double* K,
+                                  uint8_t* visible, double* mean_depth);
+int hmsg_index_set_views(hmsg_index_t* ix, int64_t n_views, const int64_t* view_obj_off, const int32_t* view_objs);
+int hmsg_rematch_in_views(hmsg_index_t* ix, int32_t Q, const float* T, const int32_t* view, int32_t* out_node, double* out_score);
+int hmsg_points_view_depths(int32_t device_id, int64_t n_pairs, const int64_t* pts_off, const double* pts, const double* pose_inv, const int32_t* wh,
+                            const double* K, double min_visible_ratio, double max_depth, double* avg_z_front, uint8_t* visible, double* mean_depth);
 
 
 #ifdef __cplusplus
