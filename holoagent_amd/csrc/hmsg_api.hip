@@ -1,10 +1,11 @@
 // C ABI of libhmsg (see include/hmsg.h).  Thin: argument checks, host<->HBM staging, error capture.
-#include "hmsg_common.h"
+#include "hmsg_boundary.h"
 #include "hmsg_ckdtree.h"
 #include "hmsg_nn.h"
 
 #include <algorithm>
 #include <cstring>
+#include <stdexcept>
 
 void hmsg_bitset_and_fp(hmsg_ctx* h, int first, int n, int M, const unsigned char* d_masks, const float* d_fg,
                         const float* d_fm, const float* d_fc, const int* d_nmask);   // hmsg_fuse.hip
@@ -68,24 +69,6 @@ namespace {
 void copy_in(void* dst, const void* src, size_t bytes, hipStream_t s) {
     if (!bytes) return;
     HIP_TRY(hipMemcpyAsync(dst, src, bytes, hmsg_is_device_ptr(src) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-}
-
-template <typename F>
-int guard(hmsg_ctx* h, F&& fn) {
-    try {
-        if (h) HIP_TRY(hipSetDevice(h->cfg.device_id));
-        fn();
-        return HMSG_OK;
-    } catch (const hmsg_error& e) {
-        if (h) h->err = e.msg;
-        return e.code;
-    } catch (const std::exception& e) {
-        if (h) h->err = e.what();
-        return HMSG_ERR_INVALID;
-    } catch (...) {      // nothing may cross the C boundary
-        if (h) h->err = "unknown error";
-        return HMSG_ERR_INVALID;
-    }
 }
 
 // A long episode's frame store (colour, depth, mask bitsets, nearest-voxel indices: 17 B per pixel and frame, 157 GB for
@@ -176,11 +159,12 @@ int hmsg_create(const hmsg_config* cfg, hmsg_t** out) {
     if (cfg->feat_dim <= 0 || cfg->height <= 0 || cfg->width <= 0 || cfg->max_frames <= 0 || cfg->voxel_size <= 0 ||
         cfg->max_masks <= 0 || cfg->max_masks > 256)
         return HMSG_ERR_INVALID;
-    hmsg_ctx* h = new hmsg_ctx();
-    h->cfg = *cfg;
-    h->NW = (cfg->max_masks + 63) / 64;
-    h->MS = h->NW * 64;
-    int rc = guard(h, [&] {
+    hmsg_ctx* h = nullptr;
+    const int rc = hmsg_boundary("hmsg_create", cfg->device_id, [&] {
+        h = new hmsg_ctx();
+        h->cfg = *cfg;
+        h->NW = (cfg->max_masks + 63) / 64;
+        h->MS = h->NW * 64;
         int ndev = 0;
         HIP_TRY(hipGetDeviceCount(&ndev));
         HMSG_REQUIRE(cfg->device_id >= 0 && cfg->device_id < ndev, HMSG_ERR_INVALID, "device_id out of range");
@@ -190,7 +174,6 @@ int hmsg_create(const hmsg_config* cfg, hmsg_t** out) {
         h->pose.alloc((size_t)16 * cfg->max_frames);
     });
     if (rc != HMSG_OK) {
-        fprintf(stderr, "hmsg_create: %s\n", h->err.c_str());
         delete h;
         return rc;
     }
@@ -220,7 +203,7 @@ void hmsg_release_cached_memory(void) { dev_cache().trim(); }
 
 int hmsg_reset(hmsg_t* h) {
     if (!h) return HMSG_ERR_INVALID;
-    return guard(h, [&] {
+    return hmsg_boundary(h, [&] {
         HIP_TRY(hipStreamSynchronize(h->stream));
         hmsg_kd_join(h);
         hmsg_fold_pipe_abort(h);
@@ -278,25 +261,30 @@ static void prof_aggregate(hmsg_ctx* h, std::vector<std::string>& names, std::ve
 
 int32_t hmsg_profile_count(hmsg_t* h) {
     if (!h) return 0;
-    std::vector<std::string> n;
-    std::vector<long long> c;
-    std::vector<double> m;
-    prof_aggregate(h, n, c, m);
-    return (int32_t)n.size();
+    int32_t count = 0;
+    hmsg_boundary(&h->err, -1, [&] {
+        std::vector<std::string> n;
+        std::vector<long long> c;
+        std::vector<double> m;
+        prof_aggregate(h, n, c, m);
+        count = (int32_t)n.size();
+    });
+    return count;
 }
 
 int hmsg_profile_entry(hmsg_t* h, int32_t i, char* name, int64_t* launches, double* total_ms, double* total_work) {
     if (!h || !name || !launches || !total_ms) return HMSG_ERR_INVALID;
-    std::vector<std::string> n;
-    std::vector<long long> c;
-    std::vector<double> m, w;
-    prof_aggregate(h, n, c, m, &w);
-    if (i < 0 || i >= (int32_t)n.size()) return HMSG_ERR_INVALID;
-    snprintf(name, 64, "%s", n[i].c_str());
-    *launches = c[i];
-    *total_ms = m[i];
-    if (total_work) *total_work = w[i];
-    return HMSG_OK;
+    return hmsg_boundary(&h->err, -1, [&] {
+        std::vector<std::string> n;
+        std::vector<long long> c;
+        std::vector<double> m, w;
+        prof_aggregate(h, n, c, m, &w);
+        HMSG_REQUIRE(i >= 0 && i < (int32_t)n.size(), HMSG_ERR_INVALID, "hmsg_profile_entry: index out of range");
+        snprintf(name, 64, "%s", n[i].c_str());
+        *launches = c[i];
+        *total_ms = m[i];
+        if (total_work) *total_work = w[i];
+    });
 }
 
 __global__ void k_depth_cut(unsigned short* __restrict__ depth, size_t n, double limit) {
@@ -306,7 +294,7 @@ __global__ void k_depth_cut(unsigned short* __restrict__ depth, size_t n, double
 
 int hmsg_add_frames(hmsg_t* h, int32_t n, const uint8_t* rgb, const uint16_t* depth, const double* pose, const double* K) {
     if (!h) return HMSG_ERR_INVALID;
-    return guard(h, [&] {
+    return hmsg_boundary(h, [&] {
         HMSG_REQUIRE(n >= 0 && rgb && depth && pose && K, HMSG_ERR_INVALID, "hmsg_add_frames: null argument");
         HMSG_REQUIRE(!h->map_ready, HMSG_ERR_INVALID, "hmsg_add_frames after hmsg_finalize_map");
         HMSG_REQUIRE(!h->frames_released, HMSG_ERR_INVALID, "hmsg_add_frames: the frame store was released (hmsg_reset first)");
@@ -358,7 +346,7 @@ int hmsg_add_frames(hmsg_t* h, int32_t n, const uint8_t* rgb, const uint16_t* de
 
 int hmsg_finalize_map(hmsg_t* h) {
     if (!h) return HMSG_ERR_INVALID;
-    return guard(h, [&] {
+    return hmsg_boundary(h, [&] {
         HMSG_REQUIRE(!h->map_ready, HMSG_ERR_INVALID, "map already finalised");
         hmsg_build_map(h);
     });
@@ -371,7 +359,7 @@ int64_t hmsg_map_size_unfiltered(const hmsg_t* h) { return h && h->map_ready ? h
 int hmsg_get_map_points(const hmsg_t* hc, double* xyz, double* rgb) {
     hmsg_ctx* h = const_cast<hmsg_ctx*>(hc);
     if (!h) return HMSG_ERR_INVALID;
-    return guard(h, [&] {
+    return hmsg_boundary(h, [&] {
         HMSG_REQUIRE(h->map_ready, HMSG_ERR_INVALID, "map not finalised");
         if (xyz) d2h_bounce(xyz, h->pts.p, (size_t)h->V * 24);
         if (rgb) d2h_bounce(rgb, h->cols.p, (size_t)h->V * 24);
@@ -381,7 +369,7 @@ int hmsg_get_map_points(const hmsg_t* hc, double* xyz, double* rgb) {
 int hmsg_add_frame_features(hmsg_t* h, int32_t first, int32_t n, int32_t M, const uint8_t* masks, const float* F_g,
                             const float* F_masked, const float* F_crop, const int32_t* n_masks) {
     if (!h) return HMSG_ERR_INVALID;
-    return guard(h, [&] {
+    return hmsg_boundary(h, [&] {
         HMSG_REQUIRE(n >= 0 && F_g, HMSG_ERR_INVALID, "hmsg_add_frame_features: null argument");
         HMSG_REQUIRE(M >= 0 && M <= h->cfg.max_masks, HMSG_ERR_INVALID, "M out of range (cfg.max_masks, <= 256)");
         HMSG_REQUIRE(M == 0 || (masks && F_masked && F_crop), HMSG_ERR_INVALID, "hmsg_add_frame_features: null argument");
@@ -449,7 +437,7 @@ int hmsg_add_frame_features(hmsg_t* h, int32_t first, int32_t n, int32_t M, cons
 
 int hmsg_set_frame_window(hmsg_t* h, int32_t first_frame) {
     if (!h) return HMSG_ERR_INVALID;
-    return guard(h, [&] {
+    return hmsg_boundary(h, [&] {
         HMSG_REQUIRE(h->map_ready, HMSG_ERR_INVALID, "hmsg_set_frame_window: call hmsg_finalize_map first");
         HMSG_REQUIRE(h->n_feat_frames == 0 && h->n_fused == 0, HMSG_ERR_INVALID, "hmsg_set_frame_window: features already handed over");
         HMSG_REQUIRE(first_frame >= 0 && first_frame <= h->n_frames, HMSG_ERR_INVALID, "hmsg_set_frame_window: frame out of range");
@@ -464,7 +452,7 @@ int hmsg_set_frame_window(hmsg_t* h, int32_t first_frame) {
 
 int hmsg_merge_tree_local(hmsg_t* h, int32_t total_frames, double* th_next, int64_t* lists_now, int64_t* my_index) {
     if (!h || !th_next || !lists_now || !my_index) return HMSG_ERR_INVALID;
-    return guard(h, [&] {
+    return hmsg_boundary(h, [&] {
         long long l = 0, i = 0;
         hmsg_fold_pipe_abort(h);
         release_frame_store_if_large(h);
@@ -476,18 +464,18 @@ int hmsg_merge_tree_local(hmsg_t* h, int32_t total_frames, double* th_next, int6
 
 int hmsg_merge_tree_join(hmsg_t* h, int32_t n_ext, const int64_t* ext_sizes, const double* ext_points, double th, int32_t final_pass) {
     if (!h) return HMSG_ERR_INVALID;
-    return guard(h, [&] { hmsg_merge_tree_join_impl(h, n_ext, (const long long*)ext_sizes, ext_points, th, final_pass); });
+    return hmsg_boundary(h, [&] { hmsg_merge_tree_join_impl(h, n_ext, (const long long*)ext_sizes, ext_points, th, final_pass); });
 }
 
 int hmsg_fuse_frames(hmsg_t* h) {
     if (!h) return HMSG_ERR_INVALID;
-    return guard(h, [&] { hmsg_fuse(h); });
+    return hmsg_boundary(h, [&] { hmsg_fuse(h); });
 }
 
 int hmsg_get_map_feats(const hmsg_t* hc, float* feats, float* counter) {
     hmsg_ctx* h = const_cast<hmsg_ctx*>(hc);
     if (!h) return HMSG_ERR_INVALID;
-    return guard(h, [&] {
+    return hmsg_boundary(h, [&] {
         HMSG_REQUIRE(h->feats_final, HMSG_ERR_INVALID, "hmsg_fuse_frames not run");
         if (feats) d2h_bounce(feats, h->feats.p, (size_t)h->V * h->cfg.feat_dim * 4);
         if (counter) {
@@ -511,7 +499,7 @@ __global__ void k_feats_refresh(const float* __restrict__ sum, const unsigned* _
 int hmsg_get_feature_sums(const hmsg_t* hc, float* sum, uint32_t* counter) {
     hmsg_ctx* h = const_cast<hmsg_ctx*>(hc);
     if (!h) return HMSG_ERR_INVALID;
-    return guard(h, [&] {
+    return hmsg_boundary(h, [&] {
         HMSG_REQUIRE(h->feats_final, HMSG_ERR_INVALID, "hmsg_fuse_frames not run");
         const size_t n = (size_t)h->V * h->cfg.feat_dim;
         // (on the handle's own stream -- ordered behind whatever produced the sums -- and complete before the call returns:
@@ -525,7 +513,7 @@ int hmsg_get_feature_sums(const hmsg_t* hc, float* sum, uint32_t* counter) {
 
 int hmsg_set_feature_sums(hmsg_t* h, const float* sum, const uint32_t* counter) {
     if (!h) return HMSG_ERR_INVALID;
-    return guard(h, [&] {
+    return hmsg_boundary(h, [&] {
         HMSG_REQUIRE(h->feats_final && sum && counter, HMSG_ERR_INVALID, "hmsg_set_feature_sums: run hmsg_fuse_frames first");
         HMSG_REQUIRE(!h->pooled, HMSG_ERR_INVALID, "hmsg_set_feature_sums after hmsg_pool_instances");
         const size_t n = (size_t)h->V * h->cfg.feat_dim;
@@ -541,7 +529,7 @@ int hmsg_set_feature_sums(hmsg_t* h, const float* sum, const uint32_t* counter) 
 int hmsg_get_frame_nn(const hmsg_t* hc, int32_t frame, int32_t* idx) {
     hmsg_ctx* h = const_cast<hmsg_ctx*>(hc);
     if (!h) return HMSG_ERR_INVALID;
-    return guard(h, [&] {
+    return hmsg_boundary(h, [&] {
         HMSG_REQUIRE(frame >= 0 && frame < h->n_fused && idx, HMSG_ERR_INVALID, "frame not fused");
         HMSG_REQUIRE(!h->frames_released, HMSG_ERR_INVALID, "hmsg_get_frame_nn: the frame store was released by the merge (very long episode)");
         const size_t HW = (size_t)h->cfg.height * h->cfg.width;
@@ -552,7 +540,7 @@ int hmsg_get_frame_nn(const hmsg_t* hc, int32_t frame, int32_t* idx) {
 int hmsg_get_frame_fp(const hmsg_t* hc, int32_t frame, float* f_p) {
     hmsg_ctx* h = const_cast<hmsg_ctx*>(hc);
     if (!h) return HMSG_ERR_INVALID;
-    return guard(h, [&] {
+    return hmsg_boundary(h, [&] {
         HMSG_REQUIRE(frame >= 0 && frame < h->n_feat_frames && f_p, HMSG_ERR_INVALID, "frame has no features");
         const size_t D = (size_t)h->cfg.feat_dim, n = (size_t)h->nmask[frame] * D;
         if (n) HIP_TRY(hipMemcpy(f_p, h->fp.p + (size_t)frame * h->MS * D, n * 4, hipMemcpyDeviceToHost));
@@ -566,7 +554,7 @@ int32_t hmsg_get_frame_num_masks(const hmsg_t* h, int32_t frame) {
 int hmsg_get_frame_mask_sizes(const hmsg_t* hc, int32_t frame, int64_t* sizes) {
     hmsg_ctx* h = const_cast<hmsg_ctx*>(hc);
     if (!h) return HMSG_ERR_INVALID;
-    return guard(h, [&] {
+    return hmsg_boundary(h, [&] {
         HMSG_REQUIRE(frame >= 0 && frame < h->n_fused && sizes, HMSG_ERR_INVALID, "frame not fused");
         for (int i = 0; i < h->nmask[frame]; ++i) {
             size_t k = (size_t)h->mask_first[frame] + i;
@@ -578,7 +566,7 @@ int hmsg_get_frame_mask_sizes(const hmsg_t* hc, int32_t frame, int64_t* sizes) {
 int hmsg_get_frame_mask_points(const hmsg_t* hc, int32_t frame, double* xyz) {
     hmsg_ctx* h = const_cast<hmsg_ctx*>(hc);
     if (!h) return HMSG_ERR_INVALID;
-    return guard(h, [&] {
+    return hmsg_boundary(h, [&] {
         HMSG_REQUIRE(frame >= 0 && frame < h->n_fused && xyz, HMSG_ERR_INVALID, "frame not fused");
         long long a = h->masks3d.off[(size_t)h->mask_first[frame]], b = h->masks3d.off[(size_t)h->mask_first[frame + 1]];
         if (b > a) d2h_bounce(xyz, h->masks3d.pts.p + (size_t)a * 3, (size_t)(b - a) * 24);
@@ -587,7 +575,7 @@ int hmsg_get_frame_mask_points(const hmsg_t* hc, int32_t frame, double* xyz) {
 
 int hmsg_merge_instances(hmsg_t* h) {
     if (!h) return HMSG_ERR_INVALID;
-    return guard(h, [&] {
+    return hmsg_boundary(h, [&] {
         release_frame_store_if_large(h);
         hmsg_merge(h);
     });
@@ -598,7 +586,7 @@ int64_t hmsg_num_instances(const hmsg_t* h) { return h && (h->merged || h->tree_
 int hmsg_get_instance_sizes(const hmsg_t* hc, int64_t* sizes) {
     hmsg_ctx* h = const_cast<hmsg_ctx*>(hc);
     if (!h) return HMSG_ERR_INVALID;
-    return guard(h, [&] {
+    return hmsg_boundary(h, [&] {
         HMSG_REQUIRE((h->merged || h->tree_partial) && sizes, HMSG_ERR_INVALID, "hmsg_merge_instances not run");
         for (size_t i = 0; i + 1 < h->inst.off.size(); ++i) sizes[i] = h->inst.off[i + 1] - h->inst.off[i];
     });
@@ -607,7 +595,7 @@ int hmsg_get_instance_sizes(const hmsg_t* hc, int64_t* sizes) {
 int hmsg_get_instance_points(const hmsg_t* hc, double* xyz) {
     hmsg_ctx* h = const_cast<hmsg_ctx*>(hc);
     if (!h) return HMSG_ERR_INVALID;
-    return guard(h, [&] {
+    return hmsg_boundary(h, [&] {
         HMSG_REQUIRE((h->merged || h->tree_partial) && xyz, HMSG_ERR_INVALID, "hmsg_merge_instances not run");
         if (h->inst.total) {
             if (hmsg_is_device_ptr(xyz)) {
@@ -621,7 +609,7 @@ int hmsg_get_instance_points(const hmsg_t* hc, double* xyz) {
 
 int hmsg_denoise_instances(hmsg_t* h, double eps, int32_t min_points) {
     if (!h) return HMSG_ERR_INVALID;
-    return guard(h, [&] {
+    return hmsg_boundary(h, [&] {
         hmsg_denoise_inst(h, eps, min_points);
         if (eps == 0.05 && min_points == 10) h->inst_denoised = true;
     });
@@ -629,7 +617,7 @@ int hmsg_denoise_instances(hmsg_t* h, double eps, int32_t min_points) {
 
 int hmsg_voxel_down_sample(hmsg_t* h, const double* points, int64_t n, double voxel_size, double* out_points, int64_t* out_n) {
     if (!h) return HMSG_ERR_INVALID;
-    return guard(h, [&] {
+    return hmsg_boundary(h, [&] {
         HMSG_REQUIRE((points || n == 0) && out_points && out_n, HMSG_ERR_INVALID, "hmsg_voxel_down_sample: null argument");
         *out_n = (int64_t)hmsg_voxel_ds(h, points, (long long)n, voxel_size, out_points);
     });
@@ -638,7 +626,7 @@ int hmsg_voxel_down_sample(hmsg_t* h, const double* points, int64_t n, double vo
 int hmsg_instance_room_share(hmsg_t* h, int32_t n_rooms, const int64_t* vert_off, const double* verts_xz, double radius,
                              double* share) {
     if (!h) return HMSG_ERR_INVALID;
-    return guard(h, [&] {
+    return hmsg_boundary(h, [&] {
         HMSG_REQUIRE(n_rooms >= 0 && vert_off && verts_xz && share && radius > 0, HMSG_ERR_INVALID,
                      "hmsg_instance_room_share: bad argument");
         hmsg_room_share(h, n_rooms, (const long long*)vert_off, verts_xz, radius, share);
@@ -648,7 +636,7 @@ int hmsg_instance_room_share(hmsg_t* h, int32_t n_rooms, const int64_t* vert_off
 int hmsg_get_instance_boxes(const hmsg_t* hc, double* boxes) {
     hmsg_ctx* h = const_cast<hmsg_ctx*>(hc);
     if (!h) return HMSG_ERR_INVALID;
-    return guard(h, [&] {
+    return hmsg_boundary(h, [&] {
         HMSG_REQUIRE(h->merged && boxes, HMSG_ERR_INVALID, "hmsg_merge_instances not run");
         if (!h->inst.box.empty()) memcpy(boxes, h->inst.box.data(), h->inst.box.size() * 8);
     });
@@ -656,13 +644,13 @@ int hmsg_get_instance_boxes(const hmsg_t* hc, double* boxes) {
 
 int hmsg_pool_instances(hmsg_t* h) {
     if (!h) return HMSG_ERR_INVALID;
-    return guard(h, [&] { hmsg_pool(h); });
+    return hmsg_boundary(h, [&] { hmsg_pool(h); });
 }
 
 int hmsg_get_instance_feats(const hmsg_t* hc, float* feats) {
     hmsg_ctx* h = const_cast<hmsg_ctx*>(hc);
     if (!h) return HMSG_ERR_INVALID;
-    return guard(h, [&] {
+    return hmsg_boundary(h, [&] {
         HMSG_REQUIRE(h->pooled && feats, HMSG_ERR_INVALID, "hmsg_pool_instances not run");
         size_t n = (h->inst.off.size() - 1) * (size_t)h->cfg.feat_dim;
         if (n) d2h_bounce(feats, h->inst_feats.p, n * 4);
@@ -674,12 +662,26 @@ int hmsg_get_instance_feats(const hmsg_t* hc, float* feats) {
 int hmsg_test_ckdtree(const double* pts, int64_t n, const double* queries, int64_t nq, int64_t* out_idx,
                       int64_t* out_indices, int64_t* out_n_nodes) {
     if (!pts || n < 0 || nq < 0) return HMSG_ERR_INVALID;
-    CKDTree t;
-    t.build(pts, n);
-    if (out_indices) memcpy(out_indices, t.indices.data(), (size_t)n * 8);
-    if (out_n_nodes) *out_n_nodes = (int64_t)t.nodes.size();
-    for (int64_t i = 0; i < nq; ++i) out_idx[i] = t.query1(queries + i * 3);
-    return HMSG_OK;
+    return hmsg_boundary("hmsg_test_ckdtree", -1, [&] {
+        CKDTree t;
+        t.build(pts, n);
+        if (out_indices) memcpy(out_indices, t.indices.data(), (size_t)n * 8);
+        if (out_n_nodes) *out_n_nodes = (int64_t)t.nodes.size();
+        for (int64_t i = 0; i < nq; ++i) out_idx[i] = t.query1(queries + i * 3);
+    });
+}
+
+// test hook: what hmsg_boundary makes of each kind of exception (tests/test_boundary.py); no GPU involved
+int hmsg_test_boundary(int32_t kind, char* msg, int64_t cap) {
+    std::string sink;
+    const int rc = hmsg_boundary(&sink, -1, [&] {
+        if (kind == 1) throw hmsg_error{HMSG_ERR_UNSUPPORTED, "x"};
+        if (kind == 2) throw std::bad_alloc();
+        if (kind == 3) throw std::length_error("y");
+        if (kind == 4) throw 4;
+    });
+    if (msg && cap > 0) snprintf(msg, (size_t)cap, "%s", sink.c_str());
+    return rc;
 }
 
 }  // extern "C"

@@ -18,6 +18,7 @@
 // -> largest cluster per segment -> keep flags -> scan -> compaction + boxes of the kept points.  The
 // neighbourhood kernels are serial chains of L2 round trips per lane: they work on a cell-SORTED COPY of the
 // points (one load per candidate), visit the nearest cells first and keep several loads in flight.
+#include "hmsg_boundary.h"
 #include "hmsg_cloudops.h"
 
 #include <algorithm>
@@ -1919,10 +1920,8 @@ long long CloudOps::voxel_down_sample(const double* src, const std::vector<SegDe
 extern "C" int hmsg_test_dbscan(const double* pts, int32_t K, const int64_t* sizes, double eps, int32_t min_points,
                                 const uint8_t* core0, double* out_pts, int64_t* out_sizes, uint8_t* out_core, int32_t* out_info) {
     if (K < 0 || (K > 0 && (!sizes || !out_sizes)) || eps <= 0 || min_points <= 0) return HMSG_ERR_INVALID;
-    hipStream_t s = nullptr;
-    int rc = HMSG_OK;
-    try {
-        HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    return hmsg_boundary("hmsg_test_dbscan", -1, [&] {
+        ScopedStream s(hipStreamNonBlocking);
         {
             CloudOps ops;
             ops.s = s;
@@ -1957,10 +1956,5 @@ extern "C" int hmsg_test_dbscan(const double* pts, int32_t K, const int64_t* siz
                 }
             }
         }
-    } catch (const hmsg_error& e) {
-        fprintf(stderr, "hmsg_test_dbscan: %s\n", e.msg.c_str());
-        rc = e.code;
-    }
-    if (s) (void)hipStreamDestroy(s);
-    return rc;
+    });
 }

@@ -10,7 +10,7 @@
 //     are all-reduced in place (graph.py:410-415: sums and counts add).
 //
 // librccl is loaded on first use (dlopen): a single-GPU process never needs it, and the kernel simulator build has none.
-#include "hmsg_common.h"
+#include "hmsg_boundary.h"
 
 #include <dlfcn.h>
 
@@ -133,34 +133,14 @@ void local_phase_then_agree(hmsg_comm* c, hipStream_t s, const char* what, F&& f
     int code = HMSG_OK;
     try {
         f();
-    } catch (const hmsg_error& e) {
-        mine = e.msg;
+    } catch (...) {      // (whatever it is: this rank must still reach the agreement below)
+        hmsg_error e = hmsg_current_error();
+        mine.swap(e.msg);
         code = e.code;
-    } catch (const std::exception& e) {
-        mine = e.what();
-        code = HMSG_ERR_INVALID;
+        if (mine.empty()) mine = what;
     }
     if (!all_ranks_ok(c, mine.empty(), s))
         throw hmsg_error{mine.empty() ? HMSG_ERR_INVALID : code, mine.empty() ? std::string(what) + ": another rank failed (see its hmsg_last_error)" : mine};
-}
-template <typename F>
-int comm_guard(std::string* err, F&& f) {        // no exception crosses the C boundary
-    try {
-        f();
-        return HMSG_OK;
-    } catch (const hmsg_error& e) {
-        if (err) *err = e.msg;
-        return e.code;
-    } catch (const std::bad_alloc&) {
-        if (err) *err = "out of host memory";
-        return HMSG_ERR_NOMEM;
-    } catch (const std::exception& e) {
-        if (err) *err = e.what();
-        return HMSG_ERR_INVALID;
-    } catch (...) {
-        if (err) *err = "unknown error";
-        return HMSG_ERR_INVALID;
-    }
 }
 }  // namespace
 
@@ -168,7 +148,7 @@ extern "C" {
 
 int hmsg_comm_unique_id(uint8_t* out_id) {
     if (!out_id) return HMSG_ERR_INVALID;
-    return comm_guard(&g_comm_err, [&] {
+    return hmsg_boundary(&g_comm_err, -1, [&] {
         rccl_need();
         rcclUniqueId id;
         rccl_try(rccl().GetUniqueId(&id), "ncclGetUniqueId");
@@ -181,7 +161,7 @@ int hmsg_comm_create(const uint8_t* id, int32_t rank, int32_t world, int32_t dev
     *out = nullptr;
     if (world < 1 || rank < 0 || rank >= world) return HMSG_ERR_INVALID;
     hmsg_comm* c = nullptr;
-    const int rc = comm_guard(&g_comm_err, [&] {
+    const int rc = hmsg_boundary(&g_comm_err, -1, [&] {
         c = new hmsg_comm();
         c->rank = rank;
         c->world = world;
@@ -221,8 +201,7 @@ int hmsg_allgather_nodes(hmsg_t* h, hmsg_comm_t* c, int32_t n_rooms_local, hmsg_
     if (!h || !c || !out_index) return HMSG_ERR_INVALID;
     *out_index = nullptr;
     int rc_index = HMSG_OK;
-    const int rc = comm_guard(&h->err, [&] {
-        HIP_TRY(hipSetDevice(h->cfg.device_id));
+    const int rc = hmsg_boundary(h, [&] {
         hipStream_t s = h->stream;
         const int W = c->world, D = h->cfg.feat_dim;
         const long long n = (long long)h->nodes.size();
@@ -308,8 +287,7 @@ int hmsg_allgather_nodes(hmsg_t* h, hmsg_comm_t* c, int32_t n_rooms_local, hmsg_
 
 int hmsg_allreduce_feature_sums(hmsg_t* h, hmsg_comm_t* c) {
     if (!h || !c) return HMSG_ERR_INVALID;
-    const int rc = comm_guard(&h->err, [&] {
-        HIP_TRY(hipSetDevice(h->cfg.device_id));
+    const int rc = hmsg_boundary(h, [&] {
         hipStream_t s = h->stream;
         std::string mine;
         if (!h->feats_final) mine = "hmsg_allreduce_feature_sums: run hmsg_fuse_frames first";
@@ -403,7 +381,7 @@ extern "C" {
  * can use the pair directly. */
 int hmsg_comm_send(hmsg_t* h, hmsg_comm_t* c, const void* dev_buf, int64_t bytes, int32_t dst) {
     if (!h || !c || bytes < 0 || (bytes && !dev_buf) || dst < 0 || dst >= c->world || dst == c->rank) return HMSG_ERR_INVALID;
-    const int rc = comm_guard(&h->err, [&] {
+    const int rc = hmsg_boundary(&h->err, -1, [&] {
         HMSG_REQUIRE(c->comm, HMSG_ERR_INVALID, "hmsg_comm_send: a communicator of one rank has nobody to send to");
         HIP_TRY(hipSetDevice(h->cfg.device_id));
         if (bytes) rccl_try(rccl().Send(dev_buf, (size_t)bytes, RCCL_INT8, dst, c->comm, h->stream), "ncclSend");
@@ -414,7 +392,7 @@ int hmsg_comm_send(hmsg_t* h, hmsg_comm_t* c, const void* dev_buf, int64_t bytes
 }
 int hmsg_comm_recv(hmsg_t* h, hmsg_comm_t* c, void* dev_buf, int64_t bytes, int32_t src) {
     if (!h || !c || bytes < 0 || (bytes && !dev_buf) || src < 0 || src >= c->world || src == c->rank) return HMSG_ERR_INVALID;
-    const int rc = comm_guard(&h->err, [&] {
+    const int rc = hmsg_boundary(&h->err, -1, [&] {
         HMSG_REQUIRE(c->comm, HMSG_ERR_INVALID, "hmsg_comm_recv: a communicator of one rank has nobody to receive from");
         HIP_TRY(hipSetDevice(h->cfg.device_id));
         if (bytes) rccl_try(rccl().Recv(dev_buf, (size_t)bytes, RCCL_INT8, src, c->comm, h->stream), "ncclRecv");
@@ -437,8 +415,7 @@ int hmsg_comm_recv(hmsg_t* h, hmsg_comm_t* c, void* dev_buf, int64_t bytes, int3
 int hmsg_merge_tree_sharded(hmsg_t* h, hmsg_comm_t* c, int32_t total_frames, int32_t* holds_result) {
     if (!h || !c || !holds_result) return HMSG_ERR_INVALID;
     *holds_result = 0;
-    const int rc = comm_guard(&h->err, [&] {
-        HIP_TRY(hipSetDevice(h->cfg.device_id));
+    const int rc = hmsg_boundary(h, [&] {
         hipStream_t s = h->stream;
         const int W = c->world, me = c->rank;
         const double factor = h->cfg.overlap_thresh_factor;

@@ -267,6 +267,24 @@ struct DevBuf {
     size_t bytes() const { return n * sizeof(T); }
 };
 
+// a stream / an event of one call's own (the entry points without a handle): made here, destroyed when the call ends either way
+struct ScopedStream {
+    hipStream_t s = nullptr;
+    explicit ScopedStream(unsigned flags) { HIP_TRY(hipStreamCreateWithFlags(&s, flags)); }
+    ScopedStream(const ScopedStream&) = delete;
+    ScopedStream& operator=(const ScopedStream&) = delete;
+    ~ScopedStream() { (void)hipStreamDestroy(s); }
+    operator hipStream_t() const { return s; }
+};
+struct ScopedEvent {
+    hipEvent_t e = nullptr;
+    ScopedEvent() { HIP_TRY(hipEventCreate(&e)); }
+    ScopedEvent(const ScopedEvent&) = delete;
+    ScopedEvent& operator=(const ScopedEvent&) = delete;
+    ~ScopedEvent() { (void)hipEventDestroy(e); }
+    operator hipEvent_t() const { return e; }
+};
+
 // ------------------------------------------------------------------ pinned host buffer + low-latency wait
 // The merge fold reads a few hundred bytes back twice per step.  A pageable destination makes the copy a blocking
 // staged transfer and hipStreamSynchronize parks the thread (tens of microseconds to wake up, a thousand times per

@@ -9,7 +9,7 @@
 // pass in int32, vertical pass (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2.  The kernel evaluates
 // exactly that per output pixel (the four taps come through L1 / L2; a crop's source window is a few hundred KB).
 // The launch is bound by the HBM WRITE of the crops: 2 M S^2 3 bytes per frame (50 MB at M = 32, S = 512).
-#include "hmsg_common.h"
+#include "hmsg_boundary.h"
 
 #include <cmath>
 
@@ -148,96 +148,79 @@ extern "C" int hmsg_crop_resize_batch(int32_t device_id, int32_t H, int32_t W, c
     if (H <= 0 || W <= 0 || !image || M < 0 || (M > 0 && !bbox) || out_size <= 0 || (out_size & 3)) return HMSG_ERR_INVALID;
     if (out_masked && !segs) return HMSG_ERR_INVALID;
     if (M == 0 || (!out_plain && !out_masked)) return HMSG_OK;
-    std::vector<CropRect> rects;
-    for (int v = 0; v < 2; ++v) {
-        if (!(v ? out_masked : out_plain)) continue;
-        for (int m = 0; m < M; ++m) {
-            double x = bbox[m * 4], y = bbox[m * 4 + 1], w = bbox[m * 4 + 2], h = bbox[m * 4 + 3];
-            if (v == 0) {                       // crop_bbox: increase_bbox_by_margin (sam_utils.py:67-81)
-                x -= bbox_margin;
-                y -= bbox_margin;
-                w += bbox_margin * 2;
-                h += bbox_margin * 2;
-                if (x < 0) {
-                    w += x;
-                    x = 0;
+    return hmsg_boundary("hmsg_crop_resize_batch", device_id, [&] {
+        std::vector<CropRect> rects;
+        for (int v = 0; v < 2; ++v) {
+            if (!(v ? out_masked : out_plain)) continue;
+            for (int m = 0; m < M; ++m) {
+                double x = bbox[m * 4], y = bbox[m * 4 + 1], w = bbox[m * 4 + 2], h = bbox[m * 4 + 3];
+                if (v == 0) {                       // crop_bbox: increase_bbox_by_margin (sam_utils.py:67-81)
+                    x -= bbox_margin;
+                    y -= bbox_margin;
+                    w += bbox_margin * 2;
+                    h += bbox_margin * 2;
+                    if (x < 0) {
+                        w += x;
+                        x = 0;
+                    }
+                    if (y < 0) {
+                        h += y;
+                        y = 0;
+                    }
                 }
-                if (y < 0) {
-                    h += y;
-                    y = 0;
+                CropRect r{0, 0, 0, 0, v ? m : -1, m, v, 0};
+                const bool finite = std::fabs(x) < 1e15 && std::fabs(y) < 1e15 && std::fabs(w) < 1e15 && std::fabs(h) < 1e15;   // (NaN fails)
+                const long long xi = finite ? (long long)x : -1, yi = finite ? (long long)y : -1, wi = finite ? (long long)w : 0,
+                                hi = finite ? (long long)h : 0;                                                // int(): toward zero
+                if (xi >= 0 && yi >= 0 && wi > 0 && hi > 0) {
+                    clip_slice(xi, wi, W, r.x0, r.w);
+                    clip_slice(yi, hi, H, r.y0, r.h);
                 }
+                HMSG_REQUIRE(r.w > 0 && r.h > 0, HMSG_ERR_INVALID,
+                             "mask " + std::to_string(m) + " has an empty " + (v ? "masked" : "bounding-box") + " crop (cv2.resize raises on it)");
+                rects.push_back(r);
             }
-            CropRect r{0, 0, 0, 0, v ? m : -1, m, v, 0};
-            const bool finite = std::fabs(x) < 1e15 && std::fabs(y) < 1e15 && std::fabs(w) < 1e15 && std::fabs(h) < 1e15;   // (NaN fails)
-            const long long xi = finite ? (long long)x : -1, yi = finite ? (long long)y : -1, wi = finite ? (long long)w : 0,
-                            hi = finite ? (long long)h : 0;                                                // int(): toward zero
-            if (xi >= 0 && yi >= 0 && wi > 0 && hi > 0) {
-                clip_slice(xi, wi, W, r.x0, r.w);
-                clip_slice(yi, hi, H, r.y0, r.h);
-            }
-            if (r.w <= 0 || r.h <= 0) {
-                fprintf(stderr, "hmsg_crop_resize_batch: mask %d has an empty %s crop (cv2.resize raises on it)\n", m,
-                        v ? "masked" : "bounding-box");
-                return HMSG_ERR_INVALID;
-            }
-            rects.push_back(r);
         }
-    }
-    hipStream_t s = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    int rc = HMSG_OK;
-    try {
-        HIP_TRY(hipSetDevice(device_id));
-        HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreate(&ev0));
-        HIP_TRY(hipEventCreate(&ev1));
-        {
-            const size_t S = (size_t)out_size, crop_bytes = S * S * 3, img_bytes = (size_t)H * W * 3, seg_bytes = (size_t)M * H * W;
-            DevBuf<unsigned char> d_img, d_seg, d_plain, d_masked;
-            DevBuf<CropRect> d_rects;
-            const unsigned char* p_img = image;
-            const unsigned char* p_seg = segs;
-            if (!hmsg_is_device_ptr(image)) {
-                d_img.alloc(img_bytes);
-                HIP_TRY(hipMemcpyAsync(d_img.p, image, img_bytes, hipMemcpyHostToDevice, s));
-                p_img = d_img.p;
-            }
-            if (out_masked && !hmsg_is_device_ptr(segs)) {
-                d_seg.alloc(seg_bytes);
-                HIP_TRY(hipMemcpyAsync(d_seg.p, segs, seg_bytes, hipMemcpyHostToDevice, s));
-                p_seg = d_seg.p;
-            }
-            unsigned char* p_plain = out_plain;
-            unsigned char* p_masked = out_masked;
-            const bool plain_host = out_plain && !hmsg_is_device_ptr(out_plain), masked_host = out_masked && !hmsg_is_device_ptr(out_masked);
-            if (plain_host) {
-                d_plain.alloc(crop_bytes * M);
-                p_plain = d_plain.p;
-            }
-            if (masked_host) {
-                d_masked.alloc(crop_bytes * M);
-                p_masked = d_masked.p;
-            }
-            d_rects.alloc(rects.size());
-            HIP_TRY(hipMemcpyAsync(d_rects.p, rects.data(), rects.size() * sizeof(CropRect), hipMemcpyHostToDevice, s));
-            HIP_TRY(hipEventRecord(ev0, s));
-            hipLaunchKernelGGL(k_crop_resize, dim3(cdiv(S, CROP_ROWS), (unsigned)rects.size()), dim3(256), 0, s, p_img, p_seg, H, W,
-                               (const CropRect*)d_rects.p, out_size, p_plain, p_masked);
-            HMSG_CHECK_LAUNCH();
-            HIP_TRY(hipEventRecord(ev1, s));
-            if (plain_host) HIP_TRY(hipMemcpyAsync(out_plain, p_plain, crop_bytes * M, hipMemcpyDeviceToHost, s));
-            if (masked_host) HIP_TRY(hipMemcpyAsync(out_masked, p_masked, crop_bytes * M, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            float ms = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
-            if (device_ms) *device_ms = ms;
+        ScopedStream s(hipStreamNonBlocking);
+        ScopedEvent ev0, ev1;
+        const size_t S = (size_t)out_size, crop_bytes = S * S * 3, img_bytes = (size_t)H * W * 3, seg_bytes = (size_t)M * H * W;
+        DevBuf<unsigned char> d_img, d_seg, d_plain, d_masked;
+        DevBuf<CropRect> d_rects;
+        const unsigned char* p_img = image;
+        const unsigned char* p_seg = segs;
+        if (!hmsg_is_device_ptr(image)) {
+            d_img.alloc(img_bytes);
+            HIP_TRY(hipMemcpyAsync(d_img.p, image, img_bytes, hipMemcpyHostToDevice, s));
+            p_img = d_img.p;
         }
-    } catch (const hmsg_error& e) {
-        fprintf(stderr, "hmsg_crop_resize_batch: %s\n", e.msg.c_str());
-        rc = e.code;
-    }
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    if (s) (void)hipStreamDestroy(s);
-    return rc;
+        if (out_masked && !hmsg_is_device_ptr(segs)) {
+            d_seg.alloc(seg_bytes);
+            HIP_TRY(hipMemcpyAsync(d_seg.p, segs, seg_bytes, hipMemcpyHostToDevice, s));
+            p_seg = d_seg.p;
+        }
+        unsigned char* p_plain = out_plain;
+        unsigned char* p_masked = out_masked;
+        const bool plain_host = out_plain && !hmsg_is_device_ptr(out_plain), masked_host = out_masked && !hmsg_is_device_ptr(out_masked);
+        if (plain_host) {
+            d_plain.alloc(crop_bytes * M);
+            p_plain = d_plain.p;
+        }
+        if (masked_host) {
+            d_masked.alloc(crop_bytes * M);
+            p_masked = d_masked.p;
+        }
+        d_rects.alloc(rects.size());
+        HIP_TRY(hipMemcpyAsync(d_rects.p, rects.data(), rects.size() * sizeof(CropRect), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipEventRecord(ev0, s));
+        hipLaunchKernelGGL(k_crop_resize, dim3(cdiv(S, CROP_ROWS), (unsigned)rects.size()), dim3(256), 0, s, p_img, p_seg, H, W,
+                           (const CropRect*)d_rects.p, out_size, p_plain, p_masked);
+        HMSG_CHECK_LAUNCH();
+        HIP_TRY(hipEventRecord(ev1, s));
+        if (plain_host) HIP_TRY(hipMemcpyAsync(out_plain, p_plain, crop_bytes * M, hipMemcpyDeviceToHost, s));
+        if (masked_host) HIP_TRY(hipMemcpyAsync(out_masked, p_masked, crop_bytes * M, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+        if (device_ms) *device_ms = ms;
+    });
 }

@@ -12,7 +12,7 @@
 // network, not stable); here ties are ordered by position.  It matters only when two equally high peaks sit within
 // 20 bins of each other.
 #include "hmsg_cloudops.h"
-#include "hmsg_common.h"
+#include "hmsg_boundary.h"
 
 #include <cmath>
 
@@ -168,8 +168,7 @@ std::vector<int> find_peaks(const std::vector<long long>& x, double height, int 
 
 extern "C" int hmsg_segment_floors(hmsg_t* h, hmsg_floor* out, int32_t capacity, int32_t* n_floors) {
     if (!h) return HMSG_ERR_INVALID;
-    try {
-        HIP_TRY(hipSetDevice(h->cfg.device_id));
+    return hmsg_boundary(h, [&] {
         HMSG_REQUIRE(h->map_ready && n_floors && (out || capacity == 0), HMSG_ERR_INVALID, "hmsg_segment_floors: bad argument (finalize the map first)");
         hipStream_t s = h->stream;
         const long long V = h->V;
@@ -255,7 +254,7 @@ extern "C" int hmsg_segment_floors(hmsg_t* h, hmsg_floor* out, int32_t capacity,
         slabs[slabs.size() - 1] = ymax;
         const int NF = (int)slabs.size() / 2;
         *n_floors = NF;
-        if (capacity == 0) return HMSG_OK;
+        if (capacity == 0) return;
         HMSG_REQUIRE(capacity >= NF, HMSG_ERR_INVALID, "hmsg_segment_floors: capacity too small (n_floors needed)");
         // ---- crops of the FULL map (:769-787)
         DevBuf<double> dsl;
@@ -282,9 +281,5 @@ extern "C" int hmsg_segment_floors(hmsg_t* h, hmsg_floor* out, int32_t capacity,
             o.zero_level = o.n_points ? o.bbox_min[1] : o.y_lo;
             o.height = o.y_hi - o.zero_level;
         }
-        return HMSG_OK;
-    } catch (const hmsg_error& e) {
-        h->err = e.msg;
-        return e.code;
-    }
+    });
 }

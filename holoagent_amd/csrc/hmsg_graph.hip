@@ -9,7 +9,7 @@
 // when every share is 0, the room whose vertex centroid is nearest to the instance's x/z centroid (:1645-1655);
 // label = arg-max over the label text features of emb . text^T (identify_object, :1441-1454, float64 MFMA GEMM);
 // object id = (room, running counter of that room) (:1696-1700).
-#include "hmsg_common.h"
+#include "hmsg_boundary.h"
 #include "hmsg_nn.h"
 #include "hmsg_view_project.h"
 #include <chrono>
@@ -23,8 +23,7 @@ int hmsg_build_object_nodes(hmsg_t* h, int32_t n_floors, const double* floor_zer
                             const int32_t* room_floor, const int64_t* vert_off, const double* verts_xz, int32_t n_labels,
                             const float* label_feats) {
     if (!h) return HMSG_ERR_INVALID;
-    try {
-        HIP_TRY(hipSetDevice(h->cfg.device_id));
+    return hmsg_boundary(h, [&] {
         HMSG_REQUIRE(h->pooled, HMSG_ERR_INVALID, "hmsg_build_object_nodes: run hmsg_pool_instances first");
         HMSG_REQUIRE(n_floors >= 0 && n_rooms >= 0 && (n_floors == 0 || (floor_zero && floor_height)) &&
                          (n_rooms == 0 || (room_floor && vert_off && verts_xz)) && (n_labels == 0 || label_feats),
@@ -39,7 +38,7 @@ int hmsg_build_object_nodes(hmsg_t* h, int32_t n_floors, const double* floor_zer
         const int N = (int)h->inst.off.size() - 1;
         h->nodes.clear();
         h->node_label.assign((size_t)std::max(N, 0), -1);
-        if (N <= 0) return HMSG_OK;
+        if (N <= 0) return;
         // labels: S = emb . text^T on the device (float32 values in float64 arithmetic, as NodeIndex.similarity)
         if (n_labels > 0) {
             hmsg_index_t* ix = nullptr;
@@ -122,11 +121,7 @@ int hmsg_build_object_nodes(hmsg_t* h, int32_t n_floors, const double* floor_zer
             }
         }
         laps.lap("floors / rooms (host)");
-        return HMSG_OK;
-    } catch (const hmsg_error& e) {
-        h->err = e.msg;
-        return e.code;
-    }
+    });
 }
 
 int64_t hmsg_num_nodes(const hmsg_t* h) { return h ? (int64_t)h->nodes.size() : -1; }
@@ -134,8 +129,7 @@ int64_t hmsg_num_nodes(const hmsg_t* h) { return h ? (int64_t)h->nodes.size() : 
 int hmsg_get_nodes(const hmsg_t* hc, hmsg_node* nodes, float* embeddings) {
     hmsg_ctx* h = const_cast<hmsg_ctx*>(hc);
     if (!h) return HMSG_ERR_INVALID;
-    try {
-        HIP_TRY(hipSetDevice(h->cfg.device_id));
+    return hmsg_boundary(h, [&] {
         const size_t n = h->nodes.size();
         if (nodes && n) memcpy(nodes, h->nodes.data(), n * sizeof(hmsg_node));
         if (embeddings && n) {
@@ -144,11 +138,7 @@ int hmsg_get_nodes(const hmsg_t* hc, hmsg_node* nodes, float* embeddings) {
             HIP_TRY(hipMemcpy(all.data(), h->inst_feats.p, NI * D * 4, hipMemcpyDeviceToHost));
             for (size_t k = 0; k < n; ++k) memcpy(embeddings + k * D, all.data() + (size_t)h->nodes[k].instance * D, D * 4);
         }
-        return HMSG_OK;
-    } catch (const hmsg_error& e) {
-        h->err = e.msg;
-        return e.code;
-    }
+    });
 }
 
 // retrieval index over the node table, built from the device-resident pooled features (node k -> its instance's
@@ -162,8 +152,7 @@ __global__ void k_gather_rows_f32(const float* __restrict__ src, const int* __re
 int hmsg_index_from_nodes(hmsg_t* h, hmsg_index_t** out) {
     if (!h || !out) return HMSG_ERR_INVALID;
     *out = nullptr;
-    try {
-        HIP_TRY(hipSetDevice(h->cfg.device_id));
+    return hmsg_boundary(h, [&] {
         const int n = (int)h->nodes.size(), D = h->cfg.feat_dim;
         HMSG_REQUIRE(n > 0, HMSG_ERR_INVALID, "hmsg_index_from_nodes: no nodes (hmsg_build_object_nodes)");
         std::vector<int> inst((size_t)n), room((size_t)n);
@@ -180,11 +169,9 @@ int hmsg_index_from_nodes(hmsg_t* h, hmsg_index_t** out) {
                            (const int*)d_inst.p, n, D, emb.p);
         HMSG_CHECK_LAUNCH();
         HIP_TRY(hipStreamSynchronize(h->stream));
-        return hmsg_index_create(h->cfg.device_id, D, n, emb.p, 0, room.data(), out);
-    } catch (const hmsg_error& e) {
-        h->err = e.msg;
-        return e.code;
-    }
+        const int rc = hmsg_index_create(h->cfg.device_id, D, n, emb.p, 0, room.data(), out);
+        HMSG_REQUIRE(rc == HMSG_OK, rc, "hmsg_index_from_nodes: hmsg_index_create failed");
+    });
 }
 
 }  // extern "C"
@@ -413,8 +400,7 @@ extern "C" int hmsg_room_clouds(hmsg_t* h, double y_lo, double y_hi, const doubl
                                 int32_t n_rooms, const int64_t* room_off, const double* room_xz, int64_t* out_sizes,
                                 int32_t* out_index, int64_t out_capacity, int64_t* n_floor_points) {
     if (!h) return HMSG_ERR_INVALID;
-    try {
-        HIP_TRY(hipSetDevice(h->cfg.device_id));
+    return hmsg_boundary(h, [&] {
         HMSG_REQUIRE(h->map_ready && T && n_levels >= 0 && (n_levels == 0 || z_levels) && n_rooms >= 0 && room_off && out_sizes && n_floor_points,
                      HMSG_ERR_INVALID, "hmsg_room_clouds: bad argument (finalize the map first)");
         hipStream_t s = h->stream;
@@ -457,7 +443,7 @@ extern "C" int hmsg_room_clouds(hmsg_t* h, double y_lo, double y_hi, const doubl
                 HIP_TRY(hipStreamSynchronize(s));
                 h->room_n = n_rooms;
             }
-            return HMSG_OK;
+            return;
         }
         HMSG_REQUIRE((long long)n_rooms * NF < (1ll << 33), HMSG_ERR_UNSUPPORTED, "hmsg_room_clouds: too many rooms x floor points");
         const unsigned tie_cap = 1u << 20;
@@ -587,11 +573,7 @@ extern "C" int hmsg_room_clouds(hmsg_t* h, double y_lo, double y_hi, const doubl
         }
         HIP_TRY(hipStreamSynchronize(s));
         HMSG_REQUIRE(!out_index || total <= out_capacity, HMSG_ERR_INVALID, "hmsg_room_clouds: out_index too small (sum of out_sizes needed)");
-        return HMSG_OK;
-    } catch (const hmsg_error& e) {
-        h->err = e.msg;
-        return e.code;
-    }
+    });
 }
 
 // camera -> room distance table of compute_room_embeddings (utils/graph_utils.py:244-291) from the room clouds the last
@@ -599,12 +581,11 @@ extern "C" int hmsg_room_clouds(hmsg_t* h, double y_lo, double y_hi, const doubl
 // (np.min over them is order-independent); out f64 [n_q][n_rooms].
 extern "C" int hmsg_room_camera_distances(hmsg_t* h, int32_t n_rooms, int64_t n_q, const double* q_xz, double* out) {
     if (!h || n_q < 0 || (n_q > 0 && (!q_xz || !out))) return HMSG_ERR_INVALID;
-    try {
-        HIP_TRY(hipSetDevice(h->cfg.device_id));
+    return hmsg_boundary(h, [&] {
         HMSG_REQUIRE(h->room_n > 0, HMSG_ERR_INVALID, "hmsg_room_camera_distances: call hmsg_room_clouds first");
         HMSG_REQUIRE(n_rooms == h->room_n, HMSG_ERR_INVALID,
                      "hmsg_room_camera_distances: n_rooms is not the room count of the last hmsg_room_clouds call (out is [n_q][n_rooms])");
-        if (n_q == 0) return HMSG_OK;
+        if (n_q == 0) return;
         hipStream_t s = h->stream;
         DevBuf<double> xz, dq, dout;
         xz.alloc((size_t)std::max<long long>(h->room_total, 1) * 2);
@@ -622,11 +603,7 @@ extern "C" int hmsg_room_camera_distances(hmsg_t* h, int32_t n_rooms, int64_t n_
         HMSG_CHECK_LAUNCH();
         HIP_TRY(hipStreamSynchronize(s));
         d2h_bounce(out, dout.p, (size_t)n_q * (size_t)h->room_n * 8);
-        return HMSG_OK;
-    } catch (const hmsg_error& e) {
-        h->err = e.msg;
-        return e.code;
-    }
+    });
 }
 
 // ------------------------------------------------------------------------------------------ A10: view <-> object topology
@@ -694,12 +671,11 @@ extern "C" int hmsg_object_views(hmsg_t* h, int32_t n_views, const double* pose_
                                  const int32_t* pair_inst, const int32_t* pair_view, double min_visible_ratio, double max_depth,
                                  uint8_t* visible, double* mean_depth) {
     if (!h) return HMSG_ERR_INVALID;
-    try {
-        HIP_TRY(hipSetDevice(h->cfg.device_id));
+    return hmsg_boundary(h, [&] {
         HMSG_REQUIRE(h->merged, HMSG_ERR_INVALID, "hmsg_object_views: run hmsg_merge_instances first");
         HMSG_REQUIRE(n_views >= 0 && n_pairs >= 0 && n_pairs < (1ll << 31) && (n_pairs == 0 || (pose_inv && wh && K && pair_inst && pair_view && visible && mean_depth)),
                      HMSG_ERR_INVALID, "hmsg_object_views: bad argument");
-        if (n_pairs == 0) return HMSG_OK;
+        if (n_pairs == 0) return;
         const long long NI = (long long)h->inst.off.size() - 1;
         std::vector<ViewPair> hp((size_t)n_pairs);
         for (int64_t k = 0; k < n_pairs; ++k) {
@@ -729,9 +705,5 @@ extern "C" int hmsg_object_views(hmsg_t* h, int32_t n_views, const double* pose_
         HIP_TRY(hipStreamSynchronize(s));
         d2h_bounce(visible, d_vis.p, (size_t)n_pairs);
         d2h_bounce(mean_depth, d_md.p, (size_t)n_pairs * 8);
-        return HMSG_OK;
-    } catch (const hmsg_error& e) {
-        h->err = e.msg;
-        return e.code;
-    }
+    });
 }

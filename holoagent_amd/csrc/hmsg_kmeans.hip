@@ -15,7 +15,7 @@
 // of the exact value where the libraries are within a few; a point whose two nearest centres tie to ~1e-7 relative can
 // therefore land on the other side.  tests/test_kmeans_cabi.py holds this file to scikit-learn itself (labels equal, centres
 // to 1e-6) on the room fixtures and on random data; scikit-learn stays the oracle.
-#include "../../include/hmsg.h"
+#include "hmsg_boundary.h"
 
 #include <algorithm>
 #include <cmath>
@@ -325,7 +325,7 @@ extern "C" int hmsg_kmeans(const float* X_in, int64_t n64, int32_t D, int32_t k,
     if (!X_in || n64 <= 0 || n64 > (1 << 24) || D <= 0 || k <= 0 || k > n64 || n_init <= 0 || max_iter <= 0 || k > 65536 || !out_labels ||
         !out_centers)
         return HMSG_ERR_INVALID;
-    try {
+    return hmsg_boundary(nullptr, -1, [&] {
         const int n = (int)n64;
         // KMeans.fit: X = copy, X_mean = X.mean(axis=0) (float32, rows added one after the other), X -= X_mean
         std::vector<float> X(X_in, X_in + (size_t)n * D), mean((size_t)D, 0.f);
@@ -389,10 +389,5 @@ extern "C" int hmsg_kmeans(const float* X_in, int64_t n64, int32_t D, int32_t k,
         for (int i = 0; i < n; ++i) out_labels[i] = best.labels[(size_t)i];
         if (out_inertia) *out_inertia = best.inertia;
         if (out_n_iter) *out_n_iter = best.n_iter;
-        return HMSG_OK;
-    } catch (const std::exception&) {
-        return HMSG_ERR_NOMEM;
-    } catch (...) {
-        return HMSG_ERR_INVALID;
-    }
+    });
 }

@@ -23,6 +23,7 @@
 //       those points (CloudOps::dbscan_keep_largest, core0);
 //   (4) empty masks never pair and are dropped by the min-points filter at the end: they are left out.
 //   HMSG_DEBUG_NOANCHOR=1 disables (3) (tests compare the two folds bit for bit).
+#include "hmsg_boundary.h"
 #include "hmsg_cloudops.h"
 
 #include <algorithm>
@@ -2010,12 +2011,8 @@ struct FoldPipe {
                 }
                 HIP_TRY(hipStreamSynchronize(s));
             }
-        } catch (const hmsg_error& e) {
-            fail(e);
-        } catch (const std::exception& e) {
-            fail(hmsg_error{HMSG_ERR_HIP, e.what()});
-        } catch (...) {
-            fail(hmsg_error{HMSG_ERR_HIP, "merge fold worker: unknown exception"});
+        } catch (...) {      // (kept for the thread that joins the fold: hmsg_fold_pipe_* rethrow it)
+            fail(hmsg_current_error());
         }
         if (s) {
             (void)hipStreamSynchronize(s);
@@ -2484,8 +2481,7 @@ extern "C" int hmsg_points_min_dist_2d(int32_t device_id, int32_t n_sets, const 
                                        const double* q_xy, double* out) {
     if (n_sets < 0 || n_q < 0 || !set_off || !out) return HMSG_ERR_INVALID;
     if (n_sets == 0 || n_q == 0) return HMSG_OK;
-    try {
-        HIP_TRY(hipSetDevice(device_id));
+    return hmsg_boundary("hmsg_points_min_dist_2d", device_id, [&] {
         const long long np = set_off[n_sets];
         DevBuf<long long> d_off;
         DevBuf<double> d_p, d_q, d_o;
@@ -2504,11 +2500,7 @@ extern "C" int hmsg_points_min_dist_2d(int32_t device_id, int32_t n_sets, const 
         HMSG_CHECK_LAUNCH();
         HIP_TRY(hipDeviceSynchronize());
         HIP_TRY(hipMemcpy(out, d_o.p, (size_t)n_q * n_sets * 8, hipMemcpyDeviceToHost));
-        return HMSG_OK;
-    } catch (const hmsg_error& e) {
-        fprintf(stderr, "hmsg_points_min_dist_2d: %s\n", e.msg.c_str());
-        return e.code;
-    }
+    });
 }
 
 // ------------------------------------------------------------------------------------------ A8 helper

@@ -10,7 +10,7 @@
 //   host   : what the reference's bookkeeping does with the pairs, step by step: `np.where(scores > 0)` in row-major order, the
 //            dictionary chaining (an index that was already absorbed can still become a key: kept), the objects not involved
 //            appended in index order, and `list(set(j))` -- CPython's set iteration order, restated below.
-#include "hmsg_common.h"
+#include "hmsg_boundary.h"
 
 #include <algorithm>
 #include <cmath>
@@ -239,8 +239,7 @@ extern "C" int hmsg_merge_room_objects(hmsg_t* h, int32_t n, const double* point
                                        double overlap_threshold, double radius, int32_t* n_groups, int32_t* group_off, int32_t* group_members,
                                        int32_t members_capacity) {
     if (!h || n < 0 || (n > 0 && (!points || !off || !name_id)) || !n_groups || !group_off || !group_members) return HMSG_ERR_INVALID;
-    try {
-        HIP_TRY(hipSetDevice(h->cfg.device_id));
+    return hmsg_boundary(h, [&] {
         std::vector<long long> start((size_t)n);
         std::vector<int> count((size_t)n);
         for (int i = 0; i < n; ++i) {
@@ -249,22 +248,10 @@ extern "C" int hmsg_merge_room_objects(hmsg_t* h, int32_t n, const double* point
         }
         std::vector<int> go, mem;
         hmsg_merge_groups(h, n, points, start.data(), count.data(), name_id, overlap_threshold, radius, go, mem);
-        if ((int64_t)mem.size() > (int64_t)members_capacity) {
-            h->err = "hmsg_merge_room_objects: group_members too small (n (n + 1) entries always suffice)";
-            return HMSG_ERR_INVALID;
-        }
+        HMSG_REQUIRE((int64_t)mem.size() <= (int64_t)members_capacity, HMSG_ERR_INVALID,
+                     "hmsg_merge_room_objects: group_members too small (n (n + 1) entries always suffice)");
         *n_groups = (int32_t)go.size() - 1;
         std::copy(go.begin(), go.end(), group_off);
         std::copy(mem.begin(), mem.end(), group_members);
-        return HMSG_OK;
-    } catch (const hmsg_error& e) {
-        h->err = e.msg;
-        return e.code;
-    } catch (const std::exception& e) {
-        h->err = e.what();
-        return HMSG_ERR_INVALID;
-    } catch (...) {
-        h->err = "unknown error";
-        return HMSG_ERR_INVALID;
-    }
+    });
 }

@@ -9,7 +9,7 @@
 // number printed like Python's float.__repr__ (shortest digits that round-trip -- std::to_chars gives the same digits --
 // laid out with Python's rule: fixed notation while -4 <= exponent < 16, else d.ddde+XX).  Strings come from the caller
 // already JSON-encoded (it owns the ids, names and view lists); only numbers are produced here.
-#include "hmsg_common.h"
+#include "hmsg_boundary.h"
 
 #include <atomic>
 #include <charconv>
@@ -104,7 +104,7 @@ bool write_file(const std::string& path, const char* data, size_t n) {
 extern "C" int hmsg_save_objects(hmsg_t* hc, const char* dir, int64_t n, const hmsg_object_record* recs, int32_t n_threads) {
     hmsg_ctx* h = hc;
     if (!h || !dir || n < 0 || (n > 0 && !recs)) return HMSG_ERR_INVALID;
-    try {
+    return hmsg_boundary(&h->err, -1, [&] {
         HMSG_REQUIRE((h->merged || h->tree_partial) && h->pooled, HMSG_ERR_INVALID, "hmsg_save_objects: instances are not merged and pooled");
         const int64_t NI = (int64_t)h->inst.off.size() - 1;
         const int D = h->cfg.feat_dim;
@@ -112,7 +112,7 @@ extern "C" int hmsg_save_objects(hmsg_t* hc, const char* dir, int64_t n, const h
             HMSG_REQUIRE(recs[i].instance >= 0 && recs[i].instance < NI && recs[i].file_stem && recs[i].object_id_json &&
                              recs[i].room_id_json && recs[i].name_json && recs[i].view_ids_json && recs[i].best_view_id_json,
                          HMSG_ERR_INVALID, "hmsg_save_objects: bad record");
-        if (n == 0) return HMSG_OK;
+        if (n == 0) return;
         HIP_TRY(hipSetDevice(h->cfg.device_id));
         std::vector<double> pts((size_t)std::max<long long>(h->inst.total, 1) * 3);
         std::vector<float> feats((size_t)NI * D);
@@ -186,17 +186,7 @@ extern "C" int hmsg_save_objects(hmsg_t* hc, const char* dir, int64_t n, const h
         work();
         for (auto& t : pool) t.join();
         HMSG_REQUIRE(!failed.load(), HMSG_ERR_INVALID, std::string("hmsg_save_objects: cannot write into ") + dir);
-        return HMSG_OK;
-    } catch (const hmsg_error& e) {
-        h->err = e.msg;
-        return e.code;
-    } catch (const std::exception& e) {
-        h->err = e.what();
-        return HMSG_ERR_INVALID;
-    } catch (...) {
-        h->err = "unknown error";
-        return HMSG_ERR_INVALID;
-    }
+    });
 }
 
 // ---- the other node records of save_hmsg_graph (graph.py:1801-1824): floors/<f>.{ply,json} (floor.py:37-52),
@@ -206,7 +196,7 @@ extern "C" int hmsg_save_objects(hmsg_t* hc, const char* dir, int64_t n, const h
 // float64 / float32 arrays and scalars as float.__repr__ of the double, integer arrays as decimal integers.
 extern "C" int hmsg_write_json(const char* path, int32_t n_fields, const hmsg_json_field* f) {
     if (!path || n_fields < 0 || (n_fields > 0 && !f)) return HMSG_ERR_INVALID;
-    try {
+    return hmsg_boundary(nullptr, -1, [&] {
         std::string js = "{";
         char num[40];
         auto put = [&](const hmsg_json_field& fd, int64_t i) {
@@ -216,10 +206,10 @@ extern "C" int hmsg_write_json(const char* path, int32_t n_fields, const hmsg_js
         };
         for (int32_t k = 0; k < n_fields; ++k) {
             const hmsg_json_field& fd = f[k];
-            if (!fd.key || fd.ndim < 0 || fd.ndim > 2 || fd.n0 < 0 || fd.n1 < 0) return HMSG_ERR_INVALID;
-            if (fd.kind != HMSG_JSON_RAW && fd.kind != HMSG_JSON_F64 && fd.kind != HMSG_JSON_F32 && fd.kind != HMSG_JSON_I64) return HMSG_ERR_INVALID;
+            HMSG_REQUIRE(fd.key && fd.ndim >= 0 && fd.ndim <= 2 && fd.n0 >= 0 && fd.n1 >= 0, HMSG_ERR_INVALID, "hmsg_write_json: bad field");
+            HMSG_REQUIRE(fd.kind == HMSG_JSON_RAW || fd.kind == HMSG_JSON_F64 || fd.kind == HMSG_JSON_F32 || fd.kind == HMSG_JSON_I64, HMSG_ERR_INVALID, "hmsg_write_json: bad field kind");
             const int64_t cnt = fd.ndim == 0 ? 1 : (fd.ndim == 1 ? fd.n0 : fd.n0 * fd.n1);
-            if (!fd.data && (fd.kind == HMSG_JSON_RAW || cnt > 0)) return HMSG_ERR_INVALID;
+            HMSG_REQUIRE(fd.data || (fd.kind != HMSG_JSON_RAW && cnt == 0), HMSG_ERR_INVALID, "hmsg_write_json: field without data");
             if (k) js += ", ";
             js += '"';
             js += fd.key;
@@ -250,12 +240,8 @@ extern "C" int hmsg_write_json(const char* path, int32_t n_fields, const hmsg_js
             }
         }
         js += '}';
-        return write_file(path, js.data(), js.size()) ? HMSG_OK : HMSG_ERR_INVALID;
-    } catch (const std::exception&) {
-        return HMSG_ERR_INVALID;
-    } catch (...) {
-        return HMSG_ERR_INVALID;
-    }
+        HMSG_REQUIRE(write_file(path, js.data(), js.size()), HMSG_ERR_INVALID, "hmsg_write_json: cannot write the file");
+    });
 }
 
 // <stem>.ply as Open3D 0.18's write_point_cloud writes a cloud without colours / normals (the header of hmsg_save_objects)
@@ -265,16 +251,12 @@ extern "C" int hmsg_write_ply(const char* path, const double* xyz, int64_t n) {
     const int hl = snprintf(hdr, sizeof(hdr),
                             "ply\nformat binary_little_endian 1.0\ncomment Created by Open3D\nelement vertex %lld\nproperty double x\n"
                             "property double y\nproperty double z\nend_header\n", (long long)n);
-    try {
+    return hmsg_boundary(nullptr, -1, [&] {
         std::vector<char> ply((size_t)hl + (size_t)n * 24);
         memcpy(ply.data(), hdr, (size_t)hl);
         if (n) memcpy(ply.data() + hl, xyz, (size_t)n * 24);
-        return write_file(path, ply.data(), ply.size()) ? HMSG_OK : HMSG_ERR_INVALID;
-    } catch (const std::exception&) {
-        return HMSG_ERR_INVALID;
-    } catch (...) {
-        return HMSG_ERR_INVALID;
-    }
+        HMSG_REQUIRE(write_file(path, ply.data(), ply.size()), HMSG_ERR_INVALID, "hmsg_write_ply: cannot write the file");
+    });
 }
 
 // ---- load side: the object table of a saved graph straight into a retrieval index
@@ -317,82 +299,82 @@ extern "C" int hmsg_index_load_objects(int32_t device_id, const char* dir, int64
                                        const int32_t* room_of_node, int32_t n_threads, hmsg_index_t** out, int32_t* feat_dim) {
     if (!dir || n <= 0 || !stems || !room_of_node || !out) return HMSG_ERR_INVALID;
     *out = nullptr;
-    std::vector<std::vector<double>> rows((size_t)n);
-    std::atomic<int64_t> next{0};
-    std::atomic<int> failed{0};
-    const std::string base = std::string(dir) + "/";
-    auto work = [&]() {
-        std::string text;
-        for (;;) {
-            const int64_t i = next.fetch_add(1);
-            if (i >= n || failed.load()) return;
-            FILE* f = stems[i] ? fopen((base + stems[i] + ".json").c_str(), "rb") : nullptr;
-            if (!f) {
-                failed.store(1);
-                return;
+    return hmsg_boundary("hmsg_index_load_objects", -1, [&] {
+        std::vector<std::vector<double>> rows((size_t)n);
+        std::atomic<int64_t> next{0};
+        std::atomic<int> failed{0};
+        const std::string base = std::string(dir) + "/";
+        auto work = [&]() {
+            std::string text;
+            for (;;) {
+                const int64_t i = next.fetch_add(1);
+                if (i >= n || failed.load()) return;
+                FILE* f = stems[i] ? fopen((base + stems[i] + ".json").c_str(), "rb") : nullptr;
+                if (!f) {
+                    failed.store(1);
+                    return;
+                }
+                fseek(f, 0, SEEK_END);
+                const long len = ftell(f);
+                fseek(f, 0, SEEK_SET);
+                text.resize((size_t)std::max<long>(len, 0));
+                const bool ok = len >= 0 && fread(&text[0], 1, (size_t)len, f) == (size_t)len;
+                fclose(f);
+                // (the key cannot occur inside another value: ids, names and view lists are the only strings of a record)
+                const size_t k = ok ? text.find("\"embedding\":") : std::string::npos;
+                if (k == std::string::npos) {
+                    failed.store(2);
+                    return;
+                }
+                const char* p = text.data() + k + 12;
+                const char* end = text.data() + text.size();
+                while (p < end && *p == ' ') ++p;
+                if (!parse_number_array(p, end, rows[(size_t)i])) {     // "" (an object saved without an embedding) lands here
+                    failed.store(2);
+                    return;
+                }
             }
-            fseek(f, 0, SEEK_END);
-            const long len = ftell(f);
-            fseek(f, 0, SEEK_SET);
-            text.resize((size_t)std::max<long>(len, 0));
-            const bool ok = len >= 0 && fread(&text[0], 1, (size_t)len, f) == (size_t)len;
-            fclose(f);
-            // (the key cannot occur inside another value: ids, names and view lists are the only strings of a record)
-            const size_t k = ok ? text.find("\"embedding\":") : std::string::npos;
-            if (k == std::string::npos) {
-                failed.store(2);
-                return;
-            }
-            const char* p = text.data() + k + 12;
-            const char* end = text.data() + text.size();
-            while (p < end && *p == ' ') ++p;
-            if (!parse_number_array(p, end, rows[(size_t)i])) {     // "" (an object saved without an embedding) lands here
-                failed.store(2);
-                return;
-            }
+        };
+        int nt = n_threads > 0 ? n_threads : (int)std::min<unsigned>(std::max(1u, std::thread::hardware_concurrency()), 32u);
+        nt = (int)std::min<int64_t>(nt, n);
+        std::vector<std::thread> pool;
+        for (int t = 1; t < nt; ++t) pool.emplace_back(work);
+        work();
+        for (auto& t : pool) t.join();
+        HMSG_REQUIRE(!failed.load(), HMSG_ERR_INVALID,
+                     std::string(failed.load() == 1 ? "an object record cannot be opened" : "an object record has no numeric \"embedding\" array") + " under " + dir);
+        const size_t D = rows[0].size();
+        HMSG_REQUIRE(D > 0, HMSG_ERR_INVALID, "an object record has an empty \"embedding\" array");
+        std::vector<double> table((size_t)n * D);
+        for (int64_t i = 0; i < n; ++i) {
+            HMSG_REQUIRE(rows[(size_t)i].size() == D, HMSG_ERR_INVALID,
+                         "embeddings of different lengths (" + std::to_string(D) + " and " + std::to_string(rows[(size_t)i].size()) + ")");
+            memcpy(&table[(size_t)i * D], rows[(size_t)i].data(), D * 8);
         }
-    };
-    int nt = n_threads > 0 ? n_threads : (int)std::min<unsigned>(std::max(1u, std::thread::hardware_concurrency()), 32u);
-    nt = (int)std::min<int64_t>(nt, n);
-    std::vector<std::thread> pool;
-    for (int t = 1; t < nt; ++t) pool.emplace_back(work);
-    work();
-    for (auto& t : pool) t.join();
-    if (failed.load()) {
-        fprintf(stderr, "hmsg_index_load_objects: %s under %s\n",
-                failed.load() == 1 ? "an object record cannot be opened" : "an object record has no numeric \"embedding\" array", dir);
-        return HMSG_ERR_INVALID;
-    }
-    const size_t D = rows[0].size();
-    if (D == 0) return HMSG_ERR_INVALID;
-    std::vector<double> table((size_t)n * D);
-    for (int64_t i = 0; i < n; ++i) {
-        if (rows[(size_t)i].size() != D) {
-            fprintf(stderr, "hmsg_index_load_objects: embeddings of different lengths (%zu and %zu)\n", D, rows[(size_t)i].size());
-            return HMSG_ERR_INVALID;
-        }
-        memcpy(&table[(size_t)i * D], rows[(size_t)i].data(), D * 8);
-    }
-    if (feat_dim) *feat_dim = (int32_t)D;
-    return hmsg_index_create(device_id, (int32_t)D, n, table.data(), 1, room_of_node, out);
+        if (feat_dim) *feat_dim = (int32_t)D;
+        const int rc = hmsg_index_create(device_id, (int32_t)D, n, table.data(), 1, room_of_node, out);
+        HMSG_REQUIRE(rc == HMSG_OK, rc, "hmsg_index_create failed");
+    });
 }
 
 // test hook: Python-repr formatting of doubles, newline separated (tests/test_persist_golden.py compares with repr())
 extern "C" int64_t hmsg_test_format_doubles(const double* v, int64_t n, char* out, int64_t cap) {
     int64_t used = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        if (used + 34 > cap) return -1;
-        char* e = py_repr(out + used, v[i]);
-        *e++ = '\n';
-        used = e - out;
-    }
-    return used;
+    const int rc = hmsg_boundary("hmsg_test_format_doubles", -1, [&] {
+        for (int64_t i = 0; i < n; ++i) {
+            HMSG_REQUIRE(used + 34 <= cap, HMSG_ERR_INVALID, "out too small");
+            char* e = py_repr(out + used, v[i]);
+            *e++ = '\n';
+            used = e - out;
+        }
+    });
+    return rc == HMSG_OK ? used : -1;
 }
 
 // test hook (include/hmsg_test.h): DevCache carving
 extern "C" int hmsg_test_allocator_carving(int32_t device_id, int32_t root_gb) {
-    try {
-        HIP_TRY(hipSetDevice(device_id));
+    int check = 0;          // the first check that failed
+    const int rc = hmsg_boundary("hmsg_test_allocator_carving", device_id, [&] {
         DevCache& c = dev_cache();
         const size_t GB = (size_t)1 << 30, root_bytes = (size_t)root_gb * GB;
         unsigned char* root = nullptr;
@@ -409,28 +391,25 @@ extern "C" int hmsg_test_allocator_carving(int32_t device_id, int32_t root_gb) {
             d.alloc(2 * GB + 12345);
         }
         auto inside = [&](const DevBuf<unsigned char>& x) { return x.p >= root && x.p + x.cap_bytes <= root + root_bytes; };
-        if (!inside(a) || !inside(b) || !inside(d)) return 1;
-        if (!(a.p + a.cap_bytes <= b.p && b.p + b.cap_bytes <= d.p)) return 2;          // cut off the front, in order
+        if (!inside(a) || !inside(b) || !inside(d)) { check = 1; return; }
+        if (!(a.p + a.cap_bytes <= b.p && b.p + b.cap_bytes <= d.p)) { check = 2; return; }          // cut off the front, in order
         DevBuf<unsigned char> e;
         e.alloc(3 * GB);                                        // outside a scope: never carved (a block of its own)
-        if (inside(e)) return 3;
+        if (inside(e)) { check = 3; return; }
         b.release();
         c.trim();                                               // pieces out: the root must survive
-        if (c.roots_.size() != 1) return 4;
+        if (c.roots_.size() != 1) { check = 4; return; }
         a.release();
         d.release();
         e.release();
         DevBuf<unsigned char> again;
         again.alloc(root_bytes);                                // every piece is back: the whole block, same address
-        if (again.p != root) return 5;
-        if (!c.roots_.empty() || !c.piece_root_.empty()) return 6;
+        if (again.p != root) { check = 5; return; }
+        if (!c.roots_.empty() || !c.piece_root_.empty()) { check = 6; return; }
         again.release();
         c.trim();
-        return 0;
-    } catch (const hmsg_error& e) {
-        fprintf(stderr, "hmsg_test_allocator_carving: %s\n", e.msg.c_str());
-        return -1;
-    }
+    });
+    return rc == HMSG_OK ? check : -1;
 }
 
 // The numbers of one key of a saved record, flattened in file order (load side of floors / rooms: "vertices", "embeddings",
@@ -439,48 +418,49 @@ extern "C" int hmsg_test_allocator_carving(int32_t device_id, int32_t root_gb) {
 extern "C" int hmsg_read_json_numbers(const char* path, const char* key, double* out, int64_t capacity, int64_t* n) {
     if (!path || !key || !n || capacity < 0 || (capacity > 0 && !out)) return HMSG_ERR_INVALID;
     *n = 0;
-    FILE* f = fopen(path, "rb");
-    if (!f) return HMSG_ERR_INVALID;
-    std::string txt;
-    char buf[1 << 16];
-    size_t got;
-    while ((got = fread(buf, 1, sizeof(buf), f)) > 0) txt.append(buf, got);
-    fclose(f);
-    const std::string pat = std::string("\"") + key + "\":";
-    size_t at = txt.find(pat);
-    if (at == std::string::npos) return HMSG_ERR_INVALID;
-    const char* p = txt.data() + at + pat.size();
-    const char* end = txt.data() + txt.size();
-    while (p < end && *p == ' ') ++p;
-    if (p >= end) return HMSG_ERR_INVALID;
-    int depth = 0;
-    int64_t cnt = 0;
-    do {                                                   // a scalar, or (nested) arrays of numbers
-        while (p < end && (*p == ' ' || *p == ',' || *p == '\n')) ++p;
-        if (p >= end) return HMSG_ERR_INVALID;
-        if (*p == '[') {
-            ++depth;
-            ++p;
-        } else if (*p == ']') {
-            --depth;
-            ++p;
-        } else {
-            double v;
-            if (!strncmp(p, "NaN", 3)) { v = __builtin_nan(""); p += 3; }
-            else if (!strncmp(p, "Infinity", 8)) { v = __builtin_inf(); p += 8; }
-            else if (!strncmp(p, "-Infinity", 9)) { v = -__builtin_inf(); p += 9; }
-            else {
-                char* q = nullptr;
-                v = strtod(p, &q);
-                if (q == p) return HMSG_ERR_INVALID;       // (a string, null, an object: not a number array)
-                p = q;
+    return hmsg_boundary(nullptr, -1, [&] {
+        std::unique_ptr<FILE, int (*)(FILE*)> f(fopen(path, "rb"), fclose);
+        HMSG_REQUIRE(f, HMSG_ERR_INVALID, "cannot open the file");
+        std::string txt;
+        char buf[1 << 16];
+        size_t got;
+        while ((got = fread(buf, 1, sizeof(buf), f.get())) > 0) txt.append(buf, got);
+        f.reset();
+        const std::string pat = std::string("\"") + key + "\":";
+        size_t at = txt.find(pat);
+        HMSG_REQUIRE(at != std::string::npos, HMSG_ERR_INVALID, "key not found");
+        const char* p = txt.data() + at + pat.size();
+        const char* end = txt.data() + txt.size();
+        while (p < end && *p == ' ') ++p;
+        HMSG_REQUIRE(p < end, HMSG_ERR_INVALID, "no value after the key");
+        int depth = 0;
+        int64_t cnt = 0;
+        do {                                                   // a scalar, or (nested) arrays of numbers
+            while (p < end && (*p == ' ' || *p == ',' || *p == '\n')) ++p;
+            HMSG_REQUIRE(p < end, HMSG_ERR_INVALID, "the value ends early");
+            if (*p == '[') {
+                ++depth;
+                ++p;
+            } else if (*p == ']') {
+                --depth;
+                ++p;
+            } else {
+                double v;
+                if (!strncmp(p, "NaN", 3)) { v = __builtin_nan(""); p += 3; }
+                else if (!strncmp(p, "Infinity", 8)) { v = __builtin_inf(); p += 8; }
+                else if (!strncmp(p, "-Infinity", 9)) { v = -__builtin_inf(); p += 9; }
+                else {
+                    char* q = nullptr;
+                    v = strtod(p, &q);
+                    HMSG_REQUIRE(q != p, HMSG_ERR_INVALID, "not a number array");       // (a string, null, an object)
+                    p = q;
+                }
+                if (cnt < capacity) out[cnt] = v;
+                ++cnt;
             }
-            if (cnt < capacity) out[cnt] = v;
-            ++cnt;
-        }
-    } while (depth > 0);
-    *n = cnt;
-    return HMSG_OK;
+        } while (depth > 0);
+        *n = cnt;
+    });
 }
 
 // ------------------------------------------------------------------------------------------ A9 / A11 bookkeeping (host only)
@@ -490,7 +470,7 @@ extern "C" int hmsg_assign_cameras_to_rooms(const double* dist, int64_t n_cams, 
     if (n_cams < 0 || n_rooms < 0 || !room_off || (n_cams > 0 && (!cam_height || !room_of_cam)) ||
         (n_cams > 0 && n_rooms > 0 && !dist) || ((n_cams > 0 || n_rooms > 0) && !room_imgs))
         return HMSG_ERR_INVALID;
-    try {
+    return hmsg_boundary(nullptr, -1, [&] {
         std::vector<std::vector<int32_t>> lists((size_t)n_rooms);
         for (int64_t i = 0; i < n_cams; ++i) {
             const bool inside = !(cam_height[i] < y_min || cam_height[i] > y_max);
@@ -523,10 +503,7 @@ extern "C" int hmsg_assign_cameras_to_rooms(const double* dist, int64_t n_cams, 
             for (int32_t v : lists[(size_t)r]) room_imgs[at++] = v;
         }
         room_off[n_rooms] = at;
-        return HMSG_OK;
-    } catch (const std::bad_alloc&) {
-        return HMSG_ERR_NOMEM;
-    }
+    });
 }
 
 // utils/graph_utils.py:334-352
@@ -565,7 +542,7 @@ extern "C" int hmsg_graph_edges(int32_t n_floors, int32_t n_rooms, const int32_t
         if (room_floor[r] < 0 || room_floor[r] >= n_floors) return HMSG_ERR_INVALID;
     for (int32_t o = 0; o < n_objects; ++o)
         if (obj_room[o] < -1 || obj_room[o] >= n_rooms) return HMSG_ERR_INVALID;
-    try {
+    return hmsg_boundary(nullptr, -1, [&] {
         const int64_t f0 = 1, r0 = f0 + n_floors, o0 = r0 + n_rooms, v0 = o0 + n_objects;
         std::vector<std::vector<int32_t>> rooms_of((size_t)n_floors), objs_of((size_t)n_rooms);
         for (int32_t r = 0; r < n_rooms; ++r) rooms_of[(size_t)room_floor[r]].push_back(r);
@@ -588,21 +565,19 @@ extern "C" int hmsg_graph_edges(int32_t n_floors, int32_t n_rooms, const int32_t
         }
         std::vector<int32_t> objs;
         for (int32_t v = 0; v < n_views; ++v) {
-            if (view_room[v] >= n_rooms) return HMSG_ERR_INVALID;
+            HMSG_REQUIRE(view_room[v] < n_rooms, HMSG_ERR_INVALID, "hmsg_graph_edges: view room out of range");
             if (view_room[v] >= 0) emit(r0 + view_room[v], v0 + v);
             const int64_t a = view_obj_off[v], b = view_obj_off[v + 1];
-            if (a > b || (b > a && !view_obj)) return HMSG_ERR_INVALID;
+            HMSG_REQUIRE(a <= b && (a == b || view_obj), HMSG_ERR_INVALID, "hmsg_graph_edges: bad view object list");
             objs.assign(view_obj + a, view_obj + b);
             std::sort(objs.begin(), objs.end());
             objs.erase(std::unique(objs.begin(), objs.end()), objs.end());
             for (int32_t o : objs) {
-                if (o < 0 || o >= n_objects) return HMSG_ERR_INVALID;
+                HMSG_REQUIRE(o >= 0 && o < n_objects, HMSG_ERR_INVALID, "hmsg_graph_edges: view object out of range");
                 emit(v0 + v, o0 + o);
             }
         }
         *n_edges = cnt;
-        return cnt <= capacity ? HMSG_OK : HMSG_ERR_INVALID;
-    } catch (const std::bad_alloc&) {
-        return HMSG_ERR_NOMEM;
-    }
+        HMSG_REQUIRE(cnt <= capacity, HMSG_ERR_INVALID, "hmsg_graph_edges: edges too small");
+    });
 }

@@ -9,6 +9,7 @@
 // one adjacency BIT per pair plus per-row neighbour counts.  Core components, border assignment and the
 // largest-cluster choice then work on the bit matrix (n^2/8 bytes).  The final mean adds rows in index
 // order in float32, which is what np.mean(axis=0) does on a C-contiguous [n, D] array.
+#include "hmsg_boundary.h"
 #include "hmsg_cloudops.h"
 #include "hmsg_nn.h"
 #include "hmsg_dbscan.h"
@@ -648,9 +649,7 @@ extern "C" int hmsg_test_pool_rows(int32_t device_id, int32_t K, const int32_t* 
                                    const float* table, int64_t table_rows, int32_t dim, double eps, int32_t min_samples, float* out) {
     if (K < 0 || (K > 0 && (!counts || !out)) || dim <= 0 || table_rows < 0 || !(eps > 0.0) || min_samples < 1) return HMSG_ERR_INVALID;
     if (K == 0) return HMSG_OK;
-    hipStream_t s = nullptr;
-    int rc = HMSG_OK;
-    try {
+    return hmsg_boundary("hmsg_test_pool_rows", -1, [&] {
         std::vector<int> dn((size_t)K);
         long long P = 0;
         for (int k = 0; k < K; ++k) {
@@ -666,7 +665,7 @@ extern "C" int hmsg_test_pool_rows(int32_t device_id, int32_t K, const int32_t* 
             HMSG_REQUIRE(!valid[i] || (idx[i] >= 0 && idx[i] < table_rows), HMSG_ERR_INVALID, "a valid row points outside the table");
         }
         HIP_TRY(hipSetDevice(device_id));
-        HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        ScopedStream s(hipStreamNonBlocking);
         {
             DevBuf<int> d_idx;
             DevBuf<unsigned> d_valid, scan_tmp;
@@ -686,10 +685,5 @@ extern "C" int hmsg_test_pool_rows(int32_t device_id, int32_t K, const int32_t* 
             HIP_TRY(hipMemcpyAsync(out, d_out.p, (size_t)K * dim * 4, hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
         }
-    } catch (const hmsg_error& e) {
-        fprintf(stderr, "hmsg_test_pool_rows: %s\n", e.msg.c_str());
-        rc = e.code;
-    }
-    if (s) (void)hipStreamDestroy(s);
-    return rc;
+    });
 }

@@ -15,7 +15,7 @@
 // MI355X design: the table stays in HBM as float64; all Q x C text rows are scored against ALL nodes by
 // one f64-MFMA GEMM (v_mfma_f64_16x16x4_f64), then one workgroup per query walks its candidate rooms
 // (CSR room -> nodes) and keeps an exact top-k.
-#include "hmsg_query.h"
+#include "hmsg_boundary.h"
 #include "hmsg_query_rules.h"
 
 #include <algorithm>
@@ -212,23 +212,6 @@ __global__ void k_fill_offsets(int* off, int n, int stride) {
 }
 
 namespace {
-template <typename F>
-int iguard(hmsg_index* ix, F&& fn) {
-    try {
-        HIP_TRY(hipSetDevice(ix->device));
-        fn();
-        return HMSG_OK;
-    } catch (const hmsg_error& e) {
-        ix->err = e.msg;
-        return e.code;
-    } catch (const std::exception& e) {
-        ix->err = e.what();
-        return HMSG_ERR_INVALID;
-    } catch (...) {
-        ix->err = "unknown error";
-        return HMSG_ERR_INVALID;
-    }
-}
 // S[M][N] = A[M][D] . B[N][D]^T  (B = the node table unless given)
 void gemm(hmsg_index* ix, const double* A, int M, double* S, const double* B = nullptr, long long N = -1) {
     if (!B) {
@@ -338,11 +321,12 @@ int hmsg_index_create(int32_t device_id, int32_t dim, int64_t n, const void* emb
     if (!out) return HMSG_ERR_INVALID;
     *out = nullptr;
     if (dim <= 0 || n <= 0 || !emb || !room_of_node) return HMSG_ERR_INVALID;
-    hmsg_index* ix = new hmsg_index();
-    ix->device = device_id;
-    ix->D = dim;
-    ix->N = n;
-    int rc = iguard(ix, [&] {
+    hmsg_index* ix = nullptr;
+    const int rc = hmsg_boundary("hmsg_index_create", device_id, [&] {
+        ix = new hmsg_index();
+        ix->device = device_id;
+        ix->D = dim;
+        ix->N = n;
         HIP_TRY(hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking));
         ix->E.alloc((size_t)n * dim);
         const size_t cnt = (size_t)n * dim;
@@ -384,7 +368,6 @@ int hmsg_index_create(int32_t device_id, int32_t dim, int64_t n, const void* emb
         HIP_TRY(hipStreamSynchronize(ix->stream));
     });
     if (rc != HMSG_OK) {
-        fprintf(stderr, "hmsg_index_create: %s\n", ix->err.c_str());
         delete ix;
         return rc;
     }
@@ -430,7 +413,7 @@ int hmsg_query_objects(hmsg_index_t* ix, int32_t Q, int32_t C, const float* T, c
                        const int32_t* rooms, int32_t k, int32_t use_negatives, int32_t* out_idx, int32_t* out_room,
                        double* out_score) {
     if (!ix) return HMSG_ERR_INVALID;
-    return iguard(ix, [&] {
+    return hmsg_boundary(ix, [&] {
         HMSG_REQUIRE(Q >= 0 && C >= 1 && T && qid && room_off && k >= 1 && out_idx && out_room && out_score, HMSG_ERR_INVALID,
                      "hmsg_query_objects: bad argument");
         if (Q == 0) return;
@@ -469,7 +452,7 @@ int hmsg_query_objects(hmsg_index_t* ix, int32_t Q, int32_t C, const float* T, c
 int hmsg_index_set_hierarchy(hmsg_index_t* ix, int32_t n_rooms, int32_t n_floors, const int32_t* floor_room_off, const int32_t* floor_rooms,
                              const double* room_name_emb, const int64_t* view_off, const double* view_emb, const int32_t* room_key) {
     if (!ix) return HMSG_ERR_INVALID;
-    return iguard(ix, [&] {
+    return hmsg_boundary(ix, [&] {
         const int R = n_rooms;                   // (rooms without objects included: >= the largest room id of a node + 1)
         HMSG_REQUIRE(R >= ix->n_rooms && n_floors >= 0 && (n_floors == 0 || (floor_room_off && floor_rooms)) && view_off && room_key,
                      HMSG_ERR_INVALID, "hmsg_index_set_hierarchy: bad argument");
@@ -514,7 +497,7 @@ int hmsg_query_hier(hmsg_index_t* ix, int32_t Q, int32_t C, const float* T_obj, 
                     const int32_t* floor_id, const int32_t* room_mode, int32_t k, int32_t use_negatives, int32_t max_rooms,
                     int32_t* out_sel, int32_t* out_nsel, int32_t* out_idx, int32_t* out_room, double* out_score) {
     if (!ix) return HMSG_ERR_INVALID;
-    return iguard(ix, [&] {
+    return hmsg_boundary(ix, [&] {
         HMSG_REQUIRE(ix->have_hier, HMSG_ERR_INVALID, "hmsg_query_hier: hmsg_index_set_hierarchy first");
         HMSG_REQUIRE(Q >= 0 && C >= 1 && T_obj && qid && floor_id && room_mode && k >= 1 && max_rooms >= 1 && out_sel && out_nsel && out_idx &&
                          out_room && out_score,
@@ -587,7 +570,7 @@ int hmsg_query_hier(hmsg_index_t* ix, int32_t Q, int32_t C, const float* T_obj, 
 
 int hmsg_similarity(hmsg_index_t* ix, int32_t Q, const float* T, double* S) {
     if (!ix) return HMSG_ERR_INVALID;
-    return iguard(ix, [&] {
+    return hmsg_boundary(ix, [&] {
         HMSG_REQUIRE(Q >= 0 && T && S, HMSG_ERR_INVALID, "hmsg_similarity: bad argument");
         if (Q == 0) return;
         hmsg_text_rows_to_f64(ix->stream, T, (size_t)Q * ix->D, ix->Tf, ix->T64);

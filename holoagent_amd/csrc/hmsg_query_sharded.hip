@@ -14,11 +14,12 @@
 //                negatives are on and any shard had a filtered candidate, and merges the shards' lists into the top k.
 // Each S[q][n] is the same float64 whichever GEMM kernel computed it (hmsg_query.h: hmsg_gemm_f64), so a shard's smaller table
 // scores exactly like its rows of the concatenated one.
-#include "hmsg_query.h"
+#include "hmsg_boundary.h"
 #include "hmsg_query_rules.h"
 
 #include <algorithm>
 #include <functional>
+#include <optional>
 
 // (hmsg_scene_graph.hip)
 struct hmsg_graph;
@@ -471,25 +472,6 @@ void run_sharded(std::vector<Shard>& local, const std::vector<std::string>& pre,
     out.give("hmsg_graph_query_sharded", st, G.out.p, h_out.data(), a.out_score, a.out_sel, a.out_nsel, a.out_idx, a.out_room);
 }
 
-template <typename F>
-int sh_guard(std::string* err, F&& f) {
-    try {
-        f();
-        return HMSG_OK;
-    } catch (const hmsg_error& e) {
-        *err = e.msg;
-        return e.code;
-    } catch (const std::bad_alloc&) {
-        *err = "out of host memory";
-        return HMSG_ERR_NOMEM;
-    } catch (const std::exception& e) {
-        *err = e.what();
-        return HMSG_ERR_INVALID;
-    } catch (...) {
-        *err = "unknown error";
-        return HMSG_ERR_INVALID;
-    }
-}
 // a graph as a shard: its resident index and scratch (what fails here is folded into the agreement, not thrown)
 void shard_of_graph(hmsg_graph* g, const double* names, Shard& sh, std::string& why) {
     try {
@@ -498,10 +480,8 @@ void shard_of_graph(hmsg_graph* g, const double* names, Shard& sh, std::string& 
         sh.ws = w;
         sh.ix = hmsg_graph_shard_index(g, &sh.nfr);
         sh.names = names;
-    } catch (const hmsg_error& e) {
-        why = e.msg;
-    } catch (const std::exception& e) {
-        why = e.what();
+    } catch (...) {
+        why = hmsg_current_error().msg;
     }
     if (why.empty() && !sh.ix) why = "hmsg_graph_query_sharded: no index";
 }
@@ -523,8 +503,7 @@ int hmsg_graph_query_sharded(hmsg_graph_t* g, hmsg_comm_t* c, const double* room
     const Query a{Q, C, T_obj, T_room, qid, floor_id, room_mode, k, use_negatives, max_rooms, out_sel, out_nsel, out_idx, out_room, out_score,
                   node_off, room_off, floor_off};
     std::string err;
-    const int rc = sh_guard(&err, [&] {
-        HIP_TRY(hipSetDevice(hmsg_comm_device(c)));
+    const int rc = hmsg_boundary(&err, hmsg_comm_device(c), [&] {
         std::vector<Shard> local(1);
         std::vector<std::string> pre(1);
         // (bad arguments, like every other local failure, travel in the header: the other ranks fail with this one)
@@ -533,20 +512,11 @@ int hmsg_graph_query_sharded(hmsg_graph_t* g, hmsg_comm_t* c, const double* room
         else shard_of_graph(g, room_name_emb, local[0], pre[0]);
         // (a rank without an index still takes part in the header exchange: on a stream of its own)
         hipStream_t st = local[0].ix ? local[0].ix->stream : nullptr;
-        hipStream_t own = nullptr;
-        if (!st) {
-            HIP_TRY(hipStreamCreateWithFlags(&own, hipStreamNonBlocking));
-            st = own;
-        }
+        std::optional<ScopedStream> own;
+        if (!st) st = own.emplace(hipStreamNonBlocking);
         Query b = a;
         if (!pre[0].empty()) b.Q = 0;                   // (no query array of a bad call is read)
-        try {
-            run_sharded(local, pre, hmsg_comm_world(c), hmsg_comm_rank(c), c, st, b);
-        } catch (...) {
-            if (own) (void)hipStreamDestroy(own);
-            throw;
-        }
-        if (own) (void)hipStreamDestroy(own);
+        run_sharded(local, pre, hmsg_comm_world(c), hmsg_comm_rank(c), c, st, b);
     });
     if (rc != HMSG_OK) {
         hmsg_graph_set_error(g, err);
@@ -566,9 +536,8 @@ int hmsg_graphs_query(int32_t n, hmsg_graph_t* const* graphs, const double* cons
                   node_off, room_off, floor_off};
     if (!query_args_ok(a)) return HMSG_ERR_INVALID;
     std::string err;
-    const int rc = sh_guard(&err, [&] {
-        const int dev = hmsg_graph_device(graphs[0]);
-        HIP_TRY(hipSetDevice(dev));
+    const int dev = hmsg_graph_device(graphs[0]);
+    const int rc = hmsg_boundary(&err, dev, [&] {
         std::vector<Shard> local((size_t)n);
         std::vector<std::string> pre((size_t)n);
         for (int i = 0; i < n; ++i) {

@@ -21,7 +21,7 @@
 // query application has.
 #include "hmsg_query_views.h"
 
-#include "hmsg_query.h"
+#include "hmsg_boundary.h"
 #include "hmsg_query_rules.h"
 #include "hmsg_view_project.h"
 
@@ -221,29 +221,9 @@ __global__ void __launch_bounds__(256) k_rematch_views(const double* __restrict_
     }
 }
 
-namespace {
-template <typename F>
-int vguard(hmsg_index* ix, F&& fn) {
-    try {
-        HIP_TRY(hipSetDevice(ix->device));
-        fn();
-        return HMSG_OK;
-    } catch (const hmsg_error& e) {
-        ix->err = e.msg;
-        return e.code;
-    } catch (const std::exception& e) {
-        ix->err = e.what();
-        return HMSG_ERR_INVALID;
-    } catch (...) {
-        ix->err = "unknown error";
-        return HMSG_ERR_INVALID;
-    }
-}
-}  // namespace
-
 extern "C" int hmsg_index_set_views(hmsg_index_t* ix, int64_t n_views, const int64_t* view_obj_off, const int32_t* view_objs) {
     if (!ix) return HMSG_ERR_INVALID;
-    return vguard(ix, [&] {
+    return hmsg_boundary(ix, [&] {
         HMSG_REQUIRE(n_views >= 0 && view_obj_off && view_obj_off[0] == 0, HMSG_ERR_INVALID, "hmsg_index_set_views: bad argument");
         for (int64_t v = 0; v < n_views; ++v)
             HMSG_REQUIRE(view_obj_off[v + 1] >= view_obj_off[v], HMSG_ERR_INVALID, "hmsg_index_set_views: offsets must not decrease");
@@ -264,7 +244,7 @@ extern "C" int hmsg_index_set_views(hmsg_index_t* ix, int64_t n_views, const int
 
 extern "C" int hmsg_rematch_in_views(hmsg_index_t* ix, int32_t Q, const float* T, const int32_t* view, int32_t* out_node, double* out_score) {
     if (!ix) return HMSG_ERR_INVALID;
-    return vguard(ix, [&] {
+    return hmsg_boundary(ix, [&] {
         HMSG_REQUIRE(ix->n_obj_views >= 0, HMSG_ERR_INVALID, "hmsg_rematch_in_views: hmsg_index_set_views first");
         HMSG_REQUIRE(Q >= 0 && (Q == 0 || (T && view && out_node && out_score)), HMSG_ERR_INVALID, "hmsg_rematch_in_views: bad argument");
         if (Q == 0) return;
@@ -434,11 +414,9 @@ void hmsg_view_depths(hipStream_t s, const double* d_pts, long long n_pairs, con
 extern "C" int hmsg_points_view_depths(int32_t device_id, int64_t n_pairs, const int64_t* pts_off, const double* pts, const double* pose_inv,
                                        const int32_t* wh, const double* K, double min_visible_ratio, double max_depth, double* avg_z_front,
                                        uint8_t* visible, double* mean_depth) {
-    hipStream_t s = nullptr;
-    int rc = HMSG_OK;
-    try {
+    return hmsg_boundary("hmsg_points_view_depths", -1, [&] {
         HMSG_REQUIRE(n_pairs >= 0 && (n_pairs == 0 || (pts_off && pose_inv && wh && K)), HMSG_ERR_INVALID, "hmsg_points_view_depths: bad argument");
-        if (n_pairs == 0) return HMSG_OK;
+        if (n_pairs == 0) return;
         HIP_TRY(hipSetDevice(device_id));
         std::vector<long long> seg_off((size_t)n_pairs + 1);
         std::vector<CloudSeg> segs((size_t)n_pairs);
@@ -451,7 +429,7 @@ extern "C" int hmsg_points_view_depths(int32_t device_id, int64_t n_pairs, const
         seg_off[(size_t)n_pairs] = n_pairs;
         const size_t total = (size_t)pts_off[n_pairs];
         HMSG_REQUIRE(total == 0 || pts, HMSG_ERR_INVALID, "hmsg_points_view_depths: no points");
-        HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        ScopedStream s(hipStreamNonBlocking);
         DevBuf<double> d_pts;
         const double* dp = pts;
         if (total && !hmsg_is_device_ptr(pts)) {
@@ -460,15 +438,5 @@ extern "C" int hmsg_points_view_depths(int32_t device_id, int64_t n_pairs, const
             dp = d_pts.p;
         }
         hmsg_view_depths(s, dp, n_pairs, seg_off, segs, pose_inv, wh, K, min_visible_ratio, max_depth, avg_z_front, visible, mean_depth);
-    } catch (const hmsg_error& e) {
-        fprintf(stderr, "hmsg_points_view_depths: %s\n", e.msg.c_str());
-        rc = e.code;
-    } catch (...) {
-        rc = HMSG_ERR_INVALID;
-    }
-    if (s) {
-        (void)hipStreamSynchronize(s);
-        (void)hipStreamDestroy(s);
-    }
-    return rc;
+    });
 }

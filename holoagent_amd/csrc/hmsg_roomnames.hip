@@ -13,6 +13,7 @@
 //   array).  float32 input uses the pooling's float32 Gram (v_mfma_f32_32x32x2_f32) and mean unchanged.  float64 input -- a LOADED graph
 //   holds json.load's float64 embeddings (object.py:71,88) -- has its own Gram on v_mfma_f64_16x16x4_f64 and a float64 mean.
 //   Scores against the type table are float64 sums of the exact products (a wave per row), whatever the input dtype.
+#include "hmsg_boundary.h"
 #include "hmsg_dbscan.h"
 
 #include <algorithm>
@@ -304,7 +305,7 @@ extern "C" int hmsg_denoise_feats_batch(int32_t device_id, int32_t n_sets, const
                                         int32_t dim, double eps, int32_t min_samples, void* out, int32_t* n_in_cluster) {
     if (n_sets < 0 || (n_sets > 0 && (!set_off || !feats || !out)) || dim <= 0 || !(eps > 0.0) || min_samples < 1) return HMSG_ERR_INVALID;
     if (n_sets == 0) return HMSG_OK;
-    try {
+    return hmsg_boundary("hmsg_denoise_feats_batch", -1, [&] {
         std::vector<long long> off((size_t)n_sets + 1);
         for (int k = 0; k <= n_sets; ++k) off[(size_t)k] = (long long)set_off[k] - (long long)set_off[0];
         for (int k = 0; k < n_sets; ++k)
@@ -327,9 +328,5 @@ extern "C" int hmsg_denoise_feats_batch(int32_t device_id, int32_t n_sets, const
         rn_denoise(s, X, feats_is_f64 != 0, dim, off, eps, min_samples, out_dev ? out : (void*)d_out.p, n_in_cluster);
         if (!out_dev) HIP_TRY(hipMemcpyAsync(out, d_out.p, out_bytes, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
-        return HMSG_OK;
-    } catch (const hmsg_error& e) {
-        fprintf(stderr, "hmsg_denoise_feats_batch: %s\n", e.msg.c_str());
-        return e.code;
-    }
+    });
 }

@@ -9,7 +9,7 @@
 // kernel instead of OpenCV's fixed-point one, filled external contours = components with their holes filled, Pick's
 // theorem for contourArea, a layer-synchronous watershed); this file implements exactly that restatement and the tests
 // hold the two equal pixel for pixel.  Parity with OpenCV itself is statistical.
-#include "hmsg_common.h"
+#include "hmsg_boundary.h"
 
 #include <cmath>
 
@@ -486,8 +486,7 @@ extern "C" int hmsg_segment_rooms(hmsg_t* h, double y_lo, double y_hi, double ze
                                   int32_t* out_markers, int64_t capacity, int32_t* out_rows, int32_t* out_cols, int32_t* out_n_rooms,
                                   double* out_xz_min) {
     if (!h) return HMSG_ERR_INVALID;
-    try {
-        HIP_TRY(hipSetDevice(h->cfg.device_id));
+    return hmsg_boundary(h, [&] {
         HMSG_REQUIRE(h->map_ready && out_rows && out_cols && out_n_rooms && out_xz_min && resolution > 0, HMSG_ERR_INVALID,
                      "hmsg_segment_rooms: bad argument (finalize the map first)");
         Rooms R;
@@ -519,7 +518,7 @@ extern "C" int hmsg_segment_rooms(hmsg_t* h, double y_lo, double y_hi, double ze
         out_xz_min[1] = r[2];
         *out_rows = g.rows;
         *out_cols = g.cols;
-        if (!out_markers) return HMSG_OK;                       // (size query)
+        if (!out_markers) return;                      // (size query)
         HMSG_REQUIRE(capacity >= (int64_t)g.n(), HMSG_ERR_INVALID, "hmsg_segment_rooms: out_markers too small (rows * cols needed)");
         // ---- histograms, normalise, blur, threshold into the padded images (graph.py:957-1040)
         DevBuf<double> dr;
@@ -634,9 +633,5 @@ extern "C" int hmsg_segment_rooms(hmsg_t* h, double y_lo, double y_hi, double ze
         HIP_TRY(hipMemcpyAsync(out_markers, cur, (size_t)g.n() * 4, hipMemcpyDefault, s));
         HIP_TRY(hipStreamSynchronize(s));
         *out_n_rooms = n_rooms;
-        return HMSG_OK;
-    } catch (const hmsg_error& e) {
-        h->err = e.msg;
-        return e.code;
-    }
+    });
 }

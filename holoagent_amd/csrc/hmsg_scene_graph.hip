@@ -9,7 +9,7 @@
 // so a C / C++ host builds, saves, loads and queries with four calls (tests/host_c/hmsg_host.c) and the benchmark's graph
 // assembly is no longer Python.  The KMeans fits of a storey's rooms run on host threads between hmsg_graph_begin (right
 // after hmsg_finalize_map) and hmsg_graph_finish (after hmsg_pool_instances): beside the fusion and the merge fold.
-#include "hmsg_common.h"
+#include "hmsg_boundary.h"
 #include "hmsg_dbscan.h"
 #include "hmsg_query.h"
 #include "hmsg_query_views.h"
@@ -148,22 +148,6 @@ struct hmsg_graph {
 
 namespace {
 
-template <typename F>
-int gguard(hmsg_graph* g, F&& f) {
-    try {
-        f();
-        return HMSG_OK;
-    } catch (const hmsg_error& e) {
-        g->err = e.msg;
-        return e.code;
-    } catch (const std::exception& e) {
-        g->err = e.what();
-        return HMSG_ERR_NOMEM;
-    } catch (...) {
-        g->err = "unknown error";
-        return HMSG_ERR_INVALID;
-    }
-}
 void need(int rc, hmsg_ctx* h, const char* what) {
     if (rc != HMSG_OK) throw hmsg_error{rc, std::string(what) + ": " + (h ? hmsg_last_error(h) : "failed")};
 }
@@ -935,8 +919,9 @@ int hmsg_graph_begin(hmsg_t* h, const hmsg_graph_params* prm, int32_t n_frames, 
         h->err = "hmsg_graph_begin: poses / view features missing";
         return HMSG_ERR_INVALID;
     }
-    hmsg_graph* g = new hmsg_graph();
-    const int rc = gguard(g, [&] {
+    hmsg_graph* g = nullptr;
+    const int rc = hmsg_boundary(&h->err, -1, [&] {
+        g = new hmsg_graph();
         const double t0 = now_ms();
         HMSG_REQUIRE(h->map_ready, HMSG_ERR_INVALID, "hmsg_graph_begin: finalize the map first");
         g->h = h;
@@ -979,22 +964,16 @@ int hmsg_graph_begin(hmsg_t* h, const hmsg_graph_params* prm, int32_t n_frames, 
             g->workers.emplace_back([g, t, nt, todo] {
                 try {
                     for (size_t k = (size_t)t; k < todo.size(); k += (size_t)nt) room_embed(g, g->rooms[(size_t)todo[k]]);
-                } catch (const hmsg_error& e) {
+                } catch (...) {      // (kept for hmsg_graph_finish, which joins the workers and reports it)
+                    hmsg_error e = hmsg_current_error();
                     std::lock_guard<std::mutex> lk(g->worker_mu);
-                    if (g->worker_err.empty()) g->worker_err = e.msg;
-                } catch (const std::exception& e) {
-                    std::lock_guard<std::mutex> lk(g->worker_mu);
-                    if (g->worker_err.empty()) g->worker_err = e.what();
-                } catch (...) {
-                    std::lock_guard<std::mutex> lk(g->worker_mu);
-                    if (g->worker_err.empty()) g->worker_err = "room level worker: unknown exception";
+                    if (g->worker_err.empty()) g->worker_err.swap(e.msg);
                 }
             });
         g->begun = true;
         g->t_begin_ms = now_ms() - t0;
     });
     if (rc != HMSG_OK) {
-        h->err = g->err;
         delete g;
         return rc;
     }
@@ -1004,7 +983,7 @@ int hmsg_graph_begin(hmsg_t* h, const hmsg_graph_params* prm, int32_t n_frames, 
 
 int hmsg_graph_finish(hmsg_graph_t* g, int32_t n_labels, const float* label_feats, const char* const* label_names) {
     if (!g) return HMSG_ERR_INVALID;
-    return gguard(g, [&] {
+    return hmsg_boundary(&g->err, -1, [&] {
         HMSG_REQUIRE(!g->failed, HMSG_ERR_INVALID, "hmsg_graph_finish: an earlier hmsg_graph_finish failed half way; destroy the graph and begin again");
         HMSG_REQUIRE(g->begun && !g->finished && g->h, HMSG_ERR_INVALID, "hmsg_graph_finish: hmsg_graph_begin first (once)");
         // everything that can be checked is checked before the graph is touched: a call that fails here can be repeated
@@ -1117,7 +1096,7 @@ int hmsg_graph_get_room_embeddings(const hmsg_graph_t* g, int32_t room, float* e
 /* the whole topology as one JSON text (ids, names, lists): what a test or a scripting host compares / walks */
 int hmsg_graph_to_json(const hmsg_graph_t* g, char* buf, int64_t capacity, int64_t* needed) {
     if (!g || !needed) return HMSG_ERR_INVALID;
-    try {
+    return hmsg_boundary(nullptr, -1, [&] {
         std::string s = "{\"floors\": [";
         for (size_t i = 0; i < g->floors.size(); ++i) {
             const GFloor& f = g->floors[i];
@@ -1164,21 +1143,16 @@ int hmsg_graph_to_json(const hmsg_graph_t* g, char* buf, int64_t capacity, int64
         for (size_t i = 0; i + 1 < g->edges.size(); i += 2) s += (i ? ", [" : "[") + std::to_string(g->edges[i]) + ", " + std::to_string(g->edges[i + 1]) + "]";
         s += "]}";
         *needed = (int64_t)s.size() + 1;
-        if (!buf) return HMSG_OK;
-        if (capacity < *needed) return HMSG_ERR_INVALID;
+        if (!buf) return;
+        HMSG_REQUIRE(capacity >= *needed, HMSG_ERR_INVALID, "hmsg_graph_to_json: buf too small (see *needed)");
         memcpy(buf, s.c_str(), s.size() + 1);
-        return HMSG_OK;
-    } catch (const std::exception&) {
-        return HMSG_ERR_NOMEM;
-    } catch (...) {
-        return HMSG_ERR_INVALID;
-    }
+    });
 }
 
 /* save_hmsg_graph (graph.py:1801-1824) in the reference layout: <dir>/floors, rooms, objects, views */
 int hmsg_save(hmsg_graph_t* g, const char* dir) {
     if (!g || !dir) return HMSG_ERR_INVALID;
-    return gguard(g, [&] {
+    return hmsg_boundary(&g->err, -1, [&] {
         HMSG_REQUIRE(g->finished && g->h, HMSG_ERR_INVALID, "hmsg_save: a graph built by hmsg_build_graph / hmsg_graph_finish (its clouds live in the scene handle)");
         hmsg_ctx* h = g->h;
         const std::string root = dir;
@@ -1291,8 +1265,9 @@ int hmsg_save(hmsg_graph_t* g, const char* dir) {
 int hmsg_load(const char* dir, int32_t device_id, hmsg_graph_t** out) {
     if (!dir || !out) return HMSG_ERR_INVALID;
     *out = nullptr;
-    hmsg_graph* g = new hmsg_graph();
-    const int rc = gguard(g, [&] {
+    hmsg_graph* g = nullptr;
+    const int rc = hmsg_boundary("hmsg_load", -1, [&] {
+        g = new hmsg_graph();
         const std::string root = dir;
         g->loaded = g->finished = true;
         g->device = device_id;
@@ -1438,7 +1413,6 @@ int hmsg_load(const char* dir, int32_t device_id, hmsg_graph_t** out) {
         }
     });
     if (rc != HMSG_OK) {
-        fprintf(stderr, "hmsg_load: %s\n", g->err.c_str());
         delete g;
         return rc;
     }
@@ -1516,7 +1490,7 @@ extern "C" {
 int hmsg_graph_index(hmsg_graph_t* g, const double* room_name_emb, hmsg_index_t** out) {
     if (!g || !out) return HMSG_ERR_INVALID;
     *out = nullptr;
-    return gguard(g, [&] { graph_make_index(g, room_name_emb, false, out); });
+    return hmsg_boundary(&g->err, -1, [&] { graph_make_index(g, room_name_emb, false, out); });
 }
 
 }  // extern "C"
@@ -1554,7 +1528,7 @@ int hmsg_graph_allgather_index(hmsg_graph_t* g, hmsg_comm_t* c, const double* ro
                                int64_t* floor_off) {
     if (!g || !c || !out) return HMSG_ERR_INVALID;
     *out = nullptr;
-    const int rc = gguard(g, [&] {
+    const int rc = hmsg_boundary(&g->err, -1, [&] {
         HMSG_REQUIRE(g->finished && g->h && !g->loaded, HMSG_ERR_INVALID, "hmsg_graph_allgather_index: a graph built by hmsg_graph_finish");
         HMSG_REQUIRE(!g->merged, HMSG_ERR_UNSUPPORTED, "hmsg_graph_allgather_index: not with merge_objects_graph (the merged objects are no rows of the scene's node table)");
         hmsg_ctx* h = g->h;
@@ -1669,7 +1643,7 @@ int hmsg_graph_query(hmsg_graph_t* g, const double* room_name_emb, int32_t Q, in
 int hmsg_graph_name_rooms(hmsg_graph_t* g, int32_t method, int32_t n_types, const float* type_feats, const char* const* type_names,
                           int32_t* type_of_room) {
     if (!g) return HMSG_ERR_INVALID;
-    return gguard(g, [&] {
+    return hmsg_boundary(&g->err, -1, [&] {
         HMSG_REQUIRE(g->finished && !g->failed, HMSG_ERR_INVALID, "hmsg_graph_name_rooms: the graph is not finished");
         HMSG_REQUIRE(method == HMSG_ROOM_NAMES_OBJ_EMBEDDING || method == HMSG_ROOM_NAMES_VIEW_EMBEDDING, HMSG_ERR_INVALID,
                      "hmsg_graph_name_rooms: unknown method (\"label\" asks an LLM: not on the device)");
@@ -1767,7 +1741,7 @@ int hmsg_graph_name_rooms(hmsg_graph_t* g, int32_t method, int32_t n_types, cons
 /* Graph.set_room_names (graph.py:2129-2144) */
 int hmsg_graph_set_room_names(hmsg_graph_t* g, int32_t n, const char* const* names) {
     if (!g) return HMSG_ERR_INVALID;
-    return gguard(g, [&] {
+    return hmsg_boundary(&g->err, -1, [&] {
         HMSG_REQUIRE(n == (int32_t)g->rooms.size(), HMSG_ERR_INVALID, "hmsg_graph_set_room_names: The length of room_names should be the same as the number of rooms in the graph");
         HMSG_REQUIRE(n == 0 || names, HMSG_ERR_INVALID, "hmsg_graph_set_room_names: no names");
         for (int r = 0; r < n; ++r) HMSG_REQUIRE(names[r] != nullptr, HMSG_ERR_INVALID, "hmsg_graph_set_room_names: a NULL name");
@@ -1870,7 +1844,7 @@ extern "C" {
 
 int hmsg_graph_get_views(hmsg_graph_t* g, hmsg_graph_view* out, int64_t capacity) {
     if (!g) return HMSG_ERR_INVALID;
-    return gguard(g, [&] {
+    return hmsg_boundary(&g->err, -1, [&] {
         views_ready(g, "hmsg_graph_get_views");
         HMSG_REQUIRE(capacity >= (int64_t)g->views.size() && (out || g->views.empty()), HMSG_ERR_INVALID, "hmsg_graph_get_views: capacity too small");
         const auto& lists = g->view_lists;
@@ -1888,7 +1862,7 @@ int hmsg_graph_get_views(hmsg_graph_t* g, hmsg_graph_view* out, int64_t capacity
 
 int hmsg_graph_get_view_objects(hmsg_graph_t* g, int32_t view, int32_t* obj, int64_t capacity) {
     if (!g) return HMSG_ERR_INVALID;
-    return gguard(g, [&] {
+    return hmsg_boundary(&g->err, -1, [&] {
         views_ready(g, "hmsg_graph_get_view_objects");
         HMSG_REQUIRE(view >= 0 && view < (int32_t)g->views.size(), HMSG_ERR_INVALID, "hmsg_graph_get_view_objects: view index out of range");
         const auto& l = g->view_lists[(size_t)view];
@@ -1901,7 +1875,7 @@ int hmsg_graph_get_view_objects(hmsg_graph_t* g, int32_t view, int32_t* obj, int
 int hmsg_graph_find_view(hmsg_graph_t* g, const char* img_path, int64_t img_id, int32_t* view) {
     if (!g || !view) return HMSG_ERR_INVALID;
     *view = -1;
-    return gguard(g, [&] {
+    return hmsg_boundary(&g->err, -1, [&] {
         views_ready(g, "hmsg_graph_find_view");
         for (size_t v = 0; v < g->views.size(); ++v) {
             const GView& w = g->views[v];
@@ -1916,7 +1890,7 @@ int hmsg_graph_find_view(hmsg_graph_t* g, const char* img_path, int64_t img_id, 
 /* graph.py:2759-2765 and :2828-2831: best_object.best_view_id -> the view that carries it -> its img_id */
 int hmsg_graph_object_best_views(hmsg_graph_t* g, int32_t n, const int32_t* obj, int32_t* view, int64_t* img_id) {
     if (!g) return HMSG_ERR_INVALID;
-    return gguard(g, [&] {
+    return hmsg_boundary(&g->err, -1, [&] {
         views_ready(g, "hmsg_graph_object_best_views");
         HMSG_REQUIRE(n >= 0 && (n == 0 || (obj && view)), HMSG_ERR_INVALID, "hmsg_graph_object_best_views: bad argument");
         for (int i = 0; i < n; ++i) HMSG_REQUIRE(obj[i] >= 0 && obj[i] < (int32_t)g->objects.size(), HMSG_ERR_INVALID, "hmsg_graph_object_best_views: object index out of range");
@@ -1932,7 +1906,7 @@ int hmsg_graph_object_best_views(hmsg_graph_t* g, int32_t n, const int32_t* obj,
 int hmsg_graph_goal_views(hmsg_graph_t* g, int32_t Q, const float* T, const int32_t* floor_id, int32_t k, int64_t* out_img, int32_t* out_room,
                           double* out_score, int32_t* out_n) {
     if (!g) return HMSG_ERR_INVALID;
-    return gguard(g, [&] {
+    return hmsg_boundary(&g->err, -1, [&] {
         views_ready(g, "hmsg_graph_goal_views");
         HMSG_REQUIRE(Q >= 0 && k >= 1 && (Q == 0 || (T && floor_id && out_img && out_room && out_score && out_n)), HMSG_ERR_INVALID,
                      "hmsg_graph_goal_views: bad argument");
@@ -1958,7 +1932,7 @@ int hmsg_graph_goal_views(hmsg_graph_t* g, int32_t Q, const float* T, const int3
 int hmsg_graph_rematch_in_views(hmsg_graph_t* g, int32_t Q, const float* T, const int32_t* view, const double* pose_inv, const int32_t* wh,
                                 const double* K, int32_t* out_obj, double* out_score, double* out_avg_distance) {
     if (!g) return HMSG_ERR_INVALID;
-    return gguard(g, [&] {
+    return hmsg_boundary(&g->err, -1, [&] {
         views_ready(g, "hmsg_graph_rematch_in_views");
         HMSG_REQUIRE(Q >= 0 && (Q == 0 || (T && view && out_obj && out_score)) && (!pose_inv || (wh && K && out_avg_distance)), HMSG_ERR_INVALID,
                      "hmsg_graph_rematch_in_views: bad argument");
@@ -1999,7 +1973,7 @@ int hmsg_graph_rematch_in_views(hmsg_graph_t* g, int32_t Q, const float* T, cons
 int hmsg_graph_object_view_depths(hmsg_graph_t* g, int32_t n, const int32_t* obj, const double* view_pose_inv, const int32_t* wh, const double* K,
                                   uint8_t* visible, double* mean_depth) {
     if (!g) return HMSG_ERR_INVALID;
-    return gguard(g, [&] {
+    return hmsg_boundary(&g->err, -1, [&] {
         views_ready(g, "hmsg_graph_object_view_depths");
         HMSG_REQUIRE(n >= 0 && (n == 0 || (obj && view_pose_inv && wh && K && visible && mean_depth)), HMSG_ERR_INVALID,
                      "hmsg_graph_object_view_depths: bad argument");

@@ -14,7 +14,7 @@
 // [digit][tile] table gives every (digit, tile) its global base; k_sort_scatter re-reads the tile, ranks equal
 // digits inside a wave with RB ballots (multi-split), adds the running per-wave digit count kept in LDS, then the
 // cross-wave prefix, and writes each pair to base + rank.
-#include "hmsg_common.h"
+#include "hmsg_boundary.h"
 
 #define SORT_IPT 16
 #define SORT_TILE (256 * SORT_IPT)
@@ -134,9 +134,8 @@ void hmsg_sort_segment_starts(const unsigned* sorted_keys, size_t n, unsigned* o
 
 // ---- test hook (include/hmsg.h: hmsg_test_sort_pairs) ------------------------------------------------------
 extern "C" int hmsg_test_sort_pairs(uint32_t* keys, uint64_t* vals, int64_t n, int32_t key_bits) {
-    try {
-        hipStream_t s = nullptr;
-        HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    return hmsg_boundary("hmsg_test_sort_pairs", -1, [&] {
+        ScopedStream s(hipStreamNonBlocking);
         {
             SortBufs b;
             b.keys.alloc((size_t)std::max<int64_t>(n, 1));
@@ -148,12 +147,7 @@ extern "C" int hmsg_test_sort_pairs(uint32_t* keys, uint64_t* vals, int64_t n, i
             HIP_TRY(hipMemcpyAsync(vals, b.res_vals, (size_t)n * 8, hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
         }
-        (void)hipStreamDestroy(s);
-        return HMSG_OK;
-    } catch (const hmsg_error& e) {
-        fprintf(stderr, "hmsg_test_sort_pairs: %s\n", e.msg.c_str());
-        return e.code;
-    }
+    });
 }
 
 // ---- test hook: repeat_add (hmsg_common.h) against the plain loop it replaces ------------------------------
@@ -163,8 +157,8 @@ __global__ void k_test_repeat_add(const double* __restrict__ s, const double* __
     if (i < n) out[i] = repeat_add(s[i], p[i], len[i]);
 }
 extern "C" int hmsg_test_repeat_add(const double* s, const double* p, const int32_t* len, double* out, int64_t n) {
-    try {
-        if (n <= 0) return HMSG_OK;
+    return hmsg_boundary("hmsg_test_repeat_add", -1, [&] {
+        if (n <= 0) return;
         DevBuf<double> ds, dp, dout;
         DevBuf<int> dl;
         ds.alloc((size_t)n); dp.alloc((size_t)n); dout.alloc((size_t)n); dl.alloc((size_t)n);
@@ -176,9 +170,5 @@ extern "C" int hmsg_test_repeat_add(const double* s, const double* p, const int3
         HMSG_CHECK_LAUNCH();
         HIP_TRY(hipDeviceSynchronize());
         HIP_TRY(hipMemcpy(out, dout.p, (size_t)n * 8, hipMemcpyDeviceToHost));
-        return HMSG_OK;
-    } catch (const hmsg_error& e) {
-        fprintf(stderr, "hmsg_test_repeat_add: %s\n", e.msg.c_str());
-        return e.code;
-    }
+    });
 }

@@ -20,6 +20,7 @@
 //   k_sp_depth             depth = uint16(float32(z * depth_factor)) of the winner
 // All of it is HBM / latency bound integer and compare work (no MFMA); per frame the traffic is ~50 B per point and
 // ~40 B per pixel.
+#include "hmsg_boundary.h"
 #include "hmsg_cloudops.h"
 
 #include <cmath>
@@ -279,14 +280,9 @@ extern "C" int hmsg_lidar_depth(int32_t device_id, const hmsg_depth_params* prm,
     const unsigned HW = (unsigned)(W * H);
     const int ksize = std::max(1, 4 / prm->image_scale), a = ksize / 2;
     const int lo = 4 * a, hi = 4 * (ksize - 1 - a);
-    hipStream_t s = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    int rc = HMSG_OK;
-    try {
-        HIP_TRY(hipSetDevice(device_id));
-        HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreate(&ev0));
-        HIP_TRY(hipEventCreate(&ev1));
+    return hmsg_boundary("hmsg_lidar_depth", device_id, [&] {
+        ScopedStream s(hipStreamNonBlocking);
+        ScopedEvent ev0, ev1;
         double total_ms = 0.0;
         {
             CloudOps ops;
@@ -431,12 +427,5 @@ extern "C" int hmsg_lidar_depth(int32_t device_id, const hmsg_depth_params* prm,
             }
         }
         if (device_ms) *device_ms = total_ms;
-    } catch (const hmsg_error& e) {
-        fprintf(stderr, "hmsg_lidar_depth: %s\n", e.msg.c_str());
-        rc = e.code;
-    }
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    if (s) (void)hipStreamDestroy(s);
-    return rc;
+    });
 }

@@ -5,7 +5,7 @@
 // per frame, depth = z of the first hit + Gaussian sensor noise, u16 millimetres.
 //   masks 0..n_ent-1 : silhouettes of the room's entities (its objects, then its 6 faces)
 //   masks n_ent..M-1 : pseudo-random rectangular tiles (overlaps allowed)
-#include "hmsg_common.h"
+#include "hmsg_boundary.h"
 
 #include <algorithm>
 
@@ -104,8 +104,7 @@ extern "C" int hmsg_synth_render(int32_t device_id, int32_t n_frames, int32_t H,
                                  const double* poses, const int32_t* room_of_frame, int32_t n_rooms, const double* room_boxes,
                                  int32_t n_obj, const double* obj_boxes, const int32_t* room_obj_off, double depth_noise_mm,
                                  uint64_t seed, uint8_t* rgb_dev, uint16_t* depth_dev, uint8_t* masks_dev, int32_t* mask_entity_host) {
-    try {
-        HIP_TRY(hipSetDevice(device_id));
+    return hmsg_boundary("hmsg_synth_render", device_id, [&] {
         DevBuf<double> dp, drb, dob;
         DevBuf<int> drf, doff, dme;
         dp.alloc((size_t)n_frames * 16);
@@ -127,9 +126,5 @@ extern "C" int hmsg_synth_render(int32_t device_id, int32_t n_frames, int32_t H,
         HMSG_CHECK_LAUNCH();
         HIP_TRY(hipDeviceSynchronize());
         HIP_TRY(hipMemcpy(mask_entity_host, dme.p, (size_t)n_frames * M * 4, hipMemcpyDeviceToHost));
-        return HMSG_OK;
-    } catch (const hmsg_error& e) {
-        fprintf(stderr, "hmsg_synth_render: %s\n", e.msg.c_str());
-        return e.code;
-    }
+    });
 }

@@ -33,6 +33,9 @@ enum {
     HMSG_ERR_UNSUPPORTED = -3, /* configuration outside what this build implements */
     HMSG_ERR_NOMEM = -4
 };
+/* What a failure inside the library becomes at this boundary (csrc/hmsg_boundary.h; no exception leaves an exported function):
+ * the library's own errors keep their code and message; running out of host memory (std::bad_alloc) is HMSG_ERR_NOMEM, "out of
+ * host memory"; any other C++ exception is HMSG_ERR_INVALID with its what(); anything else HMSG_ERR_INVALID, "unknown error". */
 
 enum { HMSG_MERGE_SEQUENTIAL = 0, HMSG_MERGE_HIERARCHICAL = 1 };
 

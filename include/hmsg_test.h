@@ -42,6 +42,11 @@ int hmsg_test_repeat_add(const double* s, const double* p, const int32_t* len, d
 int hmsg_test_ckdtree(const double* pts, int64_t n, const double* queries, int64_t nq, int64_t* out_idx,
                       int64_t* out_indices, int64_t* out_n_nodes);
 
+/* the C-boundary guard (csrc/hmsg_boundary.h) on a body that, by kind: 0 returns, 1 throws the library's own error
+ * {HMSG_ERR_UNSUPPORTED, "x"}, 2 std::bad_alloc, 3 std::length_error("y"), 4 an int.  Returns the guard's status; the message it
+ * kept is copied into msg (capacity cap).  No GPU involved. */
+int hmsg_test_boundary(int32_t kind, char* msg, int64_t cap);
+
 /* test hook: the part of hmsg_pool_instances behind the nearest-voxel step (graph.py:462-491 with feats_denoise_dbscan,
  * utils/graph_utils.py:682-728) on host arrays.  K instances; counts[k] down-sampled points of instance k, concatenated in
  * idx / valid: idx[i] is the row of table ([table_rows][dim] float32) point i snapped to, valid[i] != 0 keeps the point.
