@@ -66,11 +66,6 @@ bool hmsg_resolve_ties(hmsg_ctx* h, TieBuf& tb, int* target) {
 
 namespace {
 
-void copy_in(void* dst, const void* src, size_t bytes, hipStream_t s) {
-    if (!bytes) return;
-    HIP_TRY(hipMemcpyAsync(dst, src, bytes, hmsg_is_device_ptr(src) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-}
-
 // A long episode's frame store (colour, depth, mask bitsets, nearest-voxel indices: 17 B per pixel and frame, 157 GB for
 // 10 000 frames at 1280x720) is dead weight once every frame is fused: nothing after the fusion reads it, and the merge
 // needs the room.  Small stores stay (a service that rebuilds scenes reuses them).
@@ -299,11 +294,7 @@ int hmsg_add_frames(hmsg_t* h, int32_t n, const uint8_t* rgb, const uint16_t* de
         HMSG_REQUIRE(!h->map_ready, HMSG_ERR_INVALID, "hmsg_add_frames after hmsg_finalize_map");
         HMSG_REQUIRE(!h->frames_released, HMSG_ERR_INVALID, "hmsg_add_frames: the frame store was released (hmsg_reset first)");
         double Kh[9];
-        if (hmsg_is_device_ptr(K)) {
-            HIP_TRY(hipMemcpy(Kh, K, sizeof(Kh), hipMemcpyDeviceToHost));
-        } else {
-            memcpy(Kh, K, sizeof(Kh));
-        }
+        read_in(Kh, K, sizeof(Kh));
         if (h->have_K)
             HMSG_REQUIRE(memcmp(Kh, h->K, sizeof(Kh)) == 0, HMSG_ERR_UNSUPPORTED, "intrinsics must be the same for all frames");
         memcpy(h->K, Kh, sizeof(Kh));
@@ -314,9 +305,9 @@ int hmsg_add_frames(hmsg_t* h, int32_t n, const uint8_t* rgb, const uint16_t* de
         int kept = 0;
         if (skip == 1) {
             HMSG_REQUIRE(h->n_frames + n <= h->cfg.max_frames, HMSG_ERR_INVALID, "frame store full (cfg.max_frames)");
-            copy_in(h->rgb.p + (size_t)h->n_frames * HW * 3, rgb, (size_t)n * HW * 3, h->stream);
-            copy_in(h->depth.p + (size_t)h->n_frames * HW, depth, (size_t)n * HW * 2, h->stream);
-            copy_in(h->pose.p + (size_t)h->n_frames * 16, pose, (size_t)n * 16 * 8, h->stream);
+            copy_in(h->rgb.p + (size_t)h->n_frames * HW * 3, rgb, (size_t)n * HW * 3, h->stream, Up::direct);
+            copy_in(h->depth.p + (size_t)h->n_frames * HW, depth, (size_t)n * HW * 2, h->stream, Up::direct);
+            copy_in(h->pose.p + (size_t)h->n_frames * 16, pose, (size_t)n * 16 * 8, h->stream, Up::direct);
             kept = n;
         } else {
             // graph.py:339 / :373 `range(0, len(dataset), skip_frames)`: the k-th frame OFFERED (counted across calls) is kept
@@ -325,9 +316,9 @@ int hmsg_add_frames(hmsg_t* h, int32_t n, const uint8_t* rgb, const uint16_t* de
                 if ((h->n_offered + i) % skip != 0) continue;
                 HMSG_REQUIRE(h->n_frames + kept < h->cfg.max_frames, HMSG_ERR_INVALID, "frame store full (cfg.max_frames)");
                 const size_t f = (size_t)h->n_frames + kept;
-                copy_in(h->rgb.p + f * HW * 3, rgb + (size_t)i * HW * 3, HW * 3, h->stream);
-                copy_in(h->depth.p + f * HW, depth + (size_t)i * HW, HW * 2, h->stream);
-                copy_in(h->pose.p + f * 16, pose + (size_t)i * 16, 16 * 8, h->stream);
+                copy_in(h->rgb.p + f * HW * 3, rgb + (size_t)i * HW * 3, HW * 3, h->stream, Up::direct);
+                copy_in(h->depth.p + f * HW, depth + (size_t)i * HW, HW * 2, h->stream, Up::direct);
+                copy_in(h->pose.p + f * 16, pose + (size_t)i * 16, 16 * 8, h->stream, Up::direct);
                 ++kept;
             }
         }
@@ -385,11 +376,7 @@ int hmsg_add_frame_features(hmsg_t* h, int32_t first, int32_t n, int32_t M, cons
         // per-frame mask counts (host copy kept: the 3-D mask store holds nmask[f] clouds for frame f)
         std::vector<int> nm((size_t)n, M);
         if (n_masks) {
-            if (hmsg_is_device_ptr(n_masks)) {
-                HIP_TRY(hipMemcpy(nm.data(), n_masks, (size_t)n * 4, hipMemcpyDeviceToHost));
-            } else {
-                memcpy(nm.data(), n_masks, (size_t)n * 4);
-            }
+            read_in(nm.data(), n_masks, (size_t)n * 4);
             for (int v : nm) HMSG_REQUIRE(v >= 0 && v <= M, HMSG_ERR_INVALID, "n_masks[f] must be in [0, M]");
         }
         DevBuf<int> d_nm;
@@ -420,9 +407,9 @@ int hmsg_add_frame_features(hmsg_t* h, int32_t first, int32_t n, int32_t M, cons
                 float* g = st_f.p;
                 float* fm = g + (size_t)nc * D;
                 float* fc = fm + (size_t)nc * M * D;
-                copy_in(g, dg, (size_t)nc * D * 4, h->stream);
-                copy_in(fm, dfm, (size_t)nc * M * D * 4, h->stream);
-                copy_in(fc, dfc, (size_t)nc * M * D * 4, h->stream);
+                copy_in(g, dg, (size_t)nc * D * 4, h->stream, Up::direct);
+                copy_in(fm, dfm, (size_t)nc * M * D * 4, h->stream, Up::direct);
+                copy_in(fc, dfc, (size_t)nc * M * D * 4, h->stream, Up::direct);
                 dg = g;
                 dfm = fm;
                 dfc = fc;
@@ -504,9 +491,8 @@ int hmsg_get_feature_sums(const hmsg_t* hc, float* sum, uint32_t* counter) {
         const size_t n = (size_t)h->V * h->cfg.feat_dim;
         // (on the handle's own stream -- ordered behind whatever produced the sums -- and complete before the call returns:
         //  the caller's stream has no ordering against ours)
-        if (sum && n) HIP_TRY(hipMemcpyAsync(sum, h->sum.p, n * 4, hmsg_is_device_ptr(sum) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
-        if (counter && h->V)
-            HIP_TRY(hipMemcpyAsync(counter, h->cnt.p, (size_t)h->V * 4, hmsg_is_device_ptr(counter) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+        copy_out(sum, h->sum.p, n * 4, h->stream);
+        copy_out(counter, h->cnt.p, (size_t)h->V * 4, h->stream);
         HIP_TRY(hipStreamSynchronize(h->stream));
     });
 }
@@ -517,8 +503,8 @@ int hmsg_set_feature_sums(hmsg_t* h, const float* sum, const uint32_t* counter) 
         HMSG_REQUIRE(h->feats_final && sum && counter, HMSG_ERR_INVALID, "hmsg_set_feature_sums: run hmsg_fuse_frames first");
         HMSG_REQUIRE(!h->pooled, HMSG_ERR_INVALID, "hmsg_set_feature_sums after hmsg_pool_instances");
         const size_t n = (size_t)h->V * h->cfg.feat_dim;
-        copy_in(h->sum.p, sum, n * 4, h->stream);
-        copy_in(h->cnt.p, counter, (size_t)h->V * 4, h->stream);
+        copy_in(h->sum.p, sum, n * 4, h->stream, Up::direct);
+        copy_in(h->cnt.p, counter, (size_t)h->V * 4, h->stream, Up::direct);
         if (n) hipLaunchKernelGGL(k_feats_refresh, dim3(cdiv(n, 256)), dim3(256), 0, h->stream, (const float*)h->sum.p,
                                   (const unsigned*)h->cnt.p, (long long)h->V, h->cfg.feat_dim, h->feats.p);
         HMSG_CHECK_LAUNCH();

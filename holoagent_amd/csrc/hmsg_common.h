@@ -377,6 +377,62 @@ inline bool hmsg_is_device_ptr(const void* p) {
     }
     return a.type == hipMemoryTypeDevice;
 }
+// ------------------------------------------------------------------ caller arrays: host or device memory
+// Every array argument of the C ABI may live in host memory or in HBM.  An entry point says which array, on which stream and --
+// for a host array -- by which of the two upload routes; where the array lives is asked here, once per array, and the bool /
+// pointer that comes back carries the answer for a caller that needs it again.
+enum class Up { direct, bounce };      // a host array goes up by hipMemcpyAsync | by h2d_bounce (large pageable tables, see there)
+inline void upload(void* dst_dev, const void* src_host, size_t bytes, hipStream_t s, Up route) {
+    if (route == Up::bounce) h2d_bounce(dst_dev, src_host, bytes, s);
+    else if (bytes) HIP_TRY(hipMemcpyAsync(dst_dev, src_host, bytes, hipMemcpyHostToDevice, s));
+}
+// src (host or device) into a device buffer of the library's; true: src was device memory
+inline bool copy_in(void* dst_dev, const void* src, size_t bytes, hipStream_t s, Up route) {
+    if (!bytes) return false;
+    const bool dev = hmsg_is_device_ptr(src);
+    if (dev) HIP_TRY(hipMemcpyAsync(dst_dev, src, bytes, hipMemcpyDeviceToDevice, s));
+    else upload(dst_dev, src, bytes, s, route);
+    return dev;
+}
+// what a kernel reads: src itself when it is device memory, else `own` with the n elements uploaded (a buffer of exactly n;
+// grow: a scratch buffer kept across calls, sized by DevBuf::ensure)
+template <typename T>
+const T* stage_in(DevBuf<T>& own, const T* src, size_t n, hipStream_t s, Up route, bool grow = false) {
+    if (hmsg_is_device_ptr(src)) return src;
+    if (grow) own.ensure(n);
+    else own.alloc(n);
+    upload(own.p, src, n * sizeof(T), s, route);
+    return own.p;
+}
+// a device result into dst (host or device; nullptr: not asked for) on s; true: dst was device memory
+inline bool copy_out(void* dst, const void* src_dev, size_t bytes, hipStream_t s) {
+    if (!dst || !bytes) return false;
+    const bool dev = hmsg_is_device_ptr(dst);
+    HIP_TRY(hipMemcpyAsync(dst, src_dev, bytes, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+    return dev;
+}
+// where a kernel writes: dst itself when it is device memory (or nullptr), else `own` with room for n elements, which
+// unstage_out copies back to dst on s (p != dst says that dst is host memory)
+template <typename T>
+T* stage_out(DevBuf<T>& own, T* dst, size_t n) {
+    if (!dst || hmsg_is_device_ptr(dst)) return dst;
+    own.alloc(n);
+    return own.p;
+}
+template <typename T>
+void unstage_out(T* dst, const T* p, size_t n, hipStream_t s) {
+    if (p != dst) HIP_TRY(hipMemcpyAsync(dst, p, n * sizeof(T), hipMemcpyDeviceToHost, s));
+}
+// a small caller array the HOST reads (offsets, ids): into dst_host, synchronously
+inline void read_in(void* dst_host, const void* src, size_t bytes) {
+    if (hmsg_is_device_ptr(src)) HIP_TRY(hipMemcpy(dst_host, src, bytes, hipMemcpyDeviceToHost));
+    else memcpy(dst_host, src, bytes);
+}
+// ... and a small result the host made: into dst (host or device), synchronously
+inline void write_out(void* dst, const void* src_host, size_t bytes) {
+    if (hmsg_is_device_ptr(dst)) HIP_TRY(hipMemcpy(dst, src_host, bytes, hipMemcpyHostToDevice));
+    else memcpy(dst, src_host, bytes);
+}
 struct SpinWait {
     hipEvent_t ev = nullptr;
     ~SpinWait() {

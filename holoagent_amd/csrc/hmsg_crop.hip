@@ -186,29 +186,10 @@ extern "C" int hmsg_crop_resize_batch(int32_t device_id, int32_t H, int32_t W, c
         const size_t S = (size_t)out_size, crop_bytes = S * S * 3, img_bytes = (size_t)H * W * 3, seg_bytes = (size_t)M * H * W;
         DevBuf<unsigned char> d_img, d_seg, d_plain, d_masked;
         DevBuf<CropRect> d_rects;
-        const unsigned char* p_img = image;
-        const unsigned char* p_seg = segs;
-        if (!hmsg_is_device_ptr(image)) {
-            d_img.alloc(img_bytes);
-            HIP_TRY(hipMemcpyAsync(d_img.p, image, img_bytes, hipMemcpyHostToDevice, s));
-            p_img = d_img.p;
-        }
-        if (out_masked && !hmsg_is_device_ptr(segs)) {
-            d_seg.alloc(seg_bytes);
-            HIP_TRY(hipMemcpyAsync(d_seg.p, segs, seg_bytes, hipMemcpyHostToDevice, s));
-            p_seg = d_seg.p;
-        }
-        unsigned char* p_plain = out_plain;
-        unsigned char* p_masked = out_masked;
-        const bool plain_host = out_plain && !hmsg_is_device_ptr(out_plain), masked_host = out_masked && !hmsg_is_device_ptr(out_masked);
-        if (plain_host) {
-            d_plain.alloc(crop_bytes * M);
-            p_plain = d_plain.p;
-        }
-        if (masked_host) {
-            d_masked.alloc(crop_bytes * M);
-            p_masked = d_masked.p;
-        }
+        const unsigned char* p_img = stage_in(d_img, image, img_bytes, s, Up::direct);
+        const unsigned char* p_seg = out_masked ? stage_in(d_seg, segs, seg_bytes, s, Up::direct) : segs;
+        unsigned char* p_plain = stage_out(d_plain, out_plain, crop_bytes * M);
+        unsigned char* p_masked = stage_out(d_masked, out_masked, crop_bytes * M);
         d_rects.alloc(rects.size());
         HIP_TRY(hipMemcpyAsync(d_rects.p, rects.data(), rects.size() * sizeof(CropRect), hipMemcpyHostToDevice, s));
         HIP_TRY(hipEventRecord(ev0, s));
@@ -216,8 +197,8 @@ extern "C" int hmsg_crop_resize_batch(int32_t device_id, int32_t H, int32_t W, c
                            (const CropRect*)d_rects.p, out_size, p_plain, p_masked);
         HMSG_CHECK_LAUNCH();
         HIP_TRY(hipEventRecord(ev1, s));
-        if (plain_host) HIP_TRY(hipMemcpyAsync(out_plain, p_plain, crop_bytes * M, hipMemcpyDeviceToHost, s));
-        if (masked_host) HIP_TRY(hipMemcpyAsync(out_masked, p_masked, crop_bytes * M, hipMemcpyDeviceToHost, s));
+        unstage_out(out_plain, p_plain, crop_bytes * M, s);
+        unstage_out(out_masked, p_masked, crop_bytes * M, s);
         HIP_TRY(hipStreamSynchronize(s));
         float ms = 0.f;
         HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));

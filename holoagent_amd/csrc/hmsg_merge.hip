@@ -2210,13 +2210,8 @@ void hmsg_merge_tree_join_impl(hmsg_ctx* h, int n_ext, const long long* ext_size
     m.pool.alloc((size_t)std::max<long long>(total * 2, 1 << 16) * 3);
     m.poolcore.alloc((size_t)std::max<long long>(total * 2, 1 << 16));
     if (own) HIP_TRY(hipMemcpyAsync(m.pool.p, h->inst.pts.p, (size_t)own * 24, hipMemcpyDeviceToDevice, h->stream));
-    if (ext_total) {                               // (the partner's clouds: host memory, or device memory straight from a collective)
-        hipPointerAttribute_t pa;
-        memset(&pa, 0, sizeof(pa));
-        const bool on_dev = hipPointerGetAttributes(&pa, ext_pts) == hipSuccess && pa.type == hipMemoryTypeDevice;
-        if (!on_dev) (void)hipGetLastError();
-        HIP_TRY(hipMemcpyAsync(m.pool.p + (size_t)own * 3, ext_pts, (size_t)ext_total * 24, on_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
-    }
+    // (the partner's clouds: host memory, or device memory straight from a collective)
+    copy_in(m.pool.p + (size_t)own * 3, ext_pts, (size_t)ext_total * 24, h->stream, Up::direct);
     m.pool_used = total;
     const int n_own = (int)h->inst.off.size() - 1;
     std::vector<SegDesc> segs((size_t)(n_own + n_ext));
@@ -2513,11 +2508,7 @@ long long hmsg_voxel_ds(hmsg_ctx* h, const double* pts, long long n, double vs, 
     DevBuf<double> src, dst;
     src.alloc((size_t)n * 3);
     dst.alloc((size_t)n * 3);
-    hipPointerAttribute_t a;
-    memset(&a, 0, sizeof(a));
-    const bool on_dev = hipPointerGetAttributes(&a, pts) == hipSuccess && a.type == hipMemoryTypeDevice;
-    if (!on_dev) (void)hipGetLastError();
-    HIP_TRY(hipMemcpyAsync(src.p, pts, (size_t)n * 24, on_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    copy_in(src.p, pts, (size_t)n * 24, s, Up::direct);
     CloudOps ops;
     ops.s = s;
     std::vector<SegDesc> segs(1);

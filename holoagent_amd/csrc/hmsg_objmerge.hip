@@ -153,13 +153,8 @@ void hmsg_pair_overlaps(hmsg_ctx* h, const double* points, const long long* star
                 hi = std::max(hi, start[v] + count[v]);
             }
         }
-    const double* dpts = points;
-    DevBuf<double> up;
-    if (!hmsg_is_device_ptr(points)) {               // host clouds: the span the pairs touch goes up once
-        up.alloc((size_t)std::max<long long>(hi - lo, 1) * 3);
-        HIP_TRY(hipMemcpyAsync(up.p, points + (size_t)lo * 3, (size_t)(hi - lo) * 24, hipMemcpyHostToDevice, s));
-        dpts = up.p - (size_t)lo * 3;
-    }
+    DevBuf<double> up;                               // host clouds: the span the pairs touch goes up once
+    const double* dpts = stage_in(up, points + (size_t)lo * 3, (size_t)(hi - lo) * 3, s, Up::direct) - (size_t)lo * 3;
     DevBuf<OmTask> dt;
     DevBuf<unsigned> dc;
     dt.alloc(tasks.size());

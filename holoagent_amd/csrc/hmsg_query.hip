@@ -275,11 +275,7 @@ std::string hmsg_query_precondition(const char* who, const QueryScan& sc, int n_
 }
 void hmsg_text_rows_to_f64(hipStream_t s, const float* src, size_t n, DevBuf<float>& tmp, DevBuf<double>& dst) {
     dst.ensure(n);
-    if (!hmsg_is_device_ptr(src)) {
-        tmp.ensure(n);
-        h2d_bounce(tmp.p, src, n * 4, s);
-        src = tmp.p;
-    }
+    src = stage_in(tmp, src, n, s, Up::bounce, true);
     hipLaunchKernelGGL(k_f32_to_f64, dim3(cdiv(n, 256)), dim3(256), 0, s, src, dst.p, n);
     HMSG_CHECK_LAUNCH();
 }
@@ -331,23 +327,16 @@ int hmsg_index_create(int32_t device_id, int32_t dim, int64_t n, const void* emb
         ix->E.alloc((size_t)n * dim);
         const size_t cnt = (size_t)n * dim;
         if (emb_is_f64) {
-            if (hmsg_is_device_ptr(emb)) HIP_TRY(hipMemcpyAsync(ix->E.p, emb, cnt * 8, hipMemcpyDeviceToDevice, ix->stream));
-            else h2d_bounce(ix->E.p, emb, cnt * 8, ix->stream);
+            copy_in(ix->E.p, emb, cnt * 8, ix->stream, Up::bounce);
         } else {
-            DevBuf<float> tmp;
-            tmp.alloc(cnt);
-            if (hmsg_is_device_ptr(emb)) HIP_TRY(hipMemcpyAsync(tmp.p, emb, cnt * 4, hipMemcpyDeviceToDevice, ix->stream));
-            else h2d_bounce(tmp.p, emb, cnt * 4, ix->stream);
-            hipLaunchKernelGGL(k_f32_to_f64, dim3(cdiv(cnt, 256)), dim3(256), 0, ix->stream, (const float*)tmp.p, ix->E.p, cnt);
+            DevBuf<float> tmp;               // (a device table is widened straight from the caller's memory)
+            const float* e32 = stage_in(tmp, (const float*)emb, cnt, ix->stream, Up::bounce);
+            hipLaunchKernelGGL(k_f32_to_f64, dim3(cdiv(cnt, 256)), dim3(256), 0, ix->stream, e32, ix->E.p, cnt);
             HMSG_CHECK_LAUNCH();
             HIP_TRY(hipStreamSynchronize(ix->stream));
         }
         std::vector<int> rooms((size_t)n);
-        if (hmsg_is_device_ptr(room_of_node)) {
-            HIP_TRY(hipMemcpy(rooms.data(), room_of_node, (size_t)n * 4, hipMemcpyDeviceToHost));
-        } else {
-            memcpy(rooms.data(), room_of_node, (size_t)n * 4);
-        }
+        read_in(rooms.data(), room_of_node, (size_t)n * 4);
         int nr = 0;
         for (int r : rooms) {
             HMSG_REQUIRE(r >= 0, HMSG_ERR_INVALID, "negative room id");
@@ -422,11 +411,7 @@ int hmsg_query_objects(hmsg_index_t* ix, int32_t Q, int32_t C, const float* T, c
         ix->S.ensure((size_t)Q * C * ix->N);
         gemm(ix, ix->T64.p, Q * C, ix->S.p);
         std::vector<int> hoff(Q + 1);
-        if (hmsg_is_device_ptr(room_off)) {
-            HIP_TRY(hipMemcpy(hoff.data(), room_off, (size_t)(Q + 1) * 4, hipMemcpyDeviceToHost));
-        } else {
-            memcpy(hoff.data(), room_off, (size_t)(Q + 1) * 4);
-        }
+        read_in(hoff.data(), room_off, (size_t)(Q + 1) * 4);
         const int nr = hoff[Q];
         HMSG_REQUIRE(nr == 0 || rooms, HMSG_ERR_INVALID, "rooms list missing");
         ix->d_qid.ensure(Q);
@@ -435,9 +420,9 @@ int hmsg_query_objects(hmsg_index_t* ix, int32_t Q, int32_t C, const float* T, c
         ix->d_oidx.ensure((size_t)Q * k);
         ix->d_oroom.ensure((size_t)Q * k);
         ix->d_oscore.ensure((size_t)Q * k);
-        HIP_TRY(hipMemcpyAsync(ix->d_qid.p, qid, (size_t)Q * 4, hmsg_is_device_ptr(qid) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ix->stream));
+        copy_in(ix->d_qid.p, qid, (size_t)Q * 4, ix->stream, Up::direct);
         HIP_TRY(hipMemcpyAsync(ix->d_roff.p, hoff.data(), (size_t)(Q + 1) * 4, hipMemcpyHostToDevice, ix->stream));
-        if (nr) HIP_TRY(hipMemcpyAsync(ix->d_rooms.p, rooms, (size_t)nr * 4, hmsg_is_device_ptr(rooms) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ix->stream));
+        copy_in(ix->d_rooms.p, rooms, (size_t)nr * 4, ix->stream, Up::direct);
         hipLaunchKernelGGL(k_query_topk, dim3(Q), dim3(256), 0, ix->stream, (const double*)ix->S.p, ix->N, C, (const int*)ix->d_qid.p,
                            (const int*)ix->d_roff.p, (const int*)ix->d_rooms.p, (const int*)ix->room_off.p,
                            (const int*)ix->room_nodes.p, ix->n_rooms, k, use_negatives, ix->d_oidx.p, ix->d_oroom.p, ix->d_oscore.p);
@@ -478,16 +463,12 @@ int hmsg_index_set_hierarchy(hmsg_index_t* ix, int32_t n_rooms, int32_t n_floors
         if (nfr) HIP_TRY(hipMemcpyAsync(ix->floor_rooms.p, floor_rooms, (size_t)nfr * 4, hipMemcpyHostToDevice, ix->stream));
         if (room_name_emb) {
             ix->room_name_emb.alloc((size_t)std::max(R, 1) * ix->D);
-            if (hmsg_is_device_ptr(room_name_emb)) HIP_TRY(hipMemcpyAsync(ix->room_name_emb.p, room_name_emb, (size_t)R * ix->D * 8, hipMemcpyDeviceToDevice, ix->stream));
-            else h2d_bounce(ix->room_name_emb.p, room_name_emb, (size_t)R * ix->D * 8, ix->stream);
+            copy_in(ix->room_name_emb.p, room_name_emb, (size_t)R * ix->D * 8, ix->stream, Up::bounce);
         } else {
             ix->room_name_emb.release();
         }
         ix->view_emb.alloc((size_t)std::max<long long>(NV, 1) * ix->D);
-        if (NV) {
-            if (hmsg_is_device_ptr(view_emb)) HIP_TRY(hipMemcpyAsync(ix->view_emb.p, view_emb, (size_t)NV * ix->D * 8, hipMemcpyDeviceToDevice, ix->stream));
-            else h2d_bounce(ix->view_emb.p, view_emb, (size_t)NV * ix->D * 8, ix->stream);
-        }
+        copy_in(ix->view_emb.p, view_emb, (size_t)NV * ix->D * 8, ix->stream, Up::bounce);
         HIP_TRY(hipStreamSynchronize(ix->stream));
         ix->have_hier = true;
     });

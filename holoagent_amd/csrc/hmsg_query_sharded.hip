@@ -414,12 +414,7 @@ void run_sharded(std::vector<Shard>& local, const std::vector<std::string>& pre,
             const int R = ix->h_rooms, F = ix->n_floors;
             char* slot = G.room.p + (size_t)(first + i) * (size_t)lay.bytes;
             if (need_label && R) {
-                const double* names = sh.names;
-                if (!hmsg_is_device_ptr(names)) {
-                    L.names.ensure((size_t)R * D);
-                    h2d_bounce(L.names.p, names, (size_t)R * D * 8, st);
-                    names = L.names.p;
-                }
+                const double* names = stage_in(L.names, sh.names, (size_t)R * D, st, Up::bounce, true);
                 L.S_room.ensure((size_t)Q * R);
                 hmsg_gemm_f64(G.Tr64.p, Q, names, R, D, L.S_room.p, st);
                 hipLaunchKernelGGL(k_sh_pad_rows, dim3(cdiv((size_t)Q * R, 256)), dim3(256), 0, st, (const double*)L.S_room.p, Q, R, lay.Rmax,

@@ -82,14 +82,6 @@ struct hmsg_goal_table {
     DevBuf<long long> d_img;
 };
 
-namespace {
-// n bytes of a device result into the caller's array (host or device memory)
-void give(void* dst, const void* d_src, size_t n, hipStream_t s) {
-    if (!dst || !n) return;
-    HIP_TRY(hipMemcpyAsync(dst, d_src, n, hmsg_is_device_ptr(dst) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
-}
-}  // namespace
-
 hmsg_goal_table* hmsg_goal_table_create(int device, int D, int n_rooms, const std::vector<int>& img_off, const std::vector<float>& clip,
                                         const std::vector<long long>& img_id, const std::vector<int>& floor_room_off, const std::vector<int>& floor_rooms) {
     HMSG_REQUIRE(D > 0 && n_rooms >= 0 && (int)img_off.size() == n_rooms + 1 && !floor_room_off.empty(), HMSG_ERR_INVALID, "goal view table: bad argument");
@@ -166,10 +158,10 @@ void hmsg_goal_table_topk(hmsg_goal_table* t, int Q, const float* T, const int* 
                        (const int*)t->floor_room_off.p, (const int*)t->floor_rooms.p, (const int*)t->img_off.p, (const long long*)t->img_id.p, k, kk,
                        t->d_img.p, t->d_room.p, t->d_score.p, t->d_n.p);
     HMSG_CHECK_LAUNCH();
-    give(out_img, t->d_img.p, nk * 8, s);
-    give(out_room, t->d_room.p, nk * 4, s);
-    give(out_score, t->d_score.p, nk * 8, s);
-    give(out_n, t->d_n.p, (size_t)Q * 4, s);
+    copy_out(out_img, t->d_img.p, nk * 8, s);
+    copy_out(out_room, t->d_room.p, nk * 4, s);
+    copy_out(out_score, t->d_score.p, nk * 8, s);
+    copy_out(out_n, t->d_n.p, (size_t)Q * 4, s);
     HIP_TRY(hipStreamSynchronize(s));
 }
 
@@ -249,8 +241,7 @@ extern "C" int hmsg_rematch_in_views(hmsg_index_t* ix, int32_t Q, const float* T
         HMSG_REQUIRE(Q >= 0 && (Q == 0 || (T && view && out_node && out_score)), HMSG_ERR_INVALID, "hmsg_rematch_in_views: bad argument");
         if (Q == 0) return;
         std::vector<int> hv((size_t)Q);
-        if (hmsg_is_device_ptr(view)) HIP_TRY(hipMemcpy(hv.data(), view, (size_t)Q * 4, hipMemcpyDeviceToHost));
-        else memcpy(hv.data(), view, (size_t)Q * 4);
+        read_in(hv.data(), view, (size_t)Q * 4);
         for (int q = 0; q < Q; ++q)
             HMSG_REQUIRE(hv[(size_t)q] >= 0 && hv[(size_t)q] < ix->n_obj_views, HMSG_ERR_INVALID, "hmsg_rematch_in_views: view index out of range");
         hipStream_t s = ix->stream;
@@ -262,8 +253,8 @@ extern "C" int hmsg_rematch_in_views(hmsg_index_t* ix, int32_t Q, const float* T
         hipLaunchKernelGGL(k_rematch_views, dim3((unsigned)Q), dim3(256), 0, s, (const double*)ix->T64.p, (const double*)ix->E.p, ix->D,
                            (const int*)ix->d_view.p, (const long long*)ix->vo_off.p, (const int*)ix->vo_nodes.p, ix->d_vnode.p, ix->d_vscore.p);
         HMSG_CHECK_LAUNCH();
-        give(out_node, ix->d_vnode.p, (size_t)Q * 4, s);
-        give(out_score, ix->d_vscore.p, (size_t)Q * 8, s);
+        copy_out(out_node, ix->d_vnode.p, (size_t)Q * 4, s);
+        copy_out(out_score, ix->d_vscore.p, (size_t)Q * 8, s);
         HIP_TRY(hipStreamSynchronize(s));          // (hv, a pageable source, is done with by now as well)
     });
 }
@@ -431,12 +422,7 @@ extern "C" int hmsg_points_view_depths(int32_t device_id, int64_t n_pairs, const
         HMSG_REQUIRE(total == 0 || pts, HMSG_ERR_INVALID, "hmsg_points_view_depths: no points");
         ScopedStream s(hipStreamNonBlocking);
         DevBuf<double> d_pts;
-        const double* dp = pts;
-        if (total && !hmsg_is_device_ptr(pts)) {
-            d_pts.alloc(total * 3);
-            h2d_bounce(d_pts.p, pts, total * 24, s);
-            dp = d_pts.p;
-        }
+        const double* dp = total ? stage_in(d_pts, pts, total * 3, s, Up::bounce) : pts;
         hmsg_view_depths(s, dp, n_pairs, seg_off, segs, pose_inv, wh, K, min_visible_ratio, max_depth, avg_z_front, visible, mean_depth);
     });
 }

@@ -317,16 +317,10 @@ extern "C" int hmsg_denoise_feats_batch(int32_t device_id, int32_t n_sets, const
         const char* src = (const char*)feats + (size_t)set_off[0] * dim * esz;
         hipStream_t s = nullptr;
         DevBuf<char> d_in, d_out;
-        const void* X = src;
-        if (!hmsg_is_device_ptr(src)) {
-            d_in.alloc(in_bytes);
-            HIP_TRY(hipMemcpyAsync(d_in.p, src, in_bytes, hipMemcpyHostToDevice, s));
-            X = d_in.p;
-        }
-        const bool out_dev = hmsg_is_device_ptr(out);
-        if (!out_dev) d_out.alloc(out_bytes);
-        rn_denoise(s, X, feats_is_f64 != 0, dim, off, eps, min_samples, out_dev ? out : (void*)d_out.p, n_in_cluster);
-        if (!out_dev) HIP_TRY(hipMemcpyAsync(out, d_out.p, out_bytes, hipMemcpyDeviceToHost, s));
+        const char* X = stage_in(d_in, src, in_bytes, s, Up::direct);
+        char* Y = stage_out(d_out, (char*)out, out_bytes);
+        rn_denoise(s, X, feats_is_f64 != 0, dim, off, eps, min_samples, Y, n_in_cluster);
+        unstage_out((char*)out, Y, out_bytes, s);
         HIP_TRY(hipStreamSynchronize(s));
     });
 }

@@ -1964,8 +1964,7 @@ int hmsg_graph_rematch_in_views(hmsg_graph_t* g, int32_t Q, const float* T, cons
             hmsg_view_depths(s, base, Q, seg_off, segs, pose_inv, wh, K, g->prm.min_visible_ratio, g->prm.max_view_depth, out_avg_distance, nullptr,
                              nullptr);
         }
-        if (hmsg_is_device_ptr(out_obj)) HIP_TRY(hipMemcpy(out_obj, h_obj.data(), (size_t)Q * 4, hipMemcpyHostToDevice));
-        else memcpy(out_obj, h_obj.data(), (size_t)Q * 4);
+        write_out(out_obj, h_obj.data(), (size_t)Q * 4);
     });
 }
 
