@@ -54,7 +54,7 @@ class HmsgJsonField(C.Structure):      # include/hmsg.h: hmsg_json_field
 class HmsgGraphParams(C.Structure):    # include/hmsg.h: hmsg_graph_params
     _fields_ = [("num_views", C.c_int32), ("kmeans_n_init", C.c_int32), ("kmeans_max_iter", C.c_int32), ("kmeans_seed", C.c_uint32),
                 ("skip_frames", C.c_int32), ("image_width", C.c_int32), ("image_height", C.c_int32), ("min_visible_ratio", C.c_double),
-                ("max_view_depth", C.c_double), ("host_threads", C.c_int32), ("merge_objects_graph", C.c_int32), ("reserved_", C.c_int32)]
+                ("max_view_depth", C.c_double), ("host_threads", C.c_int32), ("merge_objects_graph", C.c_int32), ("kmeans_device", C.c_int32)]
 
 
 class HmsgGraphCounts(C.Structure):    # include/hmsg.h: hmsg_graph_counts
@@ -161,6 +161,8 @@ _SIGS = {
     "hmsg_graph_set_room_names": (C.c_int, [_P, C.c_int32, _P]),
     "hmsg_denoise_feats_batch": (C.c_int, [C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_double, C.c_int32, _P, _P]),
     "hmsg_kmeans": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, _P, _P, _P, _P]),
+    "hmsg_kmeans_batch": (C.c_int, [C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, _P, _P, _P, _P]),
+    "hmsg_test_kmeans_lloyd": (C.c_int, [C.c_int32, C.c_int32, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "hmsg_room_camera_distances": (C.c_int, [_P, C.c_int32, C.c_int64, _P, _P]),
     "hmsg_object_views": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int64, _P, _P, C.c_double, C.c_double, _P, _P]),
     "hmsg_segment_floors": (C.c_int, [_P, _P, C.c_int32, C.POINTER(C.c_int32)]),
@@ -752,7 +754,8 @@ class SceneGraph:
 
     @classmethod
     def begin(cls, scene: "Scene", poses, view_feats, poses_inv=None, img_paths=None, **params):
-        """the room level right after hmsg_finalize_map (device stage now, KMeans on host threads); finish() after the pooling"""
+        """the room level right after hmsg_finalize_map (device stage now, KMeans on host threads -- kmeans_device=1: in one batched
+        call per storey on the device); finish() after the pooling"""
         L = scene.L
         P_ = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 16))
         Pi = None if poses_inv is None else np.ascontiguousarray(np.asarray(poses_inv, np.float64).reshape(-1, 16))
@@ -1222,6 +1225,41 @@ def kmeans(X, n_clusters, n_init=5, max_iter=100, seed=0, lib_: "HmsgLib | None"
     if rc != 0:
         raise HmsgError(f"hmsg_kmeans failed ({rc})")
     return labels, centers, float(inertia.value), int(n_iter.value)
+
+
+def kmeans_batch(sets, n_clusters, n_init=5, max_iter=100, seed=0, lib_: "HmsgLib | None" = None):
+    """hmsg_kmeans for several independent sets in one call, on the device (include/hmsg.h: hmsg_kmeans_batch): the bits of
+    kmeans(set, ...) per set.  `sets`: float32 arrays [n_s, D], or torch tensors on the device (the results are device tensors
+    then).  Returns a list of (labels i32 [n_s], centers f32 [k, D], inertia, n_iter), one per set."""
+    L = lib_ or lib()
+    sets = list(sets)
+    if not sets:
+        return []
+    k = int(n_clusters)
+    on_dev = all(hasattr(x, "data_ptr") and getattr(x, "is_cuda", False) for x in sets)
+    if on_dev:
+        import torch
+        dev = sets[0].device
+        X = torch.cat([x.to(torch.float32).reshape(x.shape[0], -1) for x in sets], 0).contiguous()
+        D, device_id = int(X.shape[1]), dev.index or 0
+        sizes = [int(x.shape[0]) for x in sets]
+        labels = torch.empty(sum(sizes), dtype=torch.int32, device=dev)
+        centers = torch.empty((len(sets), k, D), dtype=torch.float32, device=dev)
+    else:
+        rows = [np.ascontiguousarray(np.asarray(x.cpu() if hasattr(x, "cpu") else x, np.float32)) for x in sets]
+        rows = [x.reshape(x.shape[0], -1) for x in rows]
+        X = np.ascontiguousarray(np.concatenate(rows, 0))
+        D, device_id = int(X.shape[1]), 0
+        sizes = [int(x.shape[0]) for x in rows]
+        labels = np.empty(sum(sizes), np.int32)
+        centers = np.empty((len(sets), k, D), np.float32)
+    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    inertia, n_iter = np.zeros(len(sets), np.float32), np.zeros(len(sets), np.int32)
+    rc = L.c.hmsg_kmeans_batch(device_id, len(sets), _ptr(off), _ptr(X), D, k, int(n_init), int(max_iter), int(seed), _ptr(labels),
+                               _ptr(centers), _ptr(inertia), _ptr(n_iter))
+    if rc != 0:
+        raise HmsgError(f"hmsg_kmeans_batch failed ({rc})")
+    return [(labels[off[s]:off[s + 1]], centers[s], float(inertia[s]), int(n_iter[s])) for s in range(len(sets))]
 
 
 def pick_representative_views(embs, labels, centers, lib_: "HmsgLib | None" = None):

@@ -319,6 +319,16 @@ bool same_clustering(const std::vector<int>& a, const std::vector<int>& b, int k
 
 }  // namespace
 
+// hmsg_kmeans_device.hip: the device restatement draws its random numbers here and is tested against one iteration of lloyd_iter
+void hmsg_kmeans_host_lloyd(const float* X, int n, int D, int k, const float* centers_old, float* centers_new, float* weight, int* labels,
+                            float* center_shift) {
+    lloyd_iter(X, n, D, k, centers_old, centers_new, weight, labels, center_shift, true);
+}
+void hmsg_kmeans_draws(uint32_t seed, size_t count, double* out) {
+    MT19937 rs(seed);
+    for (size_t i = 0; i < count; ++i) out[i] = rs.next_double();
+}
+
 /* include/hmsg.h: hmsg_kmeans */
 extern "C" int hmsg_kmeans(const float* X_in, int64_t n64, int32_t D, int32_t k, int32_t n_init, int32_t max_iter, uint32_t seed,
                            int32_t* out_labels, float* out_centers, float* out_inertia, int32_t* out_n_iter) {

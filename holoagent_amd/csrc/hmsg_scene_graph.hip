@@ -7,8 +7,9 @@
 // hmsg_build_object_nodes, hmsg_object_views, hmsg_graph_edges, hmsg_write_json / _ply, hmsg_save_objects); what the Python
 // mirror holoagent_amd/graph.py did between them -- ids, names, lists, the bookkeeping of views and objects -- is host C++ here,
 // so a C / C++ host builds, saves, loads and queries with four calls (tests/host_c/hmsg_host.c) and the benchmark's graph
-// assembly is no longer Python.  The KMeans fits of a storey's rooms run on host threads between hmsg_graph_begin (right
-// after hmsg_finalize_map) and hmsg_graph_finish (after hmsg_pool_instances): beside the fusion and the merge fold.
+// assembly is no longer Python.  The KMeans fits of a storey's rooms run on host threads (or, hmsg_graph_params::kmeans_device,
+// as one batch per storey on the device) between hmsg_graph_begin (right after hmsg_finalize_map) and hmsg_graph_finish (after
+// hmsg_pool_instances): beside the fusion and the merge fold.
 #include "hmsg_boundary.h"
 #include "hmsg_dbscan.h"
 #include "hmsg_query.h"
@@ -340,8 +341,10 @@ void room_level_prepare(hmsg_graph* g, int fi) {
     for (int i = 0; i < nr; ++i) g->rooms[room0 + (size_t)i].imgs.assign(imgs.begin() + roff[(size_t)i], imgs.begin() + roff[(size_t)i + 1]);
 }
 
-// ---- stage 2 (host only): KMeans(num_views) over a room's image embeddings + the representative picks (:329-352)
-void room_embed(hmsg_graph* g, GRoom& rm) {
+// ---- stage 2: KMeans(num_views) over a room's image embeddings + the representative picks (:329-352).  The fit is hmsg_kmeans on a
+// host thread per room, or -- hmsg_graph_params::kmeans_device -- one hmsg_kmeans_batch call per storey on the device (the same bits)
+// the rows to cluster; false: fewer images than num_views, every image represents the room (:297-301) and the room is done
+bool room_rows(hmsg_graph* g, GRoom& rm) {
     const int D = g->D, n = (int)rm.imgs.size(), nv = g->prm.num_views, skip = std::max(1, g->prm.skip_frames);
     rm.clip.resize((size_t)n * D);
     for (int i = 0; i < n; ++i) memcpy(&rm.clip[(size_t)i * D], &g->feats[(size_t)rm.imgs[(size_t)i] * D], (size_t)D * 4);
@@ -349,17 +352,18 @@ void room_embed(hmsg_graph* g, GRoom& rm) {
     rm.sample.clear();
     for (int v : rm.imgs) rm.sample.push_back((long long)v * skip);
     rm.represent.clear();
-    if (n < nv) {                                          // (:297-301: every image represents the room)
+    if (n < nv) {
         rm.emb = rm.clip;
         rm.n_emb = n;
         for (int v : rm.imgs) rm.represent.push_back((long long)v * skip);
-        return;
+        return false;
     }
     rm.km_labels.resize((size_t)n);
     rm.km_centers.resize((size_t)nv * D);
-    const int rc = hmsg_kmeans(rm.clip.data(), n, D, nv, g->prm.kmeans_n_init, g->prm.kmeans_max_iter, g->prm.kmeans_seed, rm.km_labels.data(),
-                               rm.km_centers.data(), nullptr, nullptr);
-    if (rc != HMSG_OK) throw hmsg_error{rc, "hmsg_kmeans failed"};
+    return true;
+}
+void room_pick(hmsg_graph* g, GRoom& rm) {
+    const int D = g->D, n = (int)rm.imgs.size(), nv = g->prm.num_views, skip = std::max(1, g->prm.skip_frames);
     std::vector<int32_t> member((size_t)nv);
     int32_t nm = 0;
     if (hmsg_pick_representative_views(rm.clip.data(), n, D, rm.km_labels.data(), rm.km_centers.data(), nv, member.data(), &nm) != HMSG_OK)
@@ -369,6 +373,37 @@ void room_embed(hmsg_graph* g, GRoom& rm) {
     for (int k = 0; k < nm; ++k) {
         memcpy(&rm.emb[(size_t)k * D], &rm.clip[(size_t)member[(size_t)k] * D], (size_t)D * 4);
         rm.represent.push_back((long long)rm.imgs[(size_t)member[(size_t)k]] * skip);
+    }
+}
+void room_embed(hmsg_graph* g, GRoom& rm) {
+    if (!room_rows(g, rm)) return;
+    const int rc = hmsg_kmeans(rm.clip.data(), (int)rm.imgs.size(), g->D, g->prm.num_views, g->prm.kmeans_n_init, g->prm.kmeans_max_iter,
+                               g->prm.kmeans_seed, rm.km_labels.data(), rm.km_centers.data(), nullptr, nullptr);
+    if (rc != HMSG_OK) throw hmsg_error{rc, "hmsg_kmeans failed"};
+    room_pick(g, rm);
+}
+// the rooms of one storey that have at least num_views images: one hmsg_kmeans_batch call
+void storey_embed_device(hmsg_graph* g, const GFloor& fl) {
+    const int D = g->D, nv = g->prm.num_views;
+    std::vector<int> fit;
+    std::vector<int64_t> off(1, 0);
+    for (int r : fl.rooms)
+        if (room_rows(g, g->rooms[(size_t)r])) {
+            fit.push_back(r);
+            off.push_back(off.back() + (int64_t)g->rooms[(size_t)r].imgs.size());
+        }
+    if (fit.empty()) return;
+    std::vector<float> X((size_t)off.back() * D), centers(fit.size() * (size_t)nv * D);
+    std::vector<int32_t> labels((size_t)off.back());
+    for (size_t i = 0; i < fit.size(); ++i) memcpy(&X[(size_t)off[i] * D], g->rooms[(size_t)fit[i]].clip.data(), (size_t)(off[i + 1] - off[i]) * D * 4);
+    const int rc = hmsg_kmeans_batch(g->device, (int32_t)fit.size(), off.data(), X.data(), D, nv, g->prm.kmeans_n_init, g->prm.kmeans_max_iter,
+                                     g->prm.kmeans_seed, labels.data(), centers.data(), nullptr, nullptr);
+    if (rc != HMSG_OK) throw hmsg_error{rc, "hmsg_kmeans_batch failed"};
+    for (size_t i = 0; i < fit.size(); ++i) {
+        GRoom& rm = g->rooms[(size_t)fit[i]];
+        rm.km_labels.assign(labels.begin() + (ptrdiff_t)off[i], labels.begin() + (ptrdiff_t)off[i + 1]);
+        rm.km_centers.assign(centers.begin() + (ptrdiff_t)(i * (size_t)nv * D), centers.begin() + (ptrdiff_t)((i + 1) * (size_t)nv * D));
+        room_pick(g, rm);
     }
 }
 
@@ -905,6 +940,7 @@ void hmsg_graph_default_params(hmsg_graph_params* p) {
     p->max_view_depth = 10.0;
     p->host_threads = 0;
     p->merge_objects_graph = 0;     /* false in every shipped config */
+    p->kmeans_device = 0;           /* the fits on host threads */
 }
 
 const char* hmsg_graph_last_error(const hmsg_graph_t* g) { return g ? g->err.c_str() : "null graph"; }
@@ -955,7 +991,24 @@ int hmsg_graph_begin(hmsg_t* h, const hmsg_graph_params* prm, int32_t n_frames, 
         }
         // the room level's device stage, storey by storey
         for (int i = 0; i < nf; ++i) room_level_prepare(g, i);
-        // its host stage on worker threads: the rooms are independent fits
+        // its second stage on worker threads: the rooms are independent fits
+        if (g->prm.kmeans_device) {
+            // one worker, so that begin returns before the fits are done; what its allocator cache holds goes back to the driver when
+            // it ends (the cache belongs to the thread)
+            g->workers.emplace_back([g] {
+                try {
+                    for (const GFloor& fl : g->floors) storey_embed_device(g, fl);
+                } catch (...) {
+                    hmsg_error e = hmsg_current_error();
+                    std::lock_guard<std::mutex> lk(g->worker_mu);
+                    if (g->worker_err.empty()) g->worker_err.swap(e.msg);
+                }
+                dev_cache().trim();
+            });
+            g->begun = true;
+            g->t_begin_ms = now_ms() - t0;
+            return;
+        }
         std::vector<int> todo;
         for (size_t r = 0; r < g->rooms.size(); ++r) todo.push_back((int)r);
         int nt = g->prm.host_threads > 0 ? g->prm.host_threads : (int)std::min<unsigned>(std::max(1u, std::thread::hardware_concurrency()), 16u);

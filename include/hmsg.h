@@ -448,6 +448,19 @@ int hmsg_read_json_numbers(const char* path, const char* key, double* out, int64
  * relative may be labelled differently).  tests/test_kmeans_cabi.py holds it to scikit-learn itself. */
 int hmsg_kmeans(const float* X, int64_t n, int32_t dim, int32_t k, int32_t n_init, int32_t max_iter, uint32_t seed,
                 int32_t* labels, float* centers, float* inertia, int32_t* n_iter);
+/* hmsg_kmeans_batch -- hmsg_kmeans for n_sets independent problems in one call, on the device (holoagent_amd/csrc/
+ * hmsg_kmeans_device.hip).  Set s is the rows set_off[s] .. set_off[s + 1] of X (set_off on the host, set_off[0] = 0); labels
+ * [set_off[n_sets]], centers [n_sets][k][dim], inertia / n_iter [n_sets] (optional).  X, labels, centers, inertia and n_iter may
+ * each be host or device memory.  The result equals hmsg_kmeans called once per set with the same arguments BIT FOR BIT: every
+ * float32 sum keeps its order and every float64 sum of float32 products the host's eight running sums, so both differ from
+ * the libraries scikit-learn calls in the same three places (the sgemm of the E-step, the einsum of the centre norms and the
+ * sgemv / dgemm of the k-means++ potentials are accumulated in float64 and rounded once).  All n_sets * n_init fits run side by
+ * side; no host round trip per Lloyd iteration or per chosen centre.  Argument rules are hmsg_kmeans', set by set: a set with
+ * fewer than k rows (or none) makes the call return HMSG_ERR_INVALID before anything is written; n_sets = 0 is HMSG_OK and touches
+ * nothing.  dim above 12288: HMSG_ERR_UNSUPPORTED.  Runs on a stream of its own and returns when the outputs are complete. */
+int hmsg_kmeans_batch(int32_t device_id, int32_t n_sets, const int64_t* set_off, const float* X, int32_t dim, int32_t k,
+                      int32_t n_init, int32_t max_iter, uint32_t seed, int32_t* labels, float* centers, float* inertia,
+                      int32_t* n_iter);
 int hmsg_assign_cameras_to_rooms(const double* dist, int64_t n_cams, int32_t n_rooms, const double* cam_height, double y_min,
                                  double y_max, int32_t* room_of_cam, int64_t* room_off, int32_t* room_imgs);
 int hmsg_pick_representative_views(const float* embs, int64_t n, int32_t dim, const int32_t* labels, const float* centers,
@@ -476,7 +489,8 @@ int hmsg_graph_edges(int32_t n_floors, int32_t n_rooms, const int32_t* room_floo
  *         label_feats f32 [n_labels][D] + label_names [n_labels] (get_label_feats), or 0 / NULL: every object is "object".
  *   hmsg_graph_begin / hmsg_graph_finish   the same in two halves, so that the room level runs BESIDE the fusion and the merge
  *       fold: begin right after hmsg_finalize_map (floors, regions, room clouds and the camera table on the device, then the
- *       KMeans fits on host threads), finish after hmsg_pool_instances (joins them; views, objects, edges).
+ *       KMeans fits on host threads, or with hmsg_graph_params::kmeans_device on the device), finish after hmsg_pool_instances
+ *       (joins them; views, objects, edges).
  *   hmsg_save   the whole directory in the reference layout: <dir>/floors/<f>.{ply,json}, rooms/<f>_<r>.{ply,json},
  *       objects/<id>.{ply,json}, views/<id>.json -- byte for byte what the mirror's Floor / Room / Object / View .save() write
  *       (tests/test_scene_graph_cabi.py), which tests/golden/persist.json pins to the reference's own classes.
@@ -501,7 +515,8 @@ typedef struct hmsg_graph_params {
     int32_t merge_objects_graph;   /* pipeline.merge_objects_graph (graph.py:2053-2058; false in every shipped config): after the objects, every
                                     * room fuses its same-name objects whose clouds overlap (Room.merge_objects, hmsg_merge_room_objects with
                                     * the reference's 0.01 / 0.1) and re-numbers them; the graph's object list is then the rooms' lists */
-    int32_t reserved_;
+    int32_t kmeans_device;      /* 0: the rooms' KMeans fits on host threads (hmsg_kmeans); != 0: the rooms of a storey in one hmsg_kmeans_batch
+                                 * call on the device, from one worker thread -- the same bits either way */
 } hmsg_graph_params;
 typedef struct hmsg_graph_counts {
     int32_t floors, rooms, views, objects;

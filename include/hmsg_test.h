@@ -61,6 +61,13 @@ int hmsg_test_pool_rows(int32_t device_id, int32_t K, const int32_t* counts, con
  * out, and that the block is whole again (same address) once every piece is back.  0 = ok, otherwise the failed check. */
 int hmsg_test_allocator_carving(int32_t device_id, int32_t root_gb);
 
+/* ONE Lloyd iteration of hmsg_kmeans / hmsg_kmeans_batch from given centres: E-step, centre sums, empty-cluster relocation,
+ * averaging, shift.  X [n][dim] as it is (no centring), centers_in [k][dim]; labels [n], centers_out [k][dim], shift [k].
+ * on_device 0: the host's lloyd_iter (hmsg_kmeans.hip); 1: the kernels of hmsg_kmeans_device.hip.  Random seeding practically
+ * never empties a cluster, so this is how a test puts the relocation under the kernels. */
+int hmsg_test_kmeans_lloyd(int32_t on_device, int32_t device_id, const float* X, int64_t n, int32_t dim, int32_t k,
+                           const float* centers_in, int32_t* labels, float* centers_out, float* shift);
+
 #ifdef __cplusplus
 }
 #endif
