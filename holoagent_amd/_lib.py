@@ -114,6 +114,7 @@ _SIGS = {
     "hmsg_get_frame_mask_points": (C.c_int, [_P, C.c_int32, _P]),
     "hmsg_merge_instances": (C.c_int, [_P]),
     "hmsg_set_frame_window": (C.c_int, [_P, C.c_int32]),
+    "hmsg_set_merge_tree_batch": (C.c_int, [_P, C.c_int64]),
     "hmsg_merge_tree_local": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "hmsg_merge_tree_join": (C.c_int, [_P, C.c_int32, _P, _P, C.c_double, C.c_int32]),
     "hmsg_num_instances": (C.c_int64, [_P]),
@@ -210,6 +211,7 @@ _SIGS = {
     "hmsg_test_repeat_add": (C.c_int, [_P, _P, _P, _P, C.c_int64]),
     "hmsg_test_ckdtree": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, _P]),
     "hmsg_test_boundary": (C.c_int, [C.c_int32, _P, C.c_int64]),
+    "hmsg_test_group_pairs": (C.c_int, [C.c_int32, C.c_int64, _P, C.c_int32, _P, C.c_double, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "hmsg_test_pool_rows": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_double, C.c_int32, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -477,6 +479,11 @@ class Scene:
 
     def set_frame_window(self, first_frame):
         self._ck(self.L.c.hmsg_set_frame_window(self.h, int(first_frame)))
+
+    def set_merge_tree_batch(self, max_batch_points):
+        """How the hierarchical merge walks a level of its tree (include/hmsg.h: hmsg_set_merge_tree_batch): 0 pair by pair (the
+        default), n > 0 level batches of at most n input points, -1 a whole level per batch.  Same instances either way."""
+        self._ck(self.L.c.hmsg_set_merge_tree_batch(self.h, int(max_batch_points)))
 
     def merge_tree_local(self, total_frames):
         """-> (threshold of the next level, lists at that level, index of this handle's list)"""

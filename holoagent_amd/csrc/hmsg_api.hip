@@ -216,6 +216,7 @@ int hmsg_reset(hmsg_t* h) {
         h->have_K = false;
         h->map_ready = h->feats_final = h->merged = h->pooled = h->inst_denoised = h->tree_partial = false;
         h->frame_window = 0;
+        h->merge_tree_batch = 0;
         h->nodes.clear();
         h->V = h->V0 = 0;
         h->masks3d.off.clear();
@@ -434,6 +435,16 @@ int hmsg_set_frame_window(hmsg_t* h, int32_t first_frame) {
         h->mask_first.assign((size_t)first_frame + 1, 0);
         h->masks3d.off.assign(1, 0);
         h->masks3d.total = 0;
+    });
+}
+
+int hmsg_set_merge_tree_batch(hmsg_t* h, int64_t max_batch_points) {
+    if (!h) return HMSG_ERR_INVALID;
+    return hmsg_boundary(h, [&] {
+        HMSG_REQUIRE(!h->merged && !h->tree_partial, HMSG_ERR_INVALID, "hmsg_set_merge_tree_batch: the instances are already merged (hmsg_reset first)");
+        HMSG_REQUIRE(max_batch_points >= -1 && max_batch_points <= 0x7fffffffll, HMSG_ERR_INVALID,
+                     "hmsg_set_merge_tree_batch: max_batch_points must be -1, 0 or at most 2^31 - 1");
+        h->merge_tree_batch = max_batch_points;
     });
 }
 

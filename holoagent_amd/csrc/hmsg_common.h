@@ -689,6 +689,7 @@ struct hmsg_ctx {
     bool merged = false;
     int frame_window = 0;          // first frame with features (hmsg_set_frame_window: this handle owns a frame range)
     bool tree_partial = false;     // inst holds an unfinished list of the sharded hierarchical merge tree
+    long long merge_tree_batch = 0; // hmsg_set_merge_tree_batch: 0 the merge tree pair by pair, > 0 level batches of that many points, -1 whole levels
     bool frames_released = false;  // the (very large) frame store was given back before the merge (hmsg_api.hip)
     DevBuf<float> inst_feats;      // [N][D]
     bool pooled = false;

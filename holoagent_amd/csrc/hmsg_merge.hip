@@ -581,22 +581,142 @@ __global__ void k_concat(const double* __restrict__ pool, const CatSeg* __restri
             dstcore[sg.dst + i] = sg.anchor ? poolcore[sg.src + i] : (unsigned char)0;
 }
 
-// ------------------------------------------------------------------------------------------ host side
-namespace {
-
-double bbox_iou(const Cloud& a, const Cloud& b) {   // graph_utils.py:883-915; empty cloud -> (0,0,0) box
+// ------------------------------------------------------------------------------------------ candidate pairs of a level batch
+// AABB IoU of two boxes (graph_utils.py:883-915), the ONE statement of it: the host's pair loop (bbox_iou) and the pair kernels
+// below evaluate this function, in float64, without contraction (the file is built with -ffp-contract=off), so a pair is a
+// candidate on the device exactly when it is one on the host.  The selections are written out as the comparisons std::max /
+// std::min make, not as fmax / fmin.
+__host__ __device__ inline double box_iou(const double* amn, const double* amx, const double* bmn, const double* bmx) {
     // boxes disjoint along an axis: overlap volume 0 -> IoU 0 (or 0/0): never > iou_thresh (>= 0 by contract)
-    if (a.mx[0] <= b.mn[0] || b.mx[0] <= a.mn[0] || a.mx[1] <= b.mn[1] || b.mx[1] <= a.mn[1] || a.mx[2] <= b.mn[2] ||
-        b.mx[2] <= a.mn[2])
+    if (amx[0] <= bmn[0] || bmx[0] <= amn[0] || amx[1] <= bmn[1] || bmx[1] <= amn[1] || amx[2] <= bmn[2] || bmx[2] <= amn[2])
         return 0.0;
     double ov = 1, va = 1, vb = 1;
     for (int k = 0; k < 3; ++k) {
-        double omin = std::max(a.mn[k], b.mn[k]), omax = std::min(a.mx[k], b.mx[k]);
-        ov *= std::max(omax - omin, 0.0);
-        va *= a.mx[k] - a.mn[k];
-        vb *= b.mx[k] - b.mn[k];
+        const double omin = amn[k] < bmn[k] ? bmn[k] : amn[k], omax = bmx[k] < amx[k] ? bmx[k] : amx[k];
+        const double d = omax - omin;
+        ov *= d < 0.0 ? 0.0 : d;
+        va *= amx[k] - amn[k];
+        vb *= bmx[k] - bmn[k];
     }
     return ov / (va + vb - ov);   // 0/0 -> NaN -> comparison false, like numpy
+}
+
+// The pairs (i, j), i < j, of one group with box_iou > iou_thresh, for every group of a batch: boxes [n][6] = (min xyz, max xyz),
+// an empty cloud as (+1e300, -1e300) so that the early reject drops it.  One workgroup per (group, tile of GP_TILE rows), a row
+// per lane; the group's boxes from the tile's first row on pass through LDS GP_TILE columns at a time and every lane reads the
+// same column (a broadcast).  Two passes: FILL = false counts row i's pairs into cnt[i]; after an exclusive scan FILL = true
+// writes them at start[i] in ascending j -- rows ascending, so the list is ascending in (i, j) whatever order the workgroups
+// run in.  `out` is pinned host memory: [0] = the number of pairs, pair k at int2 slot 1 + k; pairs past `cap` are counted
+// but not written (the host grows the buffer and fills again).
+static const int GP_TILE = 256;
+struct GpTile {
+    int row0, gend;             // first row of the tile, end of its group
+};
+template <bool FILL>
+__global__ void __launch_bounds__(GP_TILE) k_gp_pairs(const double* __restrict__ box, const GpTile* __restrict__ tiles, double iou_thresh, int n,
+                                                      unsigned* __restrict__ cnt, const unsigned* __restrict__ start, int* __restrict__ out,
+                                                      long long cap) {
+    __shared__ double sb[GP_TILE * 6];
+    const GpTile t = tiles[blockIdx.x];
+    const int i = t.row0 + (int)threadIdx.x;
+    const bool row = i < t.gend;
+    double a[6] = {0, 0, 0, 0, 0, 0};
+    if (row)
+        for (int k = 0; k < 6; ++k) a[k] = box[(size_t)i * 6 + k];
+    unsigned c = 0;
+    long long at = 0;
+    if (FILL) {
+        if (row) at = (long long)start[i];
+        if (blockIdx.x == 0 && threadIdx.x == 0) out[0] = (int)start[n];
+    }
+    for (int c0 = t.row0; c0 < t.gend; c0 += GP_TILE) {
+        const int nc = min(GP_TILE, t.gend - c0);
+        __syncthreads();
+        for (int q = (int)threadIdx.x; q < nc * 6; q += GP_TILE) sb[q] = box[(size_t)c0 * 6 + q];
+        __syncthreads();
+        if (!row) continue;
+        for (int q = 0; q < nc; ++q) {
+            const double* b = sb + q * 6;
+            if (c0 + q <= i || !(box_iou(a, a + 3, b, b + 3) > iou_thresh)) continue;
+            if (FILL) {
+                if (at < cap) ((int2*)out)[1 + at] = make_int2(i, c0 + q);
+                ++at;
+            } else {
+                ++c;
+            }
+        }
+    }
+    if (!FILL && row) cnt[i] = c;
+}
+
+// ------------------------------------------------------------------------------------------ host side
+namespace {
+
+// The two passes of k_gp_pairs for one batch: the ascending pair list of every group, read back through pinned memory with one
+// wait (a second one only when the list outgrew the buffer).
+struct GroupPairs {
+    PinnedBuf<char> h_in;           // [boxes | tiles], one upload
+    DevBuf<char> d_in;
+    DevBuf<unsigned> cnt, start;    // pairs per row / their exclusive scan (+1: the total)
+    PinnedBuf<int> h_out;           // [total, - | pairs]
+    long long cap_pairs = 0;        // pairs the fill pass may write: what was ASKED of h_out (the buffer itself may be larger)
+    SpinWait spin;
+    // boxes [n][6]; group g = rows [group_off[g], group_off[g + 1]).  Returns the pairs (valid until the next call).
+    const int* run(hipStream_t s, DevBuf<unsigned>& scan_tmp, Prof* prof, const double* boxes, int n, const int* group_off, int n_groups,
+                   double iou_thresh, long long* n_pairs) {
+        *n_pairs = 0;
+        std::vector<GpTile> tiles;
+        for (int g = 0; g < n_groups; ++g)
+            for (int r = group_off[g]; r < group_off[g + 1]; r += GP_TILE) tiles.push_back(GpTile{r, group_off[g + 1]});
+        if (tiles.empty()) return nullptr;
+        const size_t off_t = (size_t)n * 48, bytes = off_t + tiles.size() * sizeof(GpTile);
+        h_in.ensure(bytes);
+        d_in.ensure(bytes);
+        memcpy(h_in.p, boxes, off_t);
+        memcpy(h_in.p + off_t, tiles.data(), tiles.size() * sizeof(GpTile));
+        upload_pinned(d_in.p, h_in.p, bytes, s);
+        cnt.ensure((size_t)n + 1);
+        start.ensure((size_t)n + 1);
+        HIP_TRY(hipMemsetAsync(cnt.p + n, 0, 4, s));
+        const double* d_box = (const double*)d_in.p;
+        const GpTile* d_tiles = (const GpTile*)(d_in.p + off_t);
+        ProfScope ps(prof, s, "k_gp_pairs", (double)n * 48.0);
+        hipLaunchKernelGGL(k_gp_pairs<false>, dim3((unsigned)tiles.size()), dim3(GP_TILE), 0, s, d_box, d_tiles, iou_thresh, n, cnt.p,
+                           (const unsigned*)nullptr, (int*)nullptr, 0ll);
+        HMSG_CHECK_LAUNCH();
+        hmsg_scan_u32(cnt.p, start.p, (size_t)n + 1, s, scan_tmp, nullptr);
+        // first buffer: room for max(4 n, 4096) pairs, or what an earlier batch needed; a longer list is counted in full, written up to
+        // there, and filled again into a buffer of its size (tests/test_group_pairs.py goes through both)
+        cap_pairs = std::max<long long>(cap_pairs, std::max<long long>((long long)n * 4, 4096));
+        h_out.ensure(2 + 2 * (size_t)cap_pairs);
+        for (;;) {
+            const long long cap = cap_pairs;
+            hipLaunchKernelGGL(k_gp_pairs<true>, dim3((unsigned)tiles.size()), dim3(GP_TILE), 0, s, d_box, d_tiles, iou_thresh, n,
+                               (unsigned*)nullptr, (const unsigned*)start.p, h_out.p, cap);
+            HMSG_CHECK_LAUNCH();
+            spin.wait(s);
+            const long long total = (long long)(unsigned)h_out.p[0];
+            if (total <= cap) {
+                *n_pairs = total;
+                return h_out.p + 2;
+            }
+            cap_pairs = total;
+            h_out.ensure(2 + 2 * (size_t)cap_pairs);
+        }
+    }
+    // the scan counts in 32 bits: whether the groups' pairs (all of them candidates at worst) fit
+    static bool fits(const int* group_off, int n_groups) {
+        unsigned long long worst = 0;
+        for (int g = 0; g < n_groups; ++g) {
+            const unsigned long long m = (unsigned long long)(group_off[g + 1] - group_off[g]);
+            worst += m * (m ? m - 1 : 0) / 2;
+        }
+        return worst < (1ull << 32);
+    }
+};
+
+double bbox_iou(const Cloud& a, const Cloud& b) {   // graph_utils.py:883-915; empty cloud -> (0,0,0) box
+    return box_iou(a.mn, a.mx, b.mn, b.mx);
 }
 
 // cm[j] = box j meets the query box q = {lo0, hi0, lo1, hi1, lo2, hi2} with positive extent on every axis
@@ -1103,12 +1223,13 @@ struct Merger {
 
     // ---- candidate pairs of merge_3d_masks (graph_utils.py:937-941): AABB IoU above the threshold; sequential merge:
     // only pairs with a new or changed member (shortcut 2); hierarchical merge: cached ratios of unchanged pairs
+    // `group_off` (a level batch of the hierarchical merge: group g = L[group_off[g] .. group_off[g + 1])): pairs are looked for
+    // inside a group only -- by k_gp_pairs, or with HMSG_DEBUG_TREE_HOST_PAIRS=1 by the host's loop group by group.
     void find_pairs(const std::vector<Cloud>& L, std::vector<std::pair<int, int>>& pairs, std::vector<double>& known,
-                    std::vector<std::pair<int, int>>& known_pairs) {
+                    std::vector<std::pair<int, int>>& known_pairs, const std::vector<int>* group_off = nullptr) {
         const int n = (int)L.size();
-        auto consider = [&](int i, int j) {
-            if (L[i].n == 0 || L[j].n == 0) return;   // find_overlapping_ratio_faiss returns 0 for empty clouds
-            if (!(bbox_iou(L[i], L[j]) > iou_thresh)) return;
+        // what becomes of a pair whose boxes pass the IoU test
+        auto candidate = [&](int i, int j) {
             if (use_cache && !L[i].fresh && !L[j].fresh) {
                 auto it = ratio_cache.find(L[i].uid * 0x100000000ull + L[j].uid);
                 if (it != ratio_cache.end()) {
@@ -1119,7 +1240,33 @@ struct Merger {
             }
             pairs.emplace_back(i, j);
         };
-        if (use_cache) {
+        auto consider = [&](int i, int j) {
+            if (L[i].n == 0 || L[j].n == 0) return;   // find_overlapping_ratio_faiss returns 0 for empty clouds
+            if (!(bbox_iou(L[i], L[j]) > iou_thresh)) return;
+            candidate(i, j);
+        };
+        // (groups are a matter of the hierarchical merge: the sequential branch below enumerates from the fresh clouds over the whole list)
+        HMSG_REQUIRE(use_cache || !group_off, HMSG_ERR_INVALID, "merge_3d_masks: groups are supported by the hierarchical merge only");
+        if (use_cache && group_off && group_off->size() > 2) {
+            const int G = (int)group_off->size() - 1;
+            const bool on_device = gp_wanted && GroupPairs::fits(group_off->data(), G);
+            (on_device ? gp_device_batches : gp_host_batches) += 1;
+            if (on_device) {
+                gp_box.resize((size_t)n * 6);
+                for (int i = 0; i < n; ++i)
+                    for (int a = 0; a < 3; ++a) {
+                        gp_box[(size_t)i * 6 + a] = L[i].n ? L[i].mn[a] : 1e300;         // empty clouds never pair
+                        gp_box[(size_t)i * 6 + 3 + a] = L[i].n ? L[i].mx[a] : -1e300;
+                    }
+                long long np = 0;
+                const int* pr = gp.run(s, ops.scan_tmp, ops.prof, gp_box.data(), n, group_off->data(), G, iou_thresh, &np);
+                for (long long k = 0; k < np; ++k) candidate(pr[2 * k], pr[2 * k + 1]);
+            } else {
+                for (int g = 0; g < G; ++g)
+                    for (int i = (*group_off)[g]; i < (*group_off)[g + 1]; ++i)
+                        for (int j = i + 1; j < (*group_off)[g + 1]; ++j) consider(i, j);
+            }
+        } else if (use_cache) {
             for (int i = 0; i < n; ++i)
                 for (int j = i + 1; j < n; ++j) consider(i, j);
         } else {
@@ -1185,6 +1332,10 @@ struct Merger {
         }
     }
     // (find_pairs' buffers, kept between steps)
+    GroupPairs gp;
+    std::vector<double> gp_box;
+    bool gp_wanted = getenv("HMSG_DEBUG_TREE_HOST_PAIRS") == nullptr;   // HMSG_DEBUG_TREE_HOST_PAIRS=1: a level batch's pairs by the host's loop
+    double gp_device_batches = 0, gp_host_batches = 0;                  // (statistics: which way the level batches' pairs were listed)
     std::vector<double> fp_lo[3], fp_hi[3], fp_slo[3], fp_shi[3];
     std::vector<unsigned char> fp_fr, fp_cand;
     std::vector<int> fp_sub;
@@ -1230,8 +1381,14 @@ struct Merger {
     }
 
     // ---- merge_3d_masks (graph_utils.py:918-956)
-    std::vector<Cloud> merge_3d_masks(std::vector<Cloud> L, double th) {
+    // group_off / out_group_off (a level batch of the hierarchical merge): L is the concatenation of independent lists, list g =
+    // L[group_off[g] .. group_off[g + 1]); pairs are formed inside a list only, so no component crosses lists and -- components
+    // being labelled by their lowest member -- the result is the concatenation of the lists' own results, cut at out_group_off.
+    // Everything between the pair search and that cut works on the flat list as it does for one list.
+    std::vector<Cloud> merge_3d_masks(std::vector<Cloud> L, double th, const std::vector<int>* group_off = nullptr,
+                                      std::vector<int>* out_group_off = nullptr) {
         const int n = (int)L.size();
+        if (out_group_off) out_group_off->assign(group_off->size(), 0);
         if (n == 0) return L;
         auto tnow = [] { return std::chrono::steady_clock::now(); };
         auto t0 = tnow();
@@ -1248,7 +1405,7 @@ struct Merger {
         std::vector<std::pair<int, int>> pairs;
         std::vector<double> known;                 // cached ratios (hierarchical)
         std::vector<std::pair<int, int>> known_pairs;
-        find_pairs(L, pairs, known, known_pairs);
+        find_pairs(L, pairs, known, known_pairs, group_off);
         std::vector<double> ratio;
         lap(1);
         std::vector<unsigned char> second_ran;
@@ -1586,6 +1743,16 @@ struct Merger {
             if (!mode) cursor += r.n_out;
         }
         pool_used = cursor;
+        if (out_group_off) {
+            // output cloud c came from component c, whose members all lie in the list of its first one
+            const int G = (int)group_off->size() - 1;
+            size_t c = 0;
+            for (int g = 0; g < G; ++g) {
+                (*out_group_off)[(size_t)g] = (int)c;
+                while (c < comps.size() && comps[c][0] < (*group_off)[(size_t)g + 1]) ++c;
+            }
+            (*out_group_off)[(size_t)G] = (int)c;
+        }
         lap(5);
         return out;
     }
@@ -1712,6 +1879,48 @@ double next_level_threshold(double th, double factor, long long lists) {
     return th - factor * (double)(lists - 2) / (double)std::max<long long>(1, lists - 1);
 }
 
+// One level of the merge tree (graph_utils.py:959-986) in batches (hmsg_set_merge_tree_batch): the level's adjacent pairs
+// [lv[2k] ++ lv[2k + 1]] are independent of each other, so consecutive pairs whose input points sum to `max_points` at most
+// (-1: the whole level; a pair above the bound goes alone) pass through ONE merge_3d_masks call as its groups -- one grid build,
+// one overlap task list, one DBSCAN batch and two waits for the run instead of for every pair.  An odd last list is carried up.
+// The DBSCAN batch and the grid build address a batch's points in 32 bits: a run never exceeds 2^31 - 1 points.
+std::vector<std::vector<Cloud>> merge_level_batched(Merger& m, std::vector<std::vector<Cloud>>& lv, double th, long long max_points) {
+    const long long bound = max_points < 0 ? 0x7fffffffll : max_points;      // (the setter admits 2^31 - 1 at most)
+    std::vector<std::vector<Cloud>> nx;
+    nx.reserve((lv.size() + 1) / 2);
+    const size_t npairs = lv.size() / 2;
+    std::vector<long long> pair_pts(npairs, 0), pair_clouds(npairs, 0);
+    for (size_t k = 0; k < npairs; ++k)
+        for (size_t q = 2 * k; q < 2 * k + 2; ++q) {
+            pair_clouds[k] += (long long)lv[q].size();
+            for (const Cloud& c : lv[q]) pair_pts[k] += c.n;
+        }
+    for (size_t k0 = 0; k0 < npairs;) {
+        size_t k1 = k0;
+        long long pts = 0, clouds = 0;
+        do {
+            pts += pair_pts[k1];
+            clouds += pair_clouds[k1];
+            ++k1;
+        } while (k1 < npairs && pts + pair_pts[k1] <= bound && clouds + pair_clouds[k1] <= 0x7fffffffll);
+        std::vector<Cloud> L;
+        L.reserve((size_t)clouds);
+        std::vector<int> group_off(1, 0), out_off;
+        for (size_t k = k0; k < k1; ++k) {
+            for (size_t q = 2 * k; q < 2 * k + 2; ++q) {
+                L.insert(L.end(), lv[q].begin(), lv[q].end());
+                std::vector<Cloud>().swap(lv[q]);
+            }
+            group_off.push_back((int)L.size());
+        }
+        std::vector<Cloud> out = m.merge_3d_masks(std::move(L), th, &group_off, &out_off);
+        for (size_t g = 0; g + 1 < out_off.size(); ++g) nx.emplace_back(out.begin() + out_off[g], out.begin() + out_off[g + 1]);
+        k0 = k1;
+    }
+    if (lv.size() & 1) nx.push_back(std::move(lv.back()));
+    return nx;
+}
+
 }  // namespace
 
 // Switch a sequential fold to the incremental fold of hmsg_fold.inl: the live clouds (the instance list G and the masks
@@ -1797,6 +2006,9 @@ static void merge_report(Folder& m) {
     if (getenv("HMSG_DEBUG_TIMING"))
         fprintf(stderr, "[hmsg merge] overlap grids: %.0f over whole clouds (%.0f points), %.0f delta grids (%.0f points); of them behind the DBSCAN batches: %.0f (%.0f points), %.0f not needed\n", m.grid_full,
                 m.grid_full_pts, m.grid_delta, m.grid_delta_pts, m.spec_built, m.spec_built_pts, m.spec_skipped);
+    if (getenv("HMSG_DEBUG_TIMING") && (m.gp_device_batches > 0 || m.gp_host_batches > 0))
+        fprintf(stderr, "[hmsg merge] level batches of several pairs: candidate pairs of %.0f listed on the device (k_gp_pairs; inside 'pairs(host)' above), of %.0f by the host's loop\n",
+                m.gp_device_batches, m.gp_host_batches);
     if (getenv("HMSG_DEBUG_TIMING") && m.n_collects)
         fprintf(stderr, "[hmsg merge] %d collections of the point pool / grid arenas\n", m.n_collects);
     if (getenv("HMSG_DEBUG_TIMING") && m.ops.stat_calls > 0)
@@ -2121,14 +2333,18 @@ void hmsg_merge(hmsg_ctx* h) {
         std::vector<std::vector<Cloud>> lv = std::move(frames);
         while (lv.size() > 1) {
             std::vector<std::vector<Cloud>> nx;
-            for (size_t i = 0; i < lv.size(); i += 2) {
-                if (i == lv.size() - 1) {
-                    nx.push_back(std::move(lv[i]));
-                    break;
+            if (h->merge_tree_batch != 0) {
+                nx = merge_level_batched(m, lv, th, h->merge_tree_batch);
+            } else {
+                for (size_t i = 0; i < lv.size(); i += 2) {
+                    if (i == lv.size() - 1) {
+                        nx.push_back(std::move(lv[i]));
+                        break;
+                    }
+                    std::vector<Cloud> L = std::move(lv[i]);
+                    L.insert(L.end(), lv[i + 1].begin(), lv[i + 1].end());
+                    nx.push_back(m.merge_3d_masks(std::move(L), th));
                 }
-                std::vector<Cloud> L = std::move(lv[i]);
-                L.insert(L.end(), lv[i + 1].begin(), lv[i + 1].end());
-                nx.push_back(m.merge_3d_masks(std::move(L), th));
             }
             lv = std::move(nx);
             if (lv.size() > 1) th = next_level_threshold(th, c.overlap_thresh_factor, (long long)lv.size());
@@ -2173,14 +2389,18 @@ void hmsg_merge_tree_local_impl(hmsg_ctx* h, int total_frames, double* th_next, 
         // business (every handle then stops at a level the others can work out, whatever the window lengths).
         if (n == 1 || (off & 1) || ((n & 1) && off + n < lists)) break;
         std::vector<std::vector<Cloud>> nx;
-        for (size_t i = 0; i < lv.size(); i += 2) {
-            if (i == lv.size() - 1) {
-                nx.push_back(std::move(lv[i]));
-                break;
+        if (h->merge_tree_batch != 0) {
+            nx = merge_level_batched(m, lv, th, h->merge_tree_batch);
+        } else {
+            for (size_t i = 0; i < lv.size(); i += 2) {
+                if (i == lv.size() - 1) {
+                    nx.push_back(std::move(lv[i]));
+                    break;
+                }
+                std::vector<Cloud> L = std::move(lv[i]);
+                L.insert(L.end(), lv[i + 1].begin(), lv[i + 1].end());
+                nx.push_back(m.merge_3d_masks(std::move(L), th));
             }
-            std::vector<Cloud> L = std::move(lv[i]);
-            L.insert(L.end(), lv[i + 1].begin(), lv[i + 1].end());
-            nx.push_back(m.merge_3d_masks(std::move(L), th));
         }
         lv = std::move(nx);
         off >>= 1;
@@ -2246,6 +2466,33 @@ void hmsg_merge_tree_join_impl(hmsg_ctx* h, int n_ext, const long long* ext_size
         h->merged = true;
         h->tree_partial = false;
     }
+}
+
+// ---- test hook (include/hmsg_test.h: hmsg_test_group_pairs): the pair kernels of a level batch on host arrays
+extern "C" int hmsg_test_group_pairs(int32_t device_id, int64_t n, const double* boxes, int32_t n_groups, const int64_t* group_off,
+                                     double iou_thresh, int32_t* pairs_out, int64_t capacity, int64_t* n_pairs) {
+    if (n < 0 || n > 0x7fffffffll || n_groups < 0 || !group_off || !n_pairs || capacity < 0 || (n > 0 && !boxes) || (capacity > 0 && !pairs_out))
+        return HMSG_ERR_INVALID;
+    *n_pairs = 0;
+    return hmsg_boundary("hmsg_test_group_pairs", device_id, [&] {
+        std::vector<int> off((size_t)n_groups + 1);
+        for (int g = 0; g <= n_groups; ++g) {
+            HMSG_REQUIRE(group_off[g] >= (g ? group_off[g - 1] : 0) && group_off[g] <= n, HMSG_ERR_INVALID, "group_off must ascend from 0 to n");
+            off[(size_t)g] = (int)group_off[g];
+        }
+        HMSG_REQUIRE(off[0] == 0 && off[(size_t)n_groups] == (int)n, HMSG_ERR_INVALID, "group_off must ascend from 0 to n");
+        HMSG_REQUIRE(GroupPairs::fits(off.data(), n_groups), HMSG_ERR_UNSUPPORTED, "the groups hold 2^32 pairs or more");
+        ScopedStream s(hipStreamNonBlocking);
+        {
+            GroupPairs gp;
+            DevBuf<unsigned> scan_tmp;
+            long long np = 0;
+            const int* pr = gp.run(s, scan_tmp, nullptr, boxes, (int)n, off.data(), n_groups, iou_thresh, &np);
+            *n_pairs = np;
+            const long long m = std::min<long long>(np, capacity);
+            if (m) memcpy(pairs_out, pr, (size_t)m * 8);
+        }
+    });
 }
 
 // A10 first step (graph.py:1589-1591): every instance re-denoised with pcd_denoise_dbscan(eps, min_points),

@@ -196,6 +196,18 @@ int hmsg_get_instance_boxes(const hmsg_t* h, double* boxes /*[N][6]: AABB min xy
  *                          n_ext == 0 with final_pass: a single handle held every frame.
  * The result is bit-identical to hmsg_merge_instances over all frames (tests/test_distributed_gloo.py). */
 int hmsg_set_frame_window(hmsg_t* h, int32_t first_frame);
+/* How the hierarchical merge walks a level of its tree (merge_adjacent_frames, graph_utils.py:959-986: the level's adjacent pairs
+ * of lists, each through merge_3d_masks).  The pairs of a level are independent of each other:
+ *    0  (default; again after hmsg_reset) one merge_3d_masks pass per pair, one after the other;
+ *   >0  consecutive pairs whose input points sum to at most max_batch_points share ONE pass -- one grid build, one overlap
+ *       task list, one DBSCAN batch; candidate pairs are formed inside a pair's own lists only (on the device).  A pair above
+ *       the bound goes alone.  The bound limits the device memory of a pass (point pool, batch copy, grids);
+ *   -1  a whole level per pass (2^31 - 1 points at most, the limit of one DBSCAN batch).
+ * The instances are the same, bit for bit, whatever the value.  Honoured by hmsg_merge_instances with merge_type hierarchical
+ * and by the levels hmsg_merge_tree_local plays (so by hmsg_merge_tree_sharded); hmsg_merge_tree_join is one pair and the
+ * sequential merge a fold: neither is affected.  HMSG_ERR_INVALID once hmsg_merge_instances / hmsg_merge_tree_local have run
+ * on the scene, for values below -1 and above 2^31 - 1. */
+int hmsg_set_merge_tree_batch(hmsg_t* h, int64_t max_batch_points);
 int hmsg_merge_tree_local(hmsg_t* h, int32_t total_frames, double* th_next, int64_t* lists_now, int64_t* my_index);
 int hmsg_merge_tree_join(hmsg_t* h, int32_t n_ext, const int64_t* ext_sizes, const double* ext_points, double th,
                          int32_t final_pass);

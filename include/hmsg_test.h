@@ -68,6 +68,14 @@ int hmsg_test_allocator_carving(int32_t device_id, int32_t root_gb);
 int hmsg_test_kmeans_lloyd(int32_t on_device, int32_t device_id, const float* X, int64_t n, int32_t dim, int32_t k,
                            const float* centers_in, int32_t* labels, float* centers_out, float* shift);
 
+/* test hook: the candidate pairs of a level batch of the hierarchical merge (hmsg_set_merge_tree_batch) as its two kernels list
+ * them.  boxes f64 [n][6] = AABB (min xyz, max xyz) on the host; group g = rows [group_off[g], group_off[g + 1]), group_off i64
+ * [n_groups + 1] from 0 to n.  The pairs (i, j), i < j, both of one group, whose AABB IoU (bbox_iou, graph_utils.py:883-915, in
+ * float64 as the host evaluates it) is > iou_thresh, ascending in (i, j): n_pairs = how many there are, the first
+ * min(n_pairs, capacity) of them in pairs_out i32 [capacity][2]. */
+int hmsg_test_group_pairs(int32_t device_id, int64_t n, const double* boxes, int32_t n_groups, const int64_t* group_off,
+                          double iou_thresh, int32_t* pairs_out, int64_t capacity, int64_t* n_pairs);
+
 #ifdef __cplusplus
 }
 #endif
