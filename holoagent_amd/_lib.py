@@ -126,6 +126,8 @@ _SIGS = {
     "hmsg_voxel_down_sample": (C.c_int, [_P, _P, C.c_int64, C.c_double, _P, _P]),
     "hmsg_pool_instances": (C.c_int, [_P]),
     "hmsg_get_instance_feats": (C.c_int, [_P, _P]),
+    "hmsg_restore_stage": (C.c_int, [_P, C.c_int64, _P, _P, _P, C.c_int64, _P, _P, _P, _P]),
+    "hmsg_read_ply": (C.c_int, [C.c_char_p, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "hmsg_build_object_nodes": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, _P, _P, _P, C.c_int32, _P]),
     "hmsg_num_nodes": (C.c_int64, [_P]),
     "hmsg_get_nodes": (C.c_int, [_P, _P, _P]),
@@ -733,6 +735,49 @@ class Scene:
         if n:
             self._ck(self.L.c.hmsg_get_instance_feats(self.h, _ptr(out)))
         return out
+
+    def restore_stage(self, map_points, inst_points, inst_feats, K, map_colors=None, map_feats=None):
+        """The stage artefacts back into a fresh (or reset) scene (include/hmsg.h: hmsg_restore_stage): afterwards the scene is where
+        pool_instances() leaves one, as far as the graph level can tell.  map_points [V, 3] f64 (any cloud, its order is kept);
+        inst_points: a list of [n_i, 3] arrays, or (off i64 [N + 1], xyz [sum, 3] f64) with xyz on the host or the device;
+        inst_feats [N, D] f32; K [3, 3]; map_colors [V, 3] f64 and map_feats [V, D] f32 optional.  numpy arrays, or torch tensors
+        (host or device) of exactly these dtypes."""
+        def arr(a, dt):
+            return np.ascontiguousarray(a, dt) if isinstance(a, (np.ndarray, list, tuple)) else a
+        if isinstance(inst_points, tuple) and len(inst_points) == 2 and np.ndim(inst_points[0]) == 1:
+            off, xyz = np.ascontiguousarray(inst_points[0], np.int64), arr(inst_points[1], np.float64)
+        else:
+            clouds = [np.asarray(c, np.float64).reshape(-1, 3) for c in inst_points]
+            off = np.zeros(len(clouds) + 1, np.int64)
+            off[1:] = np.cumsum([len(c) for c in clouds])
+            xyz = np.ascontiguousarray(np.concatenate(clouds) if len(clouds) else np.zeros((0, 3)), np.float64)
+        n = len(off) - 1
+        mp, mc, mf = arr(map_points, np.float64), None if map_colors is None else arr(map_colors, np.float64), None if map_feats is None else arr(map_feats, np.float32)
+        feats = arr(inst_feats, np.float32)
+        D = self.cfg.feat_dim
+        if tuple(feats.shape) != (n, D) and not (n == 0 and int(np.prod(tuple(feats.shape))) == 0):
+            raise ValueError(f"inst_feats must be [{n}, {D}], got {tuple(feats.shape)}")
+        if mf is not None and tuple(mf.shape) != (int(mp.shape[0]), D):
+            raise ValueError(f"map_feats must be [{int(mp.shape[0])}, {D}], got {tuple(mf.shape)}")
+        if mc is not None and tuple(mc.shape) != tuple(mp.shape):
+            raise ValueError("map_colors must have the shape of map_points")
+        Kh = np.ascontiguousarray(np.asarray(K, np.float64).reshape(9))
+        self._ck(self.L.c.hmsg_restore_stage(self.h, int(mp.shape[0]), _ptr(mp), _ptr(mc), _ptr(mf), n, _ptr(off),
+                                             _ptr(xyz) if int(off[-1]) else None, _ptr(feats) if n else None, _ptr(Kh)))
+
+
+def read_ply(path, lib_: "HmsgLib | None" = None):
+    """x y z of a binary little-endian PLY file as f64 [n, 3] (include/hmsg.h: hmsg_read_ply)."""
+    L = lib_ or lib()
+    n = C.c_int64(0)
+    rc = L.c.hmsg_read_ply(str(path).encode(), None, 0, C.byref(n))
+    if rc != 0:
+        raise HmsgError(f"hmsg_read_ply failed ({rc}) for {path}")
+    out = np.empty((int(n.value), 3), np.float64)
+    rc = L.c.hmsg_read_ply(str(path).encode(), _ptr(out), int(n.value), C.byref(n))
+    if rc != 0:
+        raise HmsgError(f"hmsg_read_ply failed ({rc}) for {path}")
+    return out
 
 
 class SceneGraph:

@@ -214,7 +214,7 @@ int hmsg_reset(hmsg_t* h) {
         h->nmask.clear();
         h->mask_first.clear();
         h->have_K = false;
-        h->map_ready = h->feats_final = h->merged = h->pooled = h->inst_denoised = h->tree_partial = false;
+        h->map_ready = h->feats_final = h->merged = h->pooled = h->inst_denoised = h->tree_partial = h->restored = false;
         h->frame_window = 0;
         h->merge_tree_batch = 0;
         h->nodes.clear();
@@ -222,6 +222,7 @@ int hmsg_reset(hmsg_t* h) {
         h->masks3d.off.clear();
         h->masks3d.total = 0;
         h->inst.off.clear();
+        h->inst.box.clear();
         h->inst.total = 0;
         h->prof.clear();
     });
@@ -292,6 +293,7 @@ int hmsg_add_frames(hmsg_t* h, int32_t n, const uint8_t* rgb, const uint16_t* de
     if (!h) return HMSG_ERR_INVALID;
     return hmsg_boundary(h, [&] {
         HMSG_REQUIRE(n >= 0 && rgb && depth && pose && K, HMSG_ERR_INVALID, "hmsg_add_frames: null argument");
+        HMSG_NOT_RESTORED(h, "hmsg_add_frames");
         HMSG_REQUIRE(!h->map_ready, HMSG_ERR_INVALID, "hmsg_add_frames after hmsg_finalize_map");
         HMSG_REQUIRE(!h->frames_released, HMSG_ERR_INVALID, "hmsg_add_frames: the frame store was released (hmsg_reset first)");
         double Kh[9];
@@ -339,6 +341,7 @@ int hmsg_add_frames(hmsg_t* h, int32_t n, const uint8_t* rgb, const uint16_t* de
 int hmsg_finalize_map(hmsg_t* h) {
     if (!h) return HMSG_ERR_INVALID;
     return hmsg_boundary(h, [&] {
+        HMSG_NOT_RESTORED(h, "hmsg_finalize_map");
         HMSG_REQUIRE(!h->map_ready, HMSG_ERR_INVALID, "map already finalised");
         hmsg_build_map(h);
     });
@@ -363,6 +366,7 @@ int hmsg_add_frame_features(hmsg_t* h, int32_t first, int32_t n, int32_t M, cons
     if (!h) return HMSG_ERR_INVALID;
     return hmsg_boundary(h, [&] {
         HMSG_REQUIRE(n >= 0 && F_g, HMSG_ERR_INVALID, "hmsg_add_frame_features: null argument");
+        HMSG_NOT_RESTORED(h, "hmsg_add_frame_features");
         HMSG_REQUIRE(M >= 0 && M <= h->cfg.max_masks, HMSG_ERR_INVALID, "M out of range (cfg.max_masks, <= 256)");
         HMSG_REQUIRE(M == 0 || (masks && F_masked && F_crop), HMSG_ERR_INVALID, "hmsg_add_frame_features: null argument");
         HMSG_REQUIRE(first == h->n_feat_frames, HMSG_ERR_INVALID, "frames must be handed over in order (first == #frames so far)");
@@ -426,6 +430,7 @@ int hmsg_add_frame_features(hmsg_t* h, int32_t first, int32_t n, int32_t M, cons
 int hmsg_set_frame_window(hmsg_t* h, int32_t first_frame) {
     if (!h) return HMSG_ERR_INVALID;
     return hmsg_boundary(h, [&] {
+        HMSG_NOT_RESTORED(h, "hmsg_set_frame_window");
         HMSG_REQUIRE(h->map_ready, HMSG_ERR_INVALID, "hmsg_set_frame_window: call hmsg_finalize_map first");
         HMSG_REQUIRE(h->n_feat_frames == 0 && h->n_fused == 0, HMSG_ERR_INVALID, "hmsg_set_frame_window: features already handed over");
         HMSG_REQUIRE(first_frame >= 0 && first_frame <= h->n_frames, HMSG_ERR_INVALID, "hmsg_set_frame_window: frame out of range");
@@ -452,6 +457,7 @@ int hmsg_merge_tree_local(hmsg_t* h, int32_t total_frames, double* th_next, int6
     if (!h || !th_next || !lists_now || !my_index) return HMSG_ERR_INVALID;
     return hmsg_boundary(h, [&] {
         long long l = 0, i = 0;
+        HMSG_NOT_RESTORED(h, "hmsg_merge_tree_local");
         hmsg_fold_pipe_abort(h);
         release_frame_store_if_large(h);
         hmsg_merge_tree_local_impl(h, total_frames, th_next, &l, &i);
@@ -462,7 +468,10 @@ int hmsg_merge_tree_local(hmsg_t* h, int32_t total_frames, double* th_next, int6
 
 int hmsg_merge_tree_join(hmsg_t* h, int32_t n_ext, const int64_t* ext_sizes, const double* ext_points, double th, int32_t final_pass) {
     if (!h) return HMSG_ERR_INVALID;
-    return hmsg_boundary(h, [&] { hmsg_merge_tree_join_impl(h, n_ext, (const long long*)ext_sizes, ext_points, th, final_pass); });
+    return hmsg_boundary(h, [&] {
+        HMSG_NOT_RESTORED(h, "hmsg_merge_tree_join");
+        hmsg_merge_tree_join_impl(h, n_ext, (const long long*)ext_sizes, ext_points, th, final_pass);
+    });
 }
 
 int hmsg_fuse_frames(hmsg_t* h) {
@@ -474,7 +483,9 @@ int hmsg_get_map_feats(const hmsg_t* hc, float* feats, float* counter) {
     hmsg_ctx* h = const_cast<hmsg_ctx*>(hc);
     if (!h) return HMSG_ERR_INVALID;
     return hmsg_boundary(h, [&] {
+        HMSG_REQUIRE(h->feats_final || !h->restored, HMSG_ERR_INVALID, "hmsg_get_map_feats: the handle was restored without map features (hmsg_restore_stage)");
         HMSG_REQUIRE(h->feats_final, HMSG_ERR_INVALID, "hmsg_fuse_frames not run");
+        HMSG_REQUIRE(!(counter && h->restored), HMSG_ERR_INVALID, "hmsg_get_map_feats: a restored handle has no frame counter (hmsg_restore_stage)");
         if (feats) d2h_bounce(feats, h->feats.p, (size_t)h->V * h->cfg.feat_dim * 4);
         if (counter) {
             std::vector<unsigned> c((size_t)h->V);
@@ -498,6 +509,7 @@ int hmsg_get_feature_sums(const hmsg_t* hc, float* sum, uint32_t* counter) {
     hmsg_ctx* h = const_cast<hmsg_ctx*>(hc);
     if (!h) return HMSG_ERR_INVALID;
     return hmsg_boundary(h, [&] {
+        HMSG_NOT_RESTORED(h, "hmsg_get_feature_sums");
         HMSG_REQUIRE(h->feats_final, HMSG_ERR_INVALID, "hmsg_fuse_frames not run");
         const size_t n = (size_t)h->V * h->cfg.feat_dim;
         // (on the handle's own stream -- ordered behind whatever produced the sums -- and complete before the call returns:
@@ -511,6 +523,7 @@ int hmsg_get_feature_sums(const hmsg_t* hc, float* sum, uint32_t* counter) {
 int hmsg_set_feature_sums(hmsg_t* h, const float* sum, const uint32_t* counter) {
     if (!h) return HMSG_ERR_INVALID;
     return hmsg_boundary(h, [&] {
+        HMSG_NOT_RESTORED(h, "hmsg_set_feature_sums");
         HMSG_REQUIRE(h->feats_final && sum && counter, HMSG_ERR_INVALID, "hmsg_set_feature_sums: run hmsg_fuse_frames first");
         HMSG_REQUIRE(!h->pooled, HMSG_ERR_INVALID, "hmsg_set_feature_sums after hmsg_pool_instances");
         const size_t n = (size_t)h->V * h->cfg.feat_dim;
@@ -527,6 +540,7 @@ int hmsg_get_frame_nn(const hmsg_t* hc, int32_t frame, int32_t* idx) {
     hmsg_ctx* h = const_cast<hmsg_ctx*>(hc);
     if (!h) return HMSG_ERR_INVALID;
     return hmsg_boundary(h, [&] {
+        HMSG_NOT_RESTORED(h, "hmsg_get_frame_nn");
         HMSG_REQUIRE(frame >= 0 && frame < h->n_fused && idx, HMSG_ERR_INVALID, "frame not fused");
         HMSG_REQUIRE(!h->frames_released, HMSG_ERR_INVALID, "hmsg_get_frame_nn: the frame store was released by the merge (very long episode)");
         const size_t HW = (size_t)h->cfg.height * h->cfg.width;
@@ -538,6 +552,7 @@ int hmsg_get_frame_fp(const hmsg_t* hc, int32_t frame, float* f_p) {
     hmsg_ctx* h = const_cast<hmsg_ctx*>(hc);
     if (!h) return HMSG_ERR_INVALID;
     return hmsg_boundary(h, [&] {
+        HMSG_NOT_RESTORED(h, "hmsg_get_frame_fp");
         HMSG_REQUIRE(frame >= 0 && frame < h->n_feat_frames && f_p, HMSG_ERR_INVALID, "frame has no features");
         const size_t D = (size_t)h->cfg.feat_dim, n = (size_t)h->nmask[frame] * D;
         if (n) HIP_TRY(hipMemcpy(f_p, h->fp.p + (size_t)frame * h->MS * D, n * 4, hipMemcpyDeviceToHost));
@@ -552,6 +567,7 @@ int hmsg_get_frame_mask_sizes(const hmsg_t* hc, int32_t frame, int64_t* sizes) {
     hmsg_ctx* h = const_cast<hmsg_ctx*>(hc);
     if (!h) return HMSG_ERR_INVALID;
     return hmsg_boundary(h, [&] {
+        HMSG_NOT_RESTORED(h, "hmsg_get_frame_mask_sizes");
         HMSG_REQUIRE(frame >= 0 && frame < h->n_fused && sizes, HMSG_ERR_INVALID, "frame not fused");
         for (int i = 0; i < h->nmask[frame]; ++i) {
             size_t k = (size_t)h->mask_first[frame] + i;
@@ -564,6 +580,7 @@ int hmsg_get_frame_mask_points(const hmsg_t* hc, int32_t frame, double* xyz) {
     hmsg_ctx* h = const_cast<hmsg_ctx*>(hc);
     if (!h) return HMSG_ERR_INVALID;
     return hmsg_boundary(h, [&] {
+        HMSG_NOT_RESTORED(h, "hmsg_get_frame_mask_points");
         HMSG_REQUIRE(frame >= 0 && frame < h->n_fused && xyz, HMSG_ERR_INVALID, "frame not fused");
         long long a = h->masks3d.off[(size_t)h->mask_first[frame]], b = h->masks3d.off[(size_t)h->mask_first[frame + 1]];
         if (b > a) d2h_bounce(xyz, h->masks3d.pts.p + (size_t)a * 3, (size_t)(b - a) * 24);
@@ -573,6 +590,7 @@ int hmsg_get_frame_mask_points(const hmsg_t* hc, int32_t frame, double* xyz) {
 int hmsg_merge_instances(hmsg_t* h) {
     if (!h) return HMSG_ERR_INVALID;
     return hmsg_boundary(h, [&] {
+        HMSG_NOT_RESTORED(h, "hmsg_merge_instances");
         release_frame_store_if_large(h);
         hmsg_merge(h);
     });

@@ -290,7 +290,8 @@ int hmsg_allreduce_feature_sums(hmsg_t* h, hmsg_comm_t* c) {
     const int rc = hmsg_boundary(h, [&] {
         hipStream_t s = h->stream;
         std::string mine;
-        if (!h->feats_final) mine = "hmsg_allreduce_feature_sums: run hmsg_fuse_frames first";
+        if (h->restored) mine = "hmsg_allreduce_feature_sums: the handle was restored from stage artefacts (hmsg_restore_stage): no feature sums";
+        else if (!h->feats_final) mine = "hmsg_allreduce_feature_sums: run hmsg_fuse_frames first";
         else if (h->pooled) mine = "hmsg_allreduce_feature_sums after hmsg_pool_instances";
         if (!all_ranks_ok(c, mine.empty(), s))
             throw hmsg_error{HMSG_ERR_INVALID, mine.empty() ? "hmsg_allreduce_feature_sums: another rank is not ready (see its hmsg_last_error)" : mine};

@@ -36,6 +36,9 @@ struct hmsg_error {
         if (!(cond)) throw hmsg_error{code, text}; \
     } while (0)
 #define HMSG_CHECK_LAUNCH() HIP_TRY(hipGetLastError())
+// first line of every call that needs the frame store or the voxel bitmap (h: hmsg_ctx*)
+#define HMSG_NOT_RESTORED(h, fn) \
+    HMSG_REQUIRE(!(h)->restored, HMSG_ERR_INVALID, fn ": the handle was restored from stage artefacts (hmsg_restore_stage): no frames, no voxel bitmap")
 
 // np.sum of a short float64 array as numpy adds it (pairwise_sum below its 128-element block: eight running sums over
 // the leading multiple of 8, combined as a tree, then the tail in order) -- kernel weights are normalised by such a sum
@@ -697,6 +700,7 @@ struct hmsg_ctx {
     std::shared_ptr<struct FoldPipe> fold_pipe;
     int fold_pipe_frames = 0;      // frames handed to it so far
     DevCache fold_cache;           // the worker's allocator cache between scenes (its thread-local one while it runs)
+    bool restored = false;         // map, instances and pooled features came from hmsg_restore_stage: no frame store, no bitmap / rank / cand
     bool inst_denoised = false;    // the per-object pcd_denoise_dbscan(0.05, 10) of graph.py:1589-1591 has run
     std::vector<hmsg_node> nodes;  // object nodes (hmsg_build_object_nodes)
     // room clouds of the last hmsg_room_clouds call, resident: per room the selected floor points (indices into the storey's

@@ -699,6 +699,7 @@ static void dispatch_fuse(hmsg_ctx* h, const unsigned* stamp, int f0, int nfr) {
 }
 
 void hmsg_fuse(hmsg_ctx* h) {
+    HMSG_NOT_RESTORED(h, "hmsg_fuse_frames");
     const hmsg_config& c = h->cfg;
     hipStream_t s = h->stream;
     HMSG_REQUIRE(h->map_ready, HMSG_ERR_INVALID, "hmsg_fuse_frames: call hmsg_finalize_map first");

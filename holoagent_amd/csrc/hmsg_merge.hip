@@ -2305,6 +2305,7 @@ void hmsg_fold_pipe_abort(hmsg_ctx* h) {
 }
 
 void hmsg_merge(hmsg_ctx* h) {
+    HMSG_NOT_RESTORED(h, "hmsg_merge_instances");
     const hmsg_config& c = h->cfg;
     HMSG_REQUIRE(h->feats_final && h->n_fused > 0, HMSG_ERR_INVALID, "hmsg_merge_instances: run hmsg_fuse_frames first");
     HMSG_REQUIRE(!h->merged, HMSG_ERR_INVALID, "instances already merged");

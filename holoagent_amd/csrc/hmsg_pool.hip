@@ -596,6 +596,7 @@ static void pool_rows(hipStream_t s, DevBuf<unsigned>& scan_tmp, Prof* prof, Dbg
 }
 
 void hmsg_pool(hmsg_ctx* h) {
+    HMSG_NOT_RESTORED(h, "hmsg_pool_instances");
     const hmsg_config& c = h->cfg;
     hipStream_t s = h->stream;
     HMSG_REQUIRE(h->merged, HMSG_ERR_INVALID, "hmsg_pool_instances: run hmsg_merge_instances first");

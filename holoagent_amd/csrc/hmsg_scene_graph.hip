@@ -14,6 +14,7 @@
 #include "hmsg_dbscan.h"
 #include "hmsg_query.h"
 #include "hmsg_query_views.h"
+#include "hmsg_stage_files.h"
 
 #include <dirent.h>
 #include <sys/stat.h>
@@ -804,67 +805,13 @@ JVal read_json(const std::string& path) {
     if (v.kind != JVal::OBJ) throw hmsg_error{HMSG_ERR_INVALID, path + ": not a JSON object"};
     return v;
 }
-// Open3D read_point_cloud of the files this path writes (and of Open3D's own: double / float x y z first, other properties skipped)
+// Open3D read_point_cloud of the files this path writes (and of Open3D's own): hmsg_stage_files.h
 std::vector<double> read_ply(const std::string& path) {
-    FILE* f = fopen(path.c_str(), "rb");
-    if (!f) throw hmsg_error{HMSG_ERR_INVALID, "cannot open " + path};
+    std::vector<double> out;
+    std::string msg;
     long long n = 0;
-    struct Prop {
-        std::string type, name;
-    };
-    std::vector<Prop> props;
-    char line[512];
-    bool ok = false;
-    while (fgets(line, sizeof line, f)) {
-        std::string s(line);
-        while (!s.empty() && (s.back() == '\n' || s.back() == '\r')) s.pop_back();
-        if (s.rfind("element vertex", 0) == 0) n = atoll(s.c_str() + 14);
-        else if (s.rfind("property", 0) == 0) {
-            char t[64] = "", nm[64] = "";
-            if (sscanf(s.c_str(), "property %63s %63s", t, nm) == 2) props.push_back(Prop{t, nm});
-        } else if (s == "end_header") {
-            ok = true;
-            break;
-        }
-    }
-    if (!ok) {
-        fclose(f);
-        throw hmsg_error{HMSG_ERR_INVALID, path + ": no PLY header"};
-    }
-    size_t stride = 0;
-    int offx[3] = {-1, -1, -1};
-    bool dbl[3] = {true, true, true};
-    for (auto& pr : props) {
-        const size_t sz = pr.type == "double" ? 8 : (pr.type == "float" ? 4 : (pr.type == "uchar" ? 1 : 0));
-        if (!sz) {
-            fclose(f);
-            throw hmsg_error{HMSG_ERR_UNSUPPORTED, path + ": PLY property type " + pr.type};
-        }
-        for (int a = 0; a < 3; ++a)
-            if (pr.name == (a == 0 ? "x" : (a == 1 ? "y" : "z"))) offx[a] = (int)stride, dbl[a] = sz == 8;
-        stride += sz;
-    }
-    std::vector<double> out((size_t)n * 3);
-    std::vector<unsigned char> rec((size_t)n * stride);
-    if (n && fread(rec.data(), stride, (size_t)n, f) != (size_t)n) {
-        fclose(f);
-        throw hmsg_error{HMSG_ERR_INVALID, path + ": truncated PLY"};
-    }
-    fclose(f);
-    for (long long i = 0; i < n; ++i)
-        for (int a = 0; a < 3; ++a) {
-            if (offx[a] < 0) throw hmsg_error{HMSG_ERR_INVALID, path + ": PLY without x / y / z"};
-            const unsigned char* q = rec.data() + (size_t)i * stride + offx[a];
-            if (dbl[a]) {
-                double d;
-                memcpy(&d, q, 8);
-                out[(size_t)i * 3 + a] = d;
-            } else {
-                float fl;
-                memcpy(&fl, q, 4);
-                out[(size_t)i * 3 + a] = fl;
-            }
-        }
+    const int rc = stage_read_ply(path, true, &n, &out, &msg);
+    if (rc != STAGE_OK) throw hmsg_error{rc, msg};
     return out;
 }
 std::vector<std::string> list_dir(const std::string& dir, const char* suffix) {     // sorted(os.listdir(dir)) [endswith(suffix)]
@@ -1311,6 +1258,23 @@ int hmsg_save(hmsg_graph_t* g, const char* dir) {
                                               keep[b + 5].c_str()});
         }
         if (!recs.empty()) need(hmsg_save_objects(h, (root + "/objects").c_str(), (int64_t)recs.size(), recs.data(), g->prm.host_threads), h, "hmsg_save_objects");
+    });
+}
+
+/* the reader of hmsg_load, for a host that resumes from full_pcd.ply and objects/pcd_<i>.ply (hmsg_restore_stage) */
+int hmsg_read_ply(const char* path, double* xyz, int64_t capacity, int64_t* n) {
+    if (!path || !n || capacity < 0) return HMSG_ERR_INVALID;
+    *n = 0;
+    return hmsg_boundary("hmsg_read_ply", -1, [&] {
+        std::vector<double> pts;
+        std::string msg;
+        long long cnt = 0;
+        const int rc = stage_read_ply(path, xyz != nullptr, &cnt, &pts, &msg);
+        if (rc != STAGE_OK) throw hmsg_error{rc, msg};
+        *n = (int64_t)cnt;
+        if (!xyz) return;
+        HMSG_REQUIRE(cnt <= capacity, HMSG_ERR_INVALID, std::string(path) + ": more vertices than the capacity handed in");
+        if (cnt) memcpy(xyz, pts.data(), (size_t)cnt * 24);
     });
 }
 

@@ -582,6 +582,7 @@ class Graph:
         self.graph_path = _get(cfg, "main.graph_path")
         self._label_feats = None       # (text feats, class names) for identify_object
         self._K, self._poses = None, []
+        self._loaded = {}              # what load_full_pcd / load_full_pcd_feats / load_masked_pcds_new put into this Graph (restore_scene)
 
     # ------------------------------------------------------------------ text features
     def get_text_feats_multiple_templates(self, words: Sequence[str]) -> np.ndarray:
@@ -595,6 +596,17 @@ class Graph:
                 self._text_cache[w] = v
         return np.stack([self._text_cache[w] for w in words]).astype(np.float32)
 
+    def _scene_from_config(self, H, W, max_frames):
+        """a Scene with the pipeline.* keys of the config (graph.py:262-337)"""
+        p = lambda k, d=None: _get(self.cfg, "pipeline." + k, d)
+        merge = {"sequential": 0, "hierarchical": 1}[str(p("merge_type", "sequential"))]
+        return Scene(lib_=self.L, device_id=int(_get(self.cfg, "main.device_id", 0)), feat_dim=self.clip_feat_dim,
+                     height=H, width=W, max_frames=max_frames, max_masks=int(p("max_masks", 256)),
+                     voxel_size=float(p("voxel_size", 0.05)), init_overlap_thresh=float(p("init_overlap_thresh", 0.75)),
+                     overlap_thresh_factor=float(p("overlap_thresh_factor", 0.025)), iou_thresh=float(p("iou_thresh", 0.05)),
+                     clip_masked_weight=float(p("clip_masked_weight", 0.4418)),
+                     max_mask_distance=float(p("max_mask_distance", 10000)), merge_type=merge)
+
     # ------------------------------------------------------------------ build: graph.py:262-491
     def create_feature_map(self, save_path=None):
         if self.dataset is None:
@@ -606,13 +618,7 @@ class Graph:
         first = self.dataset[ids[0]]
         depth0 = np.asarray(first[1])
         H, W = depth0.shape[:2]
-        merge = {"sequential": 0, "hierarchical": 1}[str(p("merge_type", "sequential"))]
-        self.scene = Scene(lib_=self.L, device_id=int(_get(self.cfg, "main.device_id", 0)), feat_dim=self.clip_feat_dim,
-                           height=H, width=W, max_frames=len(ids), max_masks=int(p("max_masks", 256)),
-                           voxel_size=float(p("voxel_size", 0.05)), init_overlap_thresh=float(p("init_overlap_thresh", 0.75)),
-                           overlap_thresh_factor=float(p("overlap_thresh_factor", 0.025)), iou_thresh=float(p("iou_thresh", 0.05)),
-                           clip_masked_weight=float(p("clip_masked_weight", 0.4418)),
-                           max_mask_distance=float(p("max_mask_distance", 10000)), merge_type=merge)
+        self.scene = self._scene_from_config(H, W, len(ids))
         sc = self.scene
         B = 32
         self._poses, self._K = [], None
@@ -1155,10 +1161,69 @@ class Graph:
                 picks.append((i, fl.rooms[int(np.argmax(assoc))], int(names[i]) if names is not None else -1))
         return picks
 
+    # ------------------------------------------------------------------ resume from the stage artefacts
+    def _artefacts_loaded(self):
+        """map, instance clouds and instance features are what the three loaders left (nobody set one of them by hand since)"""
+        L = self._loaded
+        return (self.full_pcd is L.get("map") and self.mask_pcds is L.get("clouds") and self.mask_feats is L.get("feats")
+                and L.get("map") is not None and L.get("clouds") is not None and L.get("feats") is not None
+                and len(self.mask_pcds) == len(self.mask_feats))
+
+    def restore_scene(self):
+        """The resume order of the reference's build applications (semantic_scene_reconstruction.py:114-127: load_full_pcd,
+        load_full_pcd_feats, load_masked_pcds_new, then build_hier_multimodal_scene_graph) with the scene back in HBM: the loaded
+        map, instance clouds and instance features go into a Scene made from the config (hmsg_restore_stage), and this Graph is
+        afterwards where create_feature_map leaves one as far as the graph level can tell.  build_hier_multimodal_scene_graph calls it
+        by itself when everything came from the loaders; call it directly to have the device before that.
+        Image size, intrinsics and the poses of the processed frames come from the dataset; the frames' global features from
+        set_view_feats, else from the encoders, once per processed frame (graph.py:1119-1130 recomputes them at this point too)."""
+        if self.scene is not None:
+            raise RuntimeError("restore_scene: a scene is resident already")
+        if not self._artefacts_loaded():
+            raise RuntimeError("restore_scene: load_full_pcd, load_full_pcd_feats and load_masked_pcds_new first")
+        if self.dataset is None:
+            raise RuntimeError("restore_scene: no dataset (image size, intrinsics and poses come from it)")
+        skip = int(_get(self.cfg, "pipeline.skip_frames", 1))
+        ids = list(range(0, len(self.dataset), skip))
+        if len(self._view_feats) != len(ids) and self.encoders is None:
+            raise RuntimeError("restore_scene: no global feature per processed frame (%d given for %d frames) and no encoders to make "
+                               "them: call set_view_feats first" % (len(self._view_feats), len(ids)))
+        frames = [self.dataset[i] for i in ids]
+        first = frames[0]
+        shape = np.asarray(first[1] if first[1] is not None else first[0]).shape        # (create_feature_map sizes the scene by the depth image)
+        H, W = int(shape[0]), int(shape[1])
+        K = first[4] if len(first) > 4 and first[4] is not None else self.dataset.get_camera_intrinsics()
+        K = np.ascontiguousarray(np.asarray(K, dtype=np.float64))
+        if len(self._view_feats) != len(ids):
+            self._view_feats = [np.asarray(self.encoders.extract(np.asarray(_match_size(f[0], f[1]) if f[1] is not None else f[0]))["f_g"],
+                                           np.float32).reshape(1, -1) for f in frames]
+        feats = np.ascontiguousarray(np.asarray(self.mask_feats, np.float32).reshape(len(self.mask_pcds), -1))
+        map_feats = self._loaded.get("full_feats") if self.full_feats_array is self._loaded.get("full_feats") else None
+        map_pts = np.asarray(self.full_pcd.points, np.float64).reshape(-1, 3)
+        if map_feats is not None and np.asarray(map_feats).shape != (len(map_pts), self.clip_feat_dim):
+            map_feats = None
+        sc = self._scene_from_config(H, W, 1)
+        try:
+            sc.restore_stage(map_pts, [np.asarray(p.points, np.float64).reshape(-1, 3) for p in self.mask_pcds], feats, K, map_feats=map_feats)
+        except Exception:
+            sc.close()
+            raise
+        self.scene = sc
+        self._K, self._poses = K, [np.asarray(f[2], np.float64) for f in frames]
+        self._frame_ids = ids
+        self.full_pcd = _LazyFn(sc.map_points, sc.map_size())           # stays in HBM until read
+        self.take_instances()
+        self._loaded = {}
+        return sc
+
     def build_hier_multimodal_scene_graph(self, save_path=None, rooms: Sequence[dict] | None = None, room_regions=None):
         """graph.py:2033-2076 (navigation graph omitted).  Rooms: by default segment_hmsg_room per floor with the
         device room segmentation; `room_regions` = per floor a list of [n, 2] (x, z) region point arrays -> the same
         from the regions on (room clouds, room embeddings, View nodes); or `rooms` = ready-made room specs (set_rooms)."""
+        if self.scene is None and rooms is None and room_regions is None and self.dataset is not None and self._artefacts_loaded():
+            # everything came from load_full_pcd / load_full_pcd_feats / load_masked_pcds_new: the reference's resume order.  The
+            # host path below makes no rooms without a resident scene, so this case used to end without rooms and objects.
+            self.restore_scene()
         early = getattr(self, "_room_level", None)
         if early is not None and rooms is None and room_regions is None:
             early["thread"].join()
@@ -1270,6 +1335,7 @@ class Graph:
             print("full pcd not found in {}".format(path))
             return None
         self.full_pcd = _Pcd(_read_ply(os.path.join(path, "full_pcd.ply")))
+        self._loaded["map"] = self.full_pcd
         print("full pcd loaded from disk with shape {}".format(np.asarray(self.full_pcd.points).shape))
         return self.full_pcd
 
@@ -1300,6 +1366,7 @@ class Graph:
             self.full_feats_array = arr
         else:
             self.mask_feats = arr
+        self._loaded["full_feats" if full_feats else "feats"] = arr
         print("full pcd feats loaded from disk with shape {}".format(arr.shape))
         return arr
 
@@ -1339,7 +1406,11 @@ class Graph:
                 print("masked pcd {} not found in {}".format(i, path))
                 not_found.append(i)
         not_found = [i for i in not_found if i < len(self.mask_feats)]
+        from_loader = self.mask_feats is self._loaded.get("feats")
         self.mask_feats = np.delete(self.mask_feats, not_found, axis=0)
+        if from_loader:
+            self._loaded["feats"] = self.mask_feats
+        self._loaded["clouds"] = self.mask_pcds
         return self.mask_pcds
 
     def load_hmsg_graph(self, path):

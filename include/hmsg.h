@@ -216,6 +216,37 @@ int hmsg_merge_tree_join(hmsg_t* h, int32_t n_ext, const int64_t* ext_sizes, con
 int hmsg_pool_instances(hmsg_t* h);
 int hmsg_get_instance_feats(const hmsg_t* h, float* feats /*[N][D]*/);
 
+/* ---- A11 the other way: resume from the stage artefacts.  Replaces Graph.load_full_pcd + load_full_pcd_feats +
+ * load_masked_pcds_new (graph.py:3782-3990; the resume blocks of semantic_scene_reconstruction.py:114-127 and
+ * offline_mapping_create_hmsg_hm3d_benchmark.py:97-107) for a host that holds the arrays: the handle is afterwards in the state
+ * hmsg_pool_instances leaves it in, as far as the graph level can tell (hmsg_segment_floors / _rooms, hmsg_room_clouds,
+ * hmsg_build_object_nodes, hmsg_object_views, hmsg_graph_begin / _finish / hmsg_build_graph, hmsg_save, the queries, every getter
+ * of the map and the instances, hmsg_voxel_down_sample, hmsg_denoise_instances, hmsg_instance_room_share, hmsg_merge_room_objects,
+ * hmsg_index_from_nodes).  Every array is host or device memory.
+ *   map_xyz   f64 [V][3], V >= 1: ANY cloud -- it need not hold one point per voxel of a grid (a map written by the reference
+ *             loads: Open3D's grid origin, outlier filter applied); its order is kept;
+ *   map_rgb   f64 [V][3] or NULL (zeros);  map_feats f32 [V][D] or NULL (hmsg_get_map_feats then refuses), D = cfg.feat_dim;
+ *   inst_off  i64 [n_inst + 1], non-decreasing from 0; inst_xyz f64 [inst_off[n_inst]][3]; inst_feats f32 [n_inst][D];
+ *   K         f64 [9] row-major, the camera as hmsg_add_frames takes it.  Image width / height stay the handle's.
+ * An instance of size 0 is allowed: it gets no node (the `< 10` points rule of graph.py:1611-1620) and its box is six zeros (what
+ * an instance emptied by hmsg_denoise_instances has).  The boxes (hmsg_get_instance_boxes) are exact: numpy.min / max of the
+ * instance's rows bit for bit, -0.0 ordered below +0.0.
+ * HMSG_ERR_INVALID, the handle unchanged: the handle is not fresh (frames added, a map, a restore before: hmsg_reset first), a
+ * coordinate of the map or of an instance is not finite, inst_off is not non-decreasing from 0.
+ * On a restored handle hmsg_add_frames, hmsg_add_frame_features, hmsg_fuse_frames, hmsg_merge_instances, hmsg_merge_tree_local /
+ * _join, hmsg_pool_instances, hmsg_get_frame_nn / _fp / _mask_sizes / _mask_points, hmsg_get_feature_sums / hmsg_set_feature_sums
+ * and hmsg_allreduce_feature_sums return HMSG_ERR_INVALID ("... restored ...") without touching the device: there is no frame
+ * store and no voxel bitmap behind it.  hmsg_get_map_feats has no frame counter to give.  hmsg_reset makes it a fresh handle. */
+int hmsg_restore_stage(hmsg_t* h, int64_t V, const double* map_xyz, const double* map_rgb, const float* map_feats, int64_t n_inst,
+                       const int64_t* inst_off, const double* inst_xyz, const float* inst_feats, const double* K);
+/* The x y z of the vertex element of a binary little-endian PLY file (double or float properties; colours, normals and other
+ * elements are skipped): o3d.io.read_point_cloud(path).points for full_pcd.ply and objects/pcd_<i>.ply of save_full_pcd /
+ * save_masked_pcds (graph.py:3718-3780), the reader hmsg_load uses.  *n = number of vertices; xyz == NULL: the count only, else
+ * HMSG_ERR_INVALID when capacity < *n.  xyz is host memory.  HMSG_ERR_INVALID for a file that cannot be opened, has no complete
+ * header or fewer bytes than its header promises; HMSG_ERR_UNSUPPORTED for ascii / big-endian files and list properties of the
+ * vertex element. */
+int hmsg_read_ply(const char* path, double* xyz /*[capacity][3] or NULL*/, int64_t capacity, int64_t* n);
+
 /* ---- A8: the storeys of the map -- Graph.segment_floors_manually (graph.py:624-787): the map re-sampled at 5 cm, the
  * height histogram at 1 cm (device), gaussian_filter1d(sigma = 2) on the int64 counts, find_peaks(distance = 20 bins,
  * height = 90th percentile), the 1-D DBSCAN(eps = 1 m) chaining of the peaks and the reference's pick / adjust rules
