@@ -25,6 +25,7 @@
 //   HMSG_DEBUG_NOANCHOR=1 disables (3) (tests compare the two folds bit for bit).
 #include "hmsg_boundary.h"
 #include "hmsg_cloudops.h"
+#include "hmsg_fold_host.h"
 
 #include <algorithm>
 #include <cmath>
@@ -582,24 +583,7 @@ __global__ void k_concat(const double* __restrict__ pool, const CatSeg* __restri
 }
 
 // ------------------------------------------------------------------------------------------ candidate pairs of a level batch
-// AABB IoU of two boxes (graph_utils.py:883-915), the ONE statement of it: the host's pair loop (bbox_iou) and the pair kernels
-// below evaluate this function, in float64, without contraction (the file is built with -ffp-contract=off), so a pair is a
-// candidate on the device exactly when it is one on the host.  The selections are written out as the comparisons std::max /
-// std::min make, not as fmax / fmin.
-__host__ __device__ inline double box_iou(const double* amn, const double* amx, const double* bmn, const double* bmx) {
-    // boxes disjoint along an axis: overlap volume 0 -> IoU 0 (or 0/0): never > iou_thresh (>= 0 by contract)
-    if (amx[0] <= bmn[0] || bmx[0] <= amn[0] || amx[1] <= bmn[1] || bmx[1] <= amn[1] || amx[2] <= bmn[2] || bmx[2] <= amn[2])
-        return 0.0;
-    double ov = 1, va = 1, vb = 1;
-    for (int k = 0; k < 3; ++k) {
-        const double omin = amn[k] < bmn[k] ? bmn[k] : amn[k], omax = bmx[k] < amx[k] ? bmx[k] : amx[k];
-        const double d = omax - omin;
-        ov *= d < 0.0 ? 0.0 : d;
-        va *= amx[k] - amn[k];
-        vb *= bmx[k] - bmn[k];
-    }
-    return ov / (va + vb - ov);   // 0/0 -> NaN -> comparison false, like numpy
-}
+// (box_iou, the ONE statement of the AABB IoU for the host's pair loops and the pair kernels below: hmsg_fold_host.h)
 
 // The pairs (i, j), i < j, of one group with box_iou > iou_thresh, for every group of a batch: boxes [n][6] = (min xyz, max xyz),
 // an empty cloud as (+1e300, -1e300) so that the early reject drops it.  One workgroup per (group, tile of GP_TILE rows), a row
@@ -717,31 +701,6 @@ struct GroupPairs {
 
 double bbox_iou(const Cloud& a, const Cloud& b) {   // graph_utils.py:883-915; empty cloud -> (0,0,0) box
     return box_iou(a.mn, a.mx, b.mn, b.mx);
-}
-
-// cm[j] = box j meets the query box q = {lo0, hi0, lo1, hi1, lo2, hi2} with positive extent on every axis
-// (thousands of boxes per fresh cloud per step: compiled for AVX2 when the host has it)
-#define HMSG_BOX_MASK_BODY                                                                                          \
-    for (int j = 0; j < n; ++j)                                                                                     \
-        cm[j] = (unsigned char)!((q[1] <= lo0[j]) | (hi0[j] <= q[0]) | (q[3] <= lo1[j]) | (hi1[j] <= q[2]) |        \
-                                 (q[5] <= lo2[j]) | (hi2[j] <= q[4]));
-#if !defined(__HIP_DEVICE_COMPILE__) && defined(__x86_64__)
-__attribute__((target("avx2"))) void box_mask_avx2(int n, const double* lo0, const double* hi0, const double* lo1,
-                                                   const double* hi1, const double* lo2, const double* hi2, const double* q,
-                                                   unsigned char* cm) {
-    HMSG_BOX_MASK_BODY
-}
-#endif
-void box_mask(int n, const double* lo0, const double* hi0, const double* lo1, const double* hi1, const double* lo2,
-              const double* hi2, const double* q, unsigned char* cm) {
-#if !defined(__HIP_DEVICE_COMPILE__) && defined(__x86_64__)
-    static const bool have_avx2 = __builtin_cpu_supports("avx2");
-    if (have_avx2) {
-        box_mask_avx2(n, lo0, hi0, lo1, hi1, lo2, hi2, q, cm);
-        return;
-    }
-#endif
-    HMSG_BOX_MASK_BODY
 }
 
 struct IntSpan {
@@ -1112,10 +1071,14 @@ struct Merger {
         if (second_ran) second_ran->assign(pairs.size(), 0);
         if (pairs.empty()) return;
         const size_t P = pairs.size();
+        const auto pack_t0 = std::chrono::steady_clock::now();
         // compact table of the clouds involved
-        std::vector<int> slot(L.size(), -1);
-        std::vector<OvGrid> g;
-        std::vector<OvTask> tasks(P * 2);          // [0, P): smaller -> larger,  [P, 2P): larger -> smaller
+        std::vector<int>& slot = ws_slot;          // (kept between steps, like the pair search's buffers)
+        std::vector<OvGrid>& g = ws_grids;
+        std::vector<OvTask>& tasks = ws_tasks;     // [0, P): smaller -> larger,  [P, 2P): larger -> smaller
+        slot.assign(L.size(), -1);
+        g.clear();
+        tasks.resize(P * 2);
         unsigned nblk1 = 0, nblk2 = 0;          // workgroups of the two directions (work lists)
         for (size_t k = 0; k < P; ++k) {
             int a = pairs[k].first, b = pairs[k].second;
@@ -1153,6 +1116,7 @@ struct Merger {
             }
         }
         upload_pinned(d_ovpack.p, h_ovpack.p, pack, s);
+        t_ovpack += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - pack_t0).count();
         const OvGrid* const dg = (const OvGrid*)d_ovpack.p;
         const OvTask* const dt = (const OvTask*)(d_ovpack.p + off_t);
         unsigned* const dc = (unsigned*)(d_ovpack.p + off_c);
@@ -1270,65 +1234,10 @@ struct Merger {
             for (int i = 0; i < n; ++i)
                 for (int j = i + 1; j < n; ++j) consider(i, j);
         } else {
-            // shortcut (2): only pairs with a fresh member; enumerate from the (few) fresh clouds
-            // (AABBs in SoA form: the reject test -- boxes disjoint on some axis, overlap volume 0 -- is the hot loop)
-            // Round 6: the fresh clouds of a step -- a frame's masks and what the last step changed -- sit in the camera's view, the
-            // list holds the whole scene: ONE pass keeps the clouds whose box meets the fresh clouds' common box, the per-cloud
-            // passes then run over those (a tenth of the list at configs[1]); buffers are kept between steps.
-            std::vector<double>* lo = fp_lo;
-            std::vector<double>* hi = fp_hi;
-            for (int a = 0; a < 3; ++a) {
-                lo[a].resize((size_t)n);
-                hi[a].resize((size_t)n);
-            }
-            fp_fr.resize((size_t)n);
-            fp_cand.assign((size_t)n + 8, 0);
-            std::vector<unsigned char>& fr = fp_fr;
-            double u[6] = {1e300, -1e300, 1e300, -1e300, 1e300, -1e300};
-            for (int j = 0; j < n; ++j) {
-                fr[(size_t)j] = L[j].fresh ? 1 : 0;
-                for (int a = 0; a < 3; ++a) {
-                    lo[a][(size_t)j] = L[j].n ? L[j].mn[a] : 1e300;      // empty clouds never pair
-                    hi[a][(size_t)j] = L[j].n ? L[j].mx[a] : -1e300;
-                }
-                if (fr[(size_t)j] && L[j].n)
-                    for (int a = 0; a < 3; ++a) {
-                        u[2 * a] = std::min(u[2 * a], L[j].mn[a]);
-                        u[2 * a + 1] = std::max(u[2 * a + 1], L[j].mx[a]);
-                    }
-            }
-            if (!(u[0] <= u[1])) return;                        // no fresh cloud with points
-            box_mask(n, lo[0].data(), hi[0].data(), lo[1].data(), hi[1].data(), lo[2].data(), hi[2].data(), u, fp_cand.data());
-            fp_sub.clear();
-            for (int j = 0; j < n; ++j)
-                if (fp_cand[(size_t)j]) fp_sub.push_back(j);
-            const int m = (int)fp_sub.size();
-            for (int a = 0; a < 3; ++a) {
-                fp_slo[a].resize((size_t)m);
-                fp_shi[a].resize((size_t)m);
-                for (int q = 0; q < m; ++q) {
-                    fp_slo[a][(size_t)q] = lo[a][(size_t)fp_sub[(size_t)q]];
-                    fp_shi[a][(size_t)q] = hi[a][(size_t)fp_sub[(size_t)q]];
-                }
-            }
-            fp_cand.assign((size_t)m + 8, 0);
-            for (int i = 0; i < n; ++i) {
-                if (!fr[(size_t)i] || L[i].n == 0) continue;
-                // branch-free mask pass (vectorised), then a sparse walk over the few survivors
-                unsigned char* cm = fp_cand.data();
-                const double q[6] = {lo[0][(size_t)i], hi[0][(size_t)i], lo[1][(size_t)i], hi[1][(size_t)i], lo[2][(size_t)i], hi[2][(size_t)i]};
-                box_mask(m, fp_slo[0].data(), fp_shi[0].data(), fp_slo[1].data(), fp_shi[1].data(), fp_slo[2].data(), fp_shi[2].data(), q, cm);
-                for (int j0 = 0; j0 < m; j0 += 8) {
-                    unsigned long long w;
-                    std::memcpy(&w, cm + j0, 8);               // cand is padded to a multiple of 8
-                    if (!w) continue;
-                    for (int jq = j0; jq < std::min(j0 + 8, m); ++jq) {
-                        const int j = fp_sub[(size_t)jq];
-                        if (!cm[jq] || j == i || (fr[(size_t)j] && j < i)) continue;
-                        consider(std::min(i, j), std::max(i, j));
-                    }
-                }
-            }
+            // shortcut (2): only pairs with a fresh member, enumerated from the (few) fresh clouds over the AABBs in SoA form:
+            // the reference enumerator of hmsg_fold_host.h (buffers are kept between steps)
+            fold_fill_boxes(L, 0, fp_tab);
+            fold_pairs_reference(fp_tab, iou_thresh, fp_scratch, pairs);
         }
     }
     // (find_pairs' buffers, kept between steps)
@@ -1336,16 +1245,55 @@ struct Merger {
     std::vector<double> gp_box;
     bool gp_wanted = getenv("HMSG_DEBUG_TREE_HOST_PAIRS") == nullptr;   // HMSG_DEBUG_TREE_HOST_PAIRS=1: a level batch's pairs by the host's loop
     double gp_device_batches = 0, gp_host_batches = 0;                  // (statistics: which way the level batches' pairs were listed)
-    std::vector<double> fp_lo[3], fp_hi[3], fp_slo[3], fp_shi[3];
-    std::vector<unsigned char> fp_fr, fp_cand;
-    std::vector<int> fp_sub;
+    FoldBoxTable fp_tab;
+    FoldPairScratch fp_scratch;
+    // (merge_3d_masks' and make_components' vectors, kept between steps)
+    std::vector<std::pair<int, int>> ws_pairs, ws_known_pairs;
+    std::vector<double> ws_known, ws_ratio;
+    std::vector<unsigned char> ws_second_ran;
+    CompList ws_comps;
+    std::vector<int> ws_seg_of_comp, ws_seg_cap, ws_spec_code, ws_spec_first, ws_parent, ws_comp_of, ws_cid, ws_cur;
+    std::vector<long long> ws_spec_pt;
+    std::vector<int> ws_slot;
+    std::vector<OvGrid> ws_grids;
+    std::vector<OvTask> ws_tasks;
+    std::vector<SegDesc> ws_segs;
+    std::vector<CatSeg> ws_cat;
+    std::vector<DbscanResult> ws_res;
+    // ---- the sequential fold's pairs in two parts (hmsg_fold_host.h: FoldPlan).  SeqFold turns it on and names the next frame's masks
+    // before every step; every other caller of merge_3d_masks -- the hierarchical merge, the merge tree -- gets the reference enumerator.
+    //   HMSG_FOLD_HOST_AHEAD=0: the fold as it was, every pair enumerated at the start of the step and the list rebuilt per step;
+    //   HMSG_DEBUG_FOLD_PAIRS_CHECK=1: the reference list is computed as well, every step, and any difference fails the call.
+    // (read when the merger is made: tests switch them between two folds of one process)
+    FoldPlan plan;
+    bool plan_wanted = false;                            // SeqFold: this merger folds frames in sequence
+    bool plan_enabled = !(getenv("HMSG_FOLD_HOST_AHEAD") && atoi(getenv("HMSG_FOLD_HOST_AHEAD")) == 0);
+    bool plan_check = getenv("HMSG_DEBUG_FOLD_PAIRS_CHECK") != nullptr && atoi(getenv("HMSG_DEBUG_FOLD_PAIRS_CHECK")) != 0;
+    const std::vector<Cloud>* next_masks = nullptr;      // the frame the NEXT step folds, when it is known already (one step only)
+    double t_ovpack = 0;                                 // host time to fill and send the overlap pack (part of the overlap lap; ms)
+    double t_ahead_hidden = 0;                           // host time of advance + plan_ahead spent behind a DBSCAN batch's publish (ms)
+    FoldPairList chk_pairs;
+    void planned_pairs(const std::vector<Cloud>& L, FoldPairList& pairs) {
+        const int n = (int)L.size();
+        plan.step_pairs(L, iou_thresh, pairs);
+        if (plan_check) {
+            fold_fill_boxes(L, 0, fp_tab);
+            chk_pairs.clear();
+            fold_pairs_reference(fp_tab, iou_thresh, fp_scratch, chk_pairs);
+            bool same = plan.tab.n == n;
+            for (int i = 0; same && i < n; ++i) same = plan.tab.same(i, fp_tab, i);
+            HMSG_REQUIRE(same, HMSG_ERR_INVALID, "merge fold: the kept box table differs from the cloud list");
+            HMSG_REQUIRE(pairs == chk_pairs, HMSG_ERR_INVALID, "merge fold: the planned pair list differs from the reference enumerator's");
+        }
+    }
 
     // ---- components of `overlap > th` (scipy connected_components labels by lowest member index)
     void make_components(const std::vector<Cloud>& L, const std::vector<std::pair<int, int>>& pairs, const std::vector<double>& ratio,
                          const std::vector<std::pair<int, int>>& known_pairs, const std::vector<double>& known, double th,
                          CompList& comps) {
         const int n = (int)L.size();
-        std::vector<int> parent(n);
+        std::vector<int>& parent = ws_parent;
+        parent.resize((size_t)n);
         std::iota(parent.begin(), parent.end(), 0);
         auto find = [&](int x) {
             while (parent[x] != x) x = parent[x] = parent[parent[x]];
@@ -1364,7 +1312,9 @@ struct Merger {
             if (known[k] > th) unite(known_pairs[k].first, known_pairs[k].second);
         // (flat CSR: thousands of clouds per step, nearly all singletons -- no per-component allocations)
         {
-            std::vector<int> comp_of(n, -1), cid(n);
+            std::vector<int>&comp_of = ws_comp_of, &cid = ws_cid, &cur = ws_cur;
+            comp_of.assign((size_t)n, -1);
+            cid.resize((size_t)n);
             int nc = 0;
             for (int i = 0; i < n; ++i) {
                 int r = find(i);
@@ -1375,7 +1325,7 @@ struct Merger {
             for (int i = 0; i < n; ++i) ++comps.off[cid[i] + 1];
             for (int c = 0; c < nc; ++c) comps.off[c + 1] += comps.off[c];
             comps.mem.resize(n);
-            std::vector<int> cur(comps.off.begin(), comps.off.end() - 1);
+            cur.assign(comps.off.begin(), comps.off.end() - 1);
             for (int i = 0; i < n; ++i) comps.mem[cur[cid[i]]++] = i;
         }
     }
@@ -1399,16 +1349,23 @@ struct Merger {
         };
         if (want_stats)
             for (auto& c : L) c.has_index_before = c.has_index;
+        const bool planned = plan_wanted && plan_enabled && !use_cache && !group_off;
+        const std::vector<Cloud>* const masks_ahead = planned ? next_masks : nullptr;
+        next_masks = nullptr;
         build_indices(L);
         lap(0);
-        // 1. candidate pairs
-        std::vector<std::pair<int, int>> pairs;
-        std::vector<double> known;                 // cached ratios (hierarchical)
-        std::vector<std::pair<int, int>> known_pairs;
-        find_pairs(L, pairs, known, known_pairs, group_off);
-        std::vector<double> ratio;
+        // 1. candidate pairs   (the vectors of a step are members, reused from step to step: ws_*)
+        std::vector<std::pair<int, int>>& pairs = ws_pairs;
+        std::vector<double>& known = ws_known;     // cached ratios (hierarchical)
+        std::vector<std::pair<int, int>>& known_pairs = ws_known_pairs;
+        pairs.clear();
+        known.clear();
+        known_pairs.clear();
+        if (planned) planned_pairs(L, pairs);
+        else find_pairs(L, pairs, known, known_pairs, group_off);
+        std::vector<double>& ratio = ws_ratio;
         lap(1);
-        std::vector<unsigned char> second_ran;
+        std::vector<unsigned char>& second_ran = ws_second_ran;
         overlap_ratios(L, pairs, ratio, use_cache ? -1.0 : th, want_stats ? &second_ran : nullptr);
         lap(2);
         if (want_stats) {
@@ -1442,15 +1399,19 @@ struct Merger {
             }
         }
         // 2. components of `overlap > th`
-        CompList comps;
+        CompList& comps = ws_comps;
         make_components(L, pairs, ratio, known_pairs, known, th, comps);
         // 3. merge_point_clouds_list per component: concat in index order + keep-largest DBSCAN
-        std::vector<int> seg_of_comp(comps.size(), -1);
-        std::vector<SegDesc> segs;
-        std::vector<int> seg_cap;                  // per segment: capacity of its output region (0: dense output)
+        std::vector<int>& seg_of_comp = ws_seg_of_comp;
+        seg_of_comp.assign(comps.size(), -1);
+        std::vector<SegDesc>& segs = ws_segs;
+        std::vector<int>& seg_cap = ws_seg_cap;    // per segment: capacity of its output region (0: dense output)
+        segs.clear();
+        seg_cap.clear();
         long long region_total = 0;                // points of the fresh output regions (SegDesc::out_mode 1)
         const bool inplace = use_anchor && inplace_wanted && CloudOps::regions_supported();
-        std::vector<CatSeg> cat;
+        std::vector<CatSeg>& cat = ws_cat;
+        cat.clear();
         long long cat_total = 0;
         unsigned cat_blocks = 0;
         for (size_t c = 0; c < comps.size(); ++c) {
@@ -1528,7 +1489,28 @@ struct Merger {
             seg_of_comp[c] = (int)segs.size();
             segs.push_back(sd);
         }
-        std::vector<DbscanResult> res;
+        std::vector<DbscanResult>& res = ws_res;
+        // The fold's next list is known from here on but for the outputs of the batch: the box table moves on to it and, when the
+        // next frame's masks are there, their pairs are enumerated -- behind the batch's publish, while the host would only spin;
+        // right here when the step has no batch (or the batch calls nothing back).
+        bool advanced = false;
+        auto advance_plan = [&](bool hidden) {
+            if (!planned || advanced) return;
+            advanced = true;
+            const auto a0 = tnow();
+            plan.advance(comps.off.data(), comps.mem.data(), (int)comps.size(), seg_of_comp.data());
+            if (masks_ahead) {
+                for (const Cloud& c : *masks_ahead) plan.append(c.mn, c.mx, c.n);
+                plan.plan_ahead(iou_thresh);
+            }
+            const auto a1 = tnow();
+            if (hidden) {
+                t_ahead_hidden += std::chrono::duration<double, std::milli>(a1 - a0).count();
+            } else {                            // (on the chain: it counts as pair time, not as the lap it happens to fall into)
+                tphase[1] += std::chrono::duration<double, std::milli>(a1 - a0).count();
+                t0 += a1 - a0;
+            }
+        };
         // pool layout of the step's outputs: [fresh regions of the mode-1 segments | dense outputs of the mode-0 segments]
         long long dense_total = 0;
         for (auto& sd : segs) {
@@ -1557,9 +1539,11 @@ struct Merger {
             const bool speculate = spec_wanted && CloudOps::regions_supported();
             ops.dbscan_keep_largest(concat.p, segs, eps, minpts, pool.p + (size_t)out_base * 3, res,
                                     use_anchor ? (const unsigned char*)concat_core.p : nullptr, poolcore.p + out_base, &ga,
-                                    speculate ? std::function<void(const unsigned*, int)>([&](const unsigned* d_res, int K) {
-                                        speculate_indices(L, comps, seg_of_comp, segs, out_base, d_res, K);
+                                    (speculate || planned) ? std::function<void(const unsigned*, int)>([&](const unsigned* d_res, int K) {
+                                        if (speculate) speculate_indices(L, comps, seg_of_comp, segs, out_base, d_res, K);
+                                        advance_plan(true);
                                     }) : std::function<void(const unsigned*, int)>());
+            advance_plan(false);
             lap(4);
             if (want_stats) {
                 for (size_t c = 0; c < comps.size(); ++c) {
@@ -1622,11 +1606,15 @@ struct Merger {
             res.assign(segs.size(), DbscanResult{});
             spec.clear();
             spec_of_seg.assign(segs.size(), -1);
+            advance_plan(false);
         }
         // the grids built behind the batch: which of them exist (the device's decisions, replayed from the results) and how much
         // of the arenas they took -- sorted points densely one grid after the other, cells as laid out up to the last grid in use
-        std::vector<int> spec_code(spec.size(), 0), spec_first(spec.size(), 0);
-        std::vector<long long> spec_pt(spec.size(), 0);
+        std::vector<int>&spec_code = ws_spec_code, &spec_first = ws_spec_first;
+        std::vector<long long>& spec_pt = ws_spec_pt;
+        spec_code.assign(spec.size(), 0);
+        spec_first.assign(spec.size(), 0);
+        spec_pt.assign(spec.size(), 0);
         {
             long long pts = 0, cells_end = 0;
             for (size_t j = 0; j < spec.size(); ++j) {
@@ -1650,13 +1638,27 @@ struct Merger {
             ix_cells_used += cells_end;
             ix_pts_used += pts;
         }
-        // 4. new list in component order
+        // 4. new list in component order.  The sequential fold (planned) updates the list where it is: component c's output takes
+        // place c -- c <= the component's lowest member and every member of a later component lies behind it, so nothing that
+        // is still to be read gets overwritten, and the nineteen untouched singletons in twenty only have their flags set.
         std::vector<Cloud> out;
-        out.reserve(comps.size());
+        if (!planned) out.reserve(comps.size());
+        auto put = [&](size_t c, const Cloud& k) {
+            if (planned) {
+                L[c] = k;
+                plan.resolve((int)c, k.mn, k.mx, k.n, k.fresh);
+            } else {
+                out.push_back(k);
+            }
+        };
         long long cursor = out_base;
         for (size_t c = 0; c < comps.size(); ++c) {
             const auto& mem = comps[c];
             int sg = seg_of_comp[c];
+            if (sg < 0 && planned) {            // untouched singleton, in place
+                fold_keep_untouched(L, c, (size_t)mem[0]);
+                continue;
+            }
             if (sg < 0) {                       // untouched singleton
                 Cloud k = L[mem[0]];
                 k.fresh = false;
@@ -1673,7 +1675,7 @@ struct Merger {
                 k.off = cursor;                 // the identical copy DBSCAN just wrote: it carries the core flags
                 k.cap = k.n;
                 k.anchor = r.n_clusters == 1;
-                out.push_back(k);
+                put(c, k);
                 cursor += r.n_out;
                 continue;
             }
@@ -1739,10 +1741,16 @@ struct Merger {
                 take_base();
                 k.has_index = k.nb == k.n;
             }
-            out.push_back(k);
+            put(c, k);
             if (!mode) cursor += r.n_out;
         }
         pool_used = cursor;
+        if (planned) {
+            HMSG_REQUIRE(plan.resolved(), HMSG_ERR_INVALID, "merge fold: an output of the step was not entered into the box table");
+            L.resize(comps.size());
+            lap(5);
+            return L;
+        }
         if (out_group_off) {
             // output cloud c came from component c, whose members all lie in the list of its first one
             const int G = (int)group_off->size() - 1;
@@ -1980,8 +1988,11 @@ static void fold_report(Folder& m, hmsg_ctx* h) {
 
 static void merge_report(Folder& m) {
     if (getenv("HMSG_DEBUG_TIMING"))
-        fprintf(stderr, "[hmsg merge] index %.1f  pairs(host) %.1f  overlap %.1f  components+concat %.1f  dbscan %.1f  bookkeeping %.1f ms\n",
-                m.tphase[0], m.tphase[1], m.tphase[2], m.tphase[3], m.tphase[4], m.tphase[5]);
+        fprintf(stderr, "[hmsg merge] index %.1f  pairs(host) late (on the chain) %.1f  ahead (hidden) %.1f  overlap %.1f (pack fill %.1f)  components+concat %.1f  dbscan %.1f  bookkeeping %.1f ms\n",
+                m.tphase[0], m.tphase[1], m.t_ahead_hidden, m.tphase[2], m.t_ovpack, m.tphase[3], m.tphase[4], m.tphase[5]);
+    if (getenv("HMSG_DEBUG_TIMING") && m.plan_wanted)
+        fprintf(stderr, "[hmsg merge] pair lists: %.0f steps merged from an ahead and a late part, %.0f enumerated whole after the results\n",
+                m.plan.n_ahead_steps, m.plan.n_late_only_steps);
     if (m.want_stats) {
         const auto& t = m.st;
         const double S = std::max(1.0, t.steps);
@@ -2056,6 +2067,7 @@ struct SeqFold {
         switch_points = getenv("HMSG_FOLD_INCREMENTAL") ? 0.0 : 1500000.0;
         if (const char* e = getenv("HMSG_FOLD_SWITCH")) switch_points = atof(e);
         if (const char* e = getenv("HMSG_FOLD_BIG_ACTIVE")) m.big_active = atoll(e);   // (development: which components take the batch kernels)
+        m.plan_wanted = true;
     }
     // the 3-D masks of `nm.size()` more frames: npts points at src (device; complete on the fold's stream or synchronised),
     // off[i] .. off[i + 1] = points of mask i (relative to src), nm[f] = masks of frame f.  reserve: pool room per point.
@@ -2132,6 +2144,7 @@ struct SeqFold {
         if (m.needs_collect()) {
             m.collect(G, frames, f);
             prebuilt_upto = f;
+            m.plan.drop_ahead();                 // (after a collection the step's pairs come from the reference enumerator)
         }
         if (f >= prebuilt_upto) {
             const size_t b = std::min(frames.size(), f + Merger::PREBUILD_WINDOW);
@@ -2140,6 +2153,9 @@ struct SeqFold {
         }
         G.insert(G.end(), frames[f].begin(), frames[f].end());
         std::vector<Cloud>().swap(frames[f]);
+        // (the next frame's masks, if they have been ingested: their pairs with what this step leaves untouched are enumerated
+        //  while its DBSCAN batch runs.  The fold beside the fusion gets frames 64 at a time; the last step of a batch has none.)
+        m.next_masks = f + 1 < frames.size() ? &frames[f + 1] : nullptr;
         G = m.merge_3d_masks(std::move(G), c.init_overlap_thresh);
     }
     // the last pass (graph_utils.py:1033-1037), the small-cloud drop (graph.py:445-448), instances into the handle
