@@ -76,6 +76,10 @@ class HmsgGraphView(C.Structure):      # include/hmsg.h: hmsg_graph_view
     _fields_ = [("view", C.c_int32), ("room", C.c_int32), ("img_id", C.c_int64), ("n_objects", C.c_int32), ("reserved_", C.c_int32)]
 
 
+class HmsgClipPreprocess(C.Structure):   # include/hmsg.h: hmsg_clip_preprocess
+    _fields_ = [("size", C.c_int32), ("out_f16", C.c_int32), ("mean", C.c_float * 3), ("std", C.c_float * 3)]
+
+
 class HmsgError(RuntimeError):
     pass
 
@@ -174,6 +178,9 @@ _SIGS = {
     "hmsg_points_min_dist_2d": (C.c_int, [C.c_int32, C.c_int32, _P, _P, C.c_int64, _P, _P]),
     "hmsg_lidar_depth": (C.c_int, [C.c_int32, _P, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "hmsg_crop_resize_batch": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, C.c_double, C.c_int32, _P, _P, _P]),
+    "hmsg_clip_default_preprocess": (None, [_P]),
+    "hmsg_clip_preprocess_batch": (C.c_int, [C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "hmsg_frame_encoder_inputs": (C.c_int, [C.c_int32, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, C.c_double, C.c_int32, _P, _P]),
     "hmsg_save_objects": (C.c_int, [_P, C.c_char_p, C.c_int64, _P, C.c_int32]),
     "hmsg_graph_allgather_index": (C.c_int, [_P, _P, _P, C.POINTER(_P), _P, _P, _P]),
     "hmsg_graph_query_sharded": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P,
@@ -1368,6 +1375,71 @@ def crop_all_bounding_boxs(image, masks, bbox_margin=0, size=512, plain=True, ma
     if rc != 0:
         raise HmsgError(f"hmsg_crop_resize_batch failed ({rc})")
     return o_plain, o_masked
+
+
+def _clip_params(L, size, f16, mean, std):
+    p = HmsgClipPreprocess()
+    L.c.hmsg_clip_default_preprocess(C.byref(p))
+    p.size, p.out_f16 = int(size), int(bool(f16))
+    if mean is not None:
+        p.mean[:] = [float(v) for v in mean]
+    if std is not None:
+        p.std[:] = [float(v) for v in std]
+    return p
+
+
+def clip_preprocess(images, size=224, f16=False, mean=None, std=None, return_u8=False, device_id=0, lib_: "HmsgLib | None" = None):
+    """open_clip's inference `preprocess` -- Resize(size, BICUBIC), CenterCrop(size), ToTensor, Normalize -- on the device, equal
+    to it in every bit (include/hmsg.h: hmsg_clip_preprocess_batch; utils/clip_utils.py:72-73, 88-89).  images: uint8 [H, W, 3]
+    or [B, H, W, 3], a numpy array or a torch tensor on the device.  Returns [.., 3, size, size] float32 (float16 with f16), of
+    the kind that came in; with return_u8 also the resized and centre-cropped bytes [.., size, size, 3]."""
+    L = lib_ or lib()
+    on_dev = hasattr(images, "data_ptr")
+    if on_dev:
+        import torch
+        assert images.dtype == torch.uint8 and images.is_cuda
+        images = images.contiguous()
+        device_id = images.device.index or 0
+    else:
+        images = np.ascontiguousarray(images, dtype=np.uint8)
+    single = images.ndim == 3
+    shape = tuple(images.shape)
+    assert len(shape) in (3, 4) and shape[-1] == 3, "images: [H, W, 3] or [B, H, W, 3]"
+    B, (H, W) = (1 if single else shape[0]), shape[-3:-1]
+    S = int(size)
+    if on_dev:
+        out = torch.empty((B, 3, S, S), dtype=torch.float16 if f16 else torch.float32, device=images.device)
+        u8 = torch.empty((B, S, S, 3), dtype=torch.uint8, device=images.device) if return_u8 else None
+    else:
+        out = np.empty((B, 3, S, S), np.float16 if f16 else np.float32)
+        u8 = np.empty((B, S, S, 3), np.uint8) if return_u8 else None
+    p = _clip_params(L, size, f16, mean, std)
+    rc = L.c.hmsg_clip_preprocess_batch(device_id, C.byref(p), B, H, W, _ptr(images), _ptr(out), _ptr(u8), None)
+    if rc != 0:
+        raise HmsgError(f"hmsg_clip_preprocess_batch failed ({rc})")
+    if single:
+        out, u8 = out[0], (u8[0] if return_u8 else None)
+    return (out, u8) if return_u8 else out
+
+
+def frame_encoder_inputs(image, masks, bbox_margin=0, size=224, crop_size=512, f16=False, mean=None, std=None, device_id=0,
+                         lib_: "HmsgLib | None" = None):
+    """The 1 + 2 M encoder inputs of one frame (include/hmsg.h: hmsg_frame_encoder_inputs; sam_clip_feats_extractor.py:147-158):
+    row 0 the whole frame, rows 1..M the masked crops, rows M + 1..2 M the plain crops, each through clip_preprocess.  `masks`:
+    SAM records as crop_all_bounding_boxs takes them.  Returns a numpy array [1 + 2 M, 3, size, size]."""
+    L = lib_ or lib()
+    image = np.ascontiguousarray(image, dtype=np.uint8)
+    H, W = image.shape[:2]
+    M = len(masks)
+    bbox = np.ascontiguousarray([m["bbox"] for m in masks], dtype=np.float64).reshape(M, 4)
+    segs = np.ascontiguousarray(np.stack([m["segmentation"] for m in masks]).astype(np.uint8)) if M else None
+    out = np.empty((1 + 2 * M, 3, int(size), int(size)), np.float16 if f16 else np.float32)
+    p = _clip_params(L, size, f16, mean, std)
+    rc = L.c.hmsg_frame_encoder_inputs(device_id, C.byref(p), H, W, _ptr(image), M, _ptr(segs), _ptr(bbox) if M else None,
+                                       float(bbox_margin), int(crop_size), _ptr(out), None)
+    if rc != 0:
+        raise HmsgError(f"hmsg_frame_encoder_inputs failed ({rc})")
+    return out
 
 
 class NodeIndex:

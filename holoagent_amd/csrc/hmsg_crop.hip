@@ -10,6 +10,7 @@
 // exactly that per output pixel (the four taps come through L1 / L2; a crop's source window is a few hundred KB).
 // The launch is bound by the HBM WRITE of the crops: 2 M S^2 3 bytes per frame (50 MB at M = 32, S = 512).
 #include "hmsg_boundary.h"
+#include "hmsg_crop.h"
 
 #include <cmath>
 
@@ -142,6 +143,58 @@ inline void clip_slice(long long a, long long n, int L, int& start, int& len) {
 
 }  // namespace
 
+// The rectangles of a frame's crops: host work only, and the one place that refuses an empty crop -- both entry points call
+// it before they create a stream, stage an array or launch anything.
+void hmsg_crop_rects(int H, int W, int M, const double* bbox, double bbox_margin, bool want_plain, bool want_masked,
+                     hmsg_crop_scratch& scratch) {
+    std::vector<CropRect> rects;
+    for (int v = 0; v < 2; ++v) {
+        if (!(v ? want_masked : want_plain)) continue;
+        for (int m = 0; m < M; ++m) {
+            double x = bbox[m * 4], y = bbox[m * 4 + 1], w = bbox[m * 4 + 2], h = bbox[m * 4 + 3];
+            if (v == 0) {                       // crop_bbox: increase_bbox_by_margin (sam_utils.py:67-81)
+                x -= bbox_margin;
+                y -= bbox_margin;
+                w += bbox_margin * 2;
+                h += bbox_margin * 2;
+                if (x < 0) {
+                    w += x;
+                    x = 0;
+                }
+                if (y < 0) {
+                    h += y;
+                    y = 0;
+                }
+            }
+            CropRect r{0, 0, 0, 0, v ? m : -1, m, v, 0};
+            const bool finite = std::fabs(x) < 1e15 && std::fabs(y) < 1e15 && std::fabs(w) < 1e15 && std::fabs(h) < 1e15;   // (NaN fails)
+            const long long xi = finite ? (long long)x : -1, yi = finite ? (long long)y : -1, wi = finite ? (long long)w : 0,
+                            hi = finite ? (long long)h : 0;                                                // int(): toward zero
+            if (xi >= 0 && yi >= 0 && wi > 0 && hi > 0) {
+                clip_slice(xi, wi, W, r.x0, r.w);
+                clip_slice(yi, hi, H, r.y0, r.h);
+            }
+            HMSG_REQUIRE(r.w > 0 && r.h > 0, HMSG_ERR_INVALID,
+                         "mask " + std::to_string(m) + " has an empty " + (v ? "masked" : "bounding-box") + " crop (cv2.resize raises on it)");
+            rects.push_back(r);
+        }
+    }
+    scratch.host.resize(rects.size() * sizeof(CropRect));       // (the source of an asynchronous copy: it outlives this function)
+    memcpy(scratch.host.data(), rects.data(), scratch.host.size());
+}
+// the table goes up on s ...
+void hmsg_crop_upload(hmsg_crop_scratch& scratch, hipStream_t s) {
+    scratch.dev.alloc(scratch.host.size());
+    HIP_TRY(hipMemcpyAsync(scratch.dev.p, scratch.host.data(), scratch.host.size(), hipMemcpyHostToDevice, s));
+}
+// ... and the one launch (image / segs / out_*: device memory; the outputs asked for in hmsg_crop_rects)
+void hmsg_crop_launch(int H, int W, const unsigned char* p_img, const unsigned char* p_seg, int out_size, unsigned char* p_plain,
+                      unsigned char* p_masked, const hmsg_crop_scratch& scratch, hipStream_t s) {
+    hipLaunchKernelGGL(k_crop_resize, dim3(cdiv((size_t)out_size, CROP_ROWS), (unsigned)(scratch.host.size() / sizeof(CropRect))), dim3(256), 0, s,
+                       p_img, p_seg, H, W, (const CropRect*)scratch.dev.p, out_size, p_plain, p_masked);
+    HMSG_CHECK_LAUNCH();
+}
+
 extern "C" int hmsg_crop_resize_batch(int32_t device_id, int32_t H, int32_t W, const uint8_t* image, int32_t M, const uint8_t* segs,
                                       const double* bbox, double bbox_margin, int32_t out_size, uint8_t* out_plain,
                                       uint8_t* out_masked, double* device_ms) {
@@ -149,53 +202,19 @@ extern "C" int hmsg_crop_resize_batch(int32_t device_id, int32_t H, int32_t W, c
     if (out_masked && !segs) return HMSG_ERR_INVALID;
     if (M == 0 || (!out_plain && !out_masked)) return HMSG_OK;
     return hmsg_boundary("hmsg_crop_resize_batch", device_id, [&] {
-        std::vector<CropRect> rects;
-        for (int v = 0; v < 2; ++v) {
-            if (!(v ? out_masked : out_plain)) continue;
-            for (int m = 0; m < M; ++m) {
-                double x = bbox[m * 4], y = bbox[m * 4 + 1], w = bbox[m * 4 + 2], h = bbox[m * 4 + 3];
-                if (v == 0) {                       // crop_bbox: increase_bbox_by_margin (sam_utils.py:67-81)
-                    x -= bbox_margin;
-                    y -= bbox_margin;
-                    w += bbox_margin * 2;
-                    h += bbox_margin * 2;
-                    if (x < 0) {
-                        w += x;
-                        x = 0;
-                    }
-                    if (y < 0) {
-                        h += y;
-                        y = 0;
-                    }
-                }
-                CropRect r{0, 0, 0, 0, v ? m : -1, m, v, 0};
-                const bool finite = std::fabs(x) < 1e15 && std::fabs(y) < 1e15 && std::fabs(w) < 1e15 && std::fabs(h) < 1e15;   // (NaN fails)
-                const long long xi = finite ? (long long)x : -1, yi = finite ? (long long)y : -1, wi = finite ? (long long)w : 0,
-                                hi = finite ? (long long)h : 0;                                                // int(): toward zero
-                if (xi >= 0 && yi >= 0 && wi > 0 && hi > 0) {
-                    clip_slice(xi, wi, W, r.x0, r.w);
-                    clip_slice(yi, hi, H, r.y0, r.h);
-                }
-                HMSG_REQUIRE(r.w > 0 && r.h > 0, HMSG_ERR_INVALID,
-                             "mask " + std::to_string(m) + " has an empty " + (v ? "masked" : "bounding-box") + " crop (cv2.resize raises on it)");
-                rects.push_back(r);
-            }
-        }
+        hmsg_crop_scratch rects;
+        hmsg_crop_rects(H, W, M, bbox, bbox_margin, out_plain != nullptr, out_masked != nullptr, rects);
         ScopedStream s(hipStreamNonBlocking);
         ScopedEvent ev0, ev1;
         const size_t S = (size_t)out_size, crop_bytes = S * S * 3, img_bytes = (size_t)H * W * 3, seg_bytes = (size_t)M * H * W;
         DevBuf<unsigned char> d_img, d_seg, d_plain, d_masked;
-        DevBuf<CropRect> d_rects;
         const unsigned char* p_img = stage_in(d_img, image, img_bytes, s, Up::direct);
         const unsigned char* p_seg = out_masked ? stage_in(d_seg, segs, seg_bytes, s, Up::direct) : segs;
         unsigned char* p_plain = stage_out(d_plain, out_plain, crop_bytes * M);
         unsigned char* p_masked = stage_out(d_masked, out_masked, crop_bytes * M);
-        d_rects.alloc(rects.size());
-        HIP_TRY(hipMemcpyAsync(d_rects.p, rects.data(), rects.size() * sizeof(CropRect), hipMemcpyHostToDevice, s));
+        hmsg_crop_upload(rects, s);
         HIP_TRY(hipEventRecord(ev0, s));
-        hipLaunchKernelGGL(k_crop_resize, dim3(cdiv(S, CROP_ROWS), (unsigned)rects.size()), dim3(256), 0, s, p_img, p_seg, H, W,
-                           (const CropRect*)d_rects.p, out_size, p_plain, p_masked);
-        HMSG_CHECK_LAUNCH();
+        hmsg_crop_launch(H, W, p_img, p_seg, out_size, p_plain, p_masked, rects, s);
         HIP_TRY(hipEventRecord(ev1, s));
         unstage_out(out_plain, p_plain, crop_bytes * M, s);
         unstage_out(out_masked, p_masked, crop_bytes * M, s);

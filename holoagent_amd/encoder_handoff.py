@@ -110,3 +110,30 @@ def measure(L, scene, inp, device, torch, frames=8, crop=224, feat_dim=512):
                 crops_ms_per_frame=round(t_crop / F * 1e3, 3), encoder_ms_per_frame=round(t_enc / F * 1e3, 3),
                 handoff_ms_per_frame=round(t_hand / F * 1e3, 3), tensors_on_device=bool(on_device),
                 note="hmsg_crop_resize_batch -> torch module -> hmsg_add_frame_features by data_ptr(): no host copy of masks or features")
+
+
+def embed_frame_reference_inputs(L, enc, image, seg, bbox, torch, bbox_margin=50.0, crop_size=512, size=224, f16=True, mean=None,
+                                 std=None):
+    """One frame's F_g, F_masked, F_crop from the encoder inputs the reference makes (sam_clip_feats_extractor.py:147-158 with
+    clip_utils.py:72-73, 88-89): the frame and its 2 M crops of crop_size, each through open_clip's `preprocess`, bit for bit
+    (include/hmsg.h: hmsg_frame_encoder_inputs), as ONE [1 + 2 M, 3, size, size] tensor written by device pointer; the module
+    runs once on it.  image u8 [H, W, 3] and seg u8 [M, H, W]: device tensors; bbox: SAM's XYWH records, host, [M, 4].
+    Returns (f_g [1, D], f_masked [M, D], f_crop [M, D]), L2-normalised float32 on the device, ready for
+    Scene.add_frame_features(f, seg[None], f_g, f_masked[None], f_crop[None])."""
+    from ._lib import HmsgError, _clip_params, _ptr
+    assert image.dtype == torch.uint8 and image.is_cuda and image.dim() == 3 and image.shape[2] == 3, "image: uint8 [H, W, 3] on the device"
+    assert seg.dtype == torch.uint8 and seg.device == image.device and seg.dim() == 3, "seg: uint8 [M, H, W] on the image's device"
+    image, seg = image.contiguous(), seg.contiguous()         # (the library reads them by pointer, as dense arrays)
+    H, W = image.shape[:2]
+    M = int(seg.shape[0])
+    assert tuple(seg.shape[1:]) == (H, W)
+    bbox = np.ascontiguousarray(bbox, dtype=np.float64).reshape(M, 4)
+    x = torch.empty((1 + 2 * M, 3, size, size), dtype=torch.float16 if f16 else torch.float32, device=image.device)
+    prm = _clip_params(L, size, f16, mean, std)
+    rc = L.c.hmsg_frame_encoder_inputs(image.device.index or 0, C.byref(prm), H, W, _ptr(image), M, _ptr(seg) if M else None,
+                                       _ptr(bbox) if M else None, float(bbox_margin), int(crop_size), _ptr(x), None)
+    if rc != 0:
+        raise HmsgError(f"hmsg_frame_encoder_inputs failed ({rc})")
+    with torch.no_grad():
+        f = torch.nn.functional.normalize(enc(x).float(), dim=-1)
+    return f[:1].contiguous(), f[1:1 + M].contiguous(), f[1 + M:].contiguous()

@@ -438,6 +438,48 @@ int hmsg_crop_resize_batch(int32_t device_id, int32_t H, int32_t W, const uint8_
                            const double* bbox, double bbox_margin, int32_t out_size, uint8_t* out_plain, uint8_t* out_masked,
                            double* device_ms);
 
+/* ---- N4b (encoder side): open_clip's inference `preprocess` on the device.  The reference sends every one of a frame's 2 M
+ * crops and the frame itself through it, one PIL image at a time on the host, before the image tower
+ * (utils/clip_utils.py:72-73, 88-89; called from perception/models/sam_clip_feats_extractor.py:147-158), and graph.py:1127 makes
+ * the room level's per-frame view embedding through the same transform:
+ *     Resize(S, BICUBIC) -> CenterCrop(S) -> ToTensor -> Normalize(mean, std)
+ * What is pinned, bit for bit:
+ *   - Pillow 12.2's 8-bit BICUBIC resample (ImagingResample): a horizontal pass, a uint8 image, a vertical pass; double
+ *     coefficients rounded to 1 / 2^22, integer accumulation, (sum + 2^21) >> 22 clamped to 0..255; a pass whose input and
+ *     output lengths are equal is skipped (a copy);
+ *   - torchvision's size rules: Resize(S) makes the shorter side S and the other int(S * long / short); CenterCrop(S) starts at
+ *     int(round((n - S) / 2.0)) with Python's round (halves to even);
+ *   - ToTensor + Normalize in float32: ((float)u8 / 255.0f - mean[c]) / std[c], channel-first; float16 output is the
+ *     round-to-nearest-even of that float32.
+ * torchvision's and open_clip's composition is taken from their documented behaviour; Pillow's arithmetic is what the tests
+ * check against the installed Pillow.  Coefficients are made on the host per call; the device does integer work only. */
+typedef struct {
+    int32_t size;       /* S: output side, 1..1024 (224) */
+    int32_t out_f16;    /* 0: float32 output, else float16 */
+    float mean[3];
+    float std[3];       /* finite and non-zero */
+} hmsg_clip_preprocess;
+/* 224, float32, the OpenAI constants (0.48145466, 0.4578275, 0.40821073) / (0.26862954, 0.26130258, 0.27577711) */
+void hmsg_clip_default_preprocess(hmsg_clip_preprocess* p);
+/* B images of one shape, u8 [B][H][W][3] -> out [B][3][S][S] (float32, or float16 with out_f16) = preprocess(Image.fromarray(img)).
+ * out_u8 (optional) u8 [B][S][S][3]: the resized and centre-cropped bytes, = np.asarray(CenterCrop(S)(Resize(S)(img))).
+ * images / out / out_u8 may be host or device pointers.  B = 0 is HMSG_OK.  HMSG_ERR_INVALID (before any device work): a null
+ * prm / images / out, B < 0, H or W < 1, size outside 1..1024, a non-finite mean or std, std = 0.  HMSG_ERR_UNSUPPORTED: a source
+ * side above 16384, B above 65535, or a down-scale so large that the source rows of one output row do not fit the kernel's LDS.
+ * device_ms (optional): HIP-event time of the launch. */
+int hmsg_clip_preprocess_batch(int32_t device_id, const hmsg_clip_preprocess* prm, int32_t B, int32_t H, int32_t W,
+                               const uint8_t* images, void* out, uint8_t* out_u8, double* device_ms);
+/* One frame's 1 + 2 M encoder inputs in one call (sam_clip_feats_extractor.py:147-158 with clip_utils.py:72-73, 88-89):
+ * out [1 + 2 M][3][S][S], row 0 the whole frame (F_g's input), rows 1..M the masked crops, rows M + 1..2 M the plain crops --
+ * the order hmsg_add_frame_features takes their features in.  The crops are exactly what hmsg_crop_resize_batch(out_size =
+ * crop_size, 512 in the reference) makes (same kernel), held in a scratch buffer of the call, then preprocessed like any image.
+ * Arguments as in hmsg_crop_resize_batch (image, segs, out: host or device; bbox: host); crop_size a multiple of 4.  A mask with
+ * an empty crop is HMSG_ERR_INVALID, as there, and like every refusal of this call it comes before anything is staged or launched.
+ * device_ms (optional): HIP-event time of the three launches (the tables are made and sent up before the first event). */
+int hmsg_frame_encoder_inputs(int32_t device_id, const hmsg_clip_preprocess* prm, int32_t H, int32_t W, const uint8_t* image,
+                              int32_t M, const uint8_t* segs, const double* bbox, double bbox_margin, int32_t crop_size,
+                              void* out, double* device_ms);
+
 /* ---- A11: the other node records of save_hmsg_graph (graph.py:1801-1824) -- floors/<f>.{ply,json} (floor.py:37-52),
  * rooms/<f>_<r>.{ply,json} (room.py:309-337), views/<id>.json (view.py:56-74) -- from a C / C++ host, byte for byte what
  * json.dump writes: one JSON object per call, fields in the order given (the reference's key order).  A field is either RAW
