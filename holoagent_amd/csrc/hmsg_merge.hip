@@ -1065,10 +1065,13 @@ struct Merger {
     // ---- overlap ratios for a list of (i, j) pairs of L.  `decide_th` >= 0 (sequential merge): only `ratio > th`
     // is needed downstream, so the pair's smaller cloud is counted first and the scan of the larger one is skipped on
     // the device when the first ratio already exceeds the threshold (its entry then reports the first ratio).
+    // `raw_counts` (optional; the test hook hmsg_test_overlap): the count words as the device left them -- [k] points of pair k's
+    // smaller cloud with a witness, [P + k] the same of the larger one, or 0x80000000 where the box bound decided that direction.
     void overlap_ratios(const std::vector<Cloud>& L, const std::vector<std::pair<int, int>>& pairs, std::vector<double>& ratio,
-                        double decide_th, std::vector<unsigned char>* second_ran = nullptr) {
+                        double decide_th, std::vector<unsigned char>* second_ran = nullptr, std::vector<unsigned>* raw_counts = nullptr) {
         ratio.assign(pairs.size(), 0.0);
         if (second_ran) second_ran->assign(pairs.size(), 0);
+        if (raw_counts) raw_counts->clear();
         if (pairs.empty()) return;
         const size_t P = pairs.size();
         const auto pack_t0 = std::chrono::steady_clock::now();
@@ -1169,6 +1172,7 @@ struct Merger {
         pub_counts.launch(s, (const unsigned*)dc, tasks.size());
         pub_counts.wait();
         const unsigned* hc = pub_counts.data();
+        if (raw_counts) raw_counts->assign(hc, hc + 2 * P);
         // Algorithmic bytes of the step (merge): `sum over bbox-overlapping pairs (n_A + n_B) * 12` -- the float32 points
         // of both clouds of every pair the filter passes, each read once.  What the implementation skips (the larger cloud's scan
         // when the smaller one's ratio decides, or when the box bound does) is its own cleverness, not a smaller problem.
@@ -1772,6 +1776,24 @@ struct Merger {
 
 namespace {
 
+// How far a witness can be, and the grids' cell side with it, for clouds whose coordinates lie in [lo, hi] (merger_init: the map
+// grid's bounds; hmsg_test_overlap, whose handle has no map: the joint box of its clouds).  Needs m.radius and m.faiss_form.
+void merger_set_reach(Merger& m, const double* lo, const double* hi) {
+    m.reach = m.radius;
+    if (m.faiss_form) {
+        // |x|^2 + |y|^2 - 2 x.y in float32: three 3-term sums of magnitude <= M2 = max |p|^2 over the map, each within 3 ulp,
+        // then two more roundings of numbers <= 2 M2: the value is within E = 16 * 2^-24 * M2 of the true squared distance, so
+        // a point up to sqrt(radius^2 + E) away can still compare below radius^2 -- the grids must reach that far
+        double m2 = 0.0;
+        for (int a = 0; a < 3; ++a) {
+            const double v = std::max(std::fabs(lo[a]), std::fabs(hi[a])) + 1.0;
+            m2 += v * v;
+        }
+        m.reach = std::sqrt(m.radius * m.radius + 16.0 * 5.9604644775390625e-08 * m2);
+    }
+    m.cell = m.reach * (1.0 + 1e-3) + 2e-3;
+}
+
 void merger_init(Merger& m, hmsg_ctx* h) {
     const hmsg_config& c = h->cfg;
     m.h = h;
@@ -1779,22 +1801,11 @@ void merger_init(Merger& m, hmsg_ctx* h) {
     m.ops.s = h->stream;
     m.ops.prof = &h->prof;
     m.radius = 1.5 * c.voxel_size;
-    m.reach = m.radius;
     m.faiss_form = c.overlap_distance_form == HMSG_OVERLAP_FAISS_BLAS ? 1 : 0;
-    if (m.faiss_form) {
-        // |x|^2 + |y|^2 - 2 x.y in float32: three 3-term sums of magnitude <= M2 = max |p|^2 over the map, each within 3 ulp,
-        // then two more roundings of numbers <= 2 M2: the value is within E = 16 * 2^-24 * M2 of the true squared distance, so
-        // a point up to sqrt(radius^2 + E) away can still compare below radius^2 -- the grids must reach that far
-        const GridGeom& g = h->grid;
-        double m2 = 0.0;
-        const double lo[3] = {g.ox, g.oy, g.oz}, ext[3] = {g.nx * g.vs, g.ny * g.vs, g.nz * g.vs};
-        for (int a = 0; a < 3; ++a) {
-            const double v = std::max(std::fabs(lo[a]), std::fabs(lo[a] + ext[a])) + 1.0;
-            m2 += v * v;
-        }
-        m.reach = std::sqrt(m.radius * m.radius + 16.0 * 5.9604644775390625e-08 * m2);
-    }
-    m.cell = m.reach * (1.0 + 1e-3) + 2e-3;
+    const GridGeom& g = h->grid;
+    const double lo[3] = {g.ox, g.oy, g.oz}, ext[3] = {g.nx * g.vs, g.ny * g.vs, g.nz * g.vs};
+    const double hi[3] = {lo[0] + ext[0], lo[1] + ext[1], lo[2] + ext[2]};
+    merger_set_reach(m, lo, hi);
     m.eps = c.merge_dbscan_eps;
     m.minpts = c.merge_dbscan_min;
     m.iou_thresh = c.iou_thresh;
@@ -2508,6 +2519,105 @@ extern "C" int hmsg_test_group_pairs(int32_t device_id, int64_t n, const double*
             *n_pairs = np;
             const long long m = std::min<long long>(np, capacity);
             if (m) memcpy(pairs_out, pr, (size_t)m * 8);
+        }
+    });
+}
+
+// ---- test hook (include/hmsg_test.h: hmsg_test_overlap): Merger::overlap_ratios on host clouds, with the grids a merge would have
+// made for them -- a cloud with n_base[k] < sizes[k] gets its base grid while it holds its first n_base[k] points only, then grows
+extern "C" int hmsg_test_overlap(hmsg_t* h, int32_t K, const int64_t* sizes, const int64_t* n_base, const double* pts, int64_t P,
+                                 const int32_t* pairs, double decide_th, uint32_t* out_counts, uint8_t* out_state, double* out_ratio) {
+    if (!h) return HMSG_ERR_INVALID;
+    return hmsg_boundary(h, [&] {
+        HMSG_REQUIRE(K >= 0 && P >= 0 && P <= 0x3fffffffll && (K == 0 || sizes) && (P == 0 || (pairs && out_counts && out_state && out_ratio)),
+                     HMSG_ERR_INVALID, "hmsg_test_overlap: bad argument");
+        HMSG_REQUIRE(decide_th == decide_th, HMSG_ERR_INVALID, "hmsg_test_overlap: decide_th is not a number");
+        long long total = 0;
+        for (int k = 0; k < K; ++k) {
+            HMSG_REQUIRE(sizes[k] >= 0 && sizes[k] <= 0x7fffffffll, HMSG_ERR_INVALID, "hmsg_test_overlap: bad cloud size");
+            HMSG_REQUIRE(!n_base || sizes[k] == 0 || (n_base[k] >= 1 && n_base[k] <= sizes[k]), HMSG_ERR_INVALID,
+                         "hmsg_test_overlap: n_base must lie in [1, size] for every cloud that has points");
+            total += sizes[k];
+        }
+        HMSG_REQUIRE(total <= 0x7fffffffll && (total == 0 || pts), HMSG_ERR_INVALID, "hmsg_test_overlap: bad argument");
+        std::vector<std::pair<int, int>> pr((size_t)P);
+        for (int64_t k = 0; k < P; ++k) {
+            const int a = pairs[2 * k], b = pairs[2 * k + 1];
+            HMSG_REQUIRE(a >= 0 && a < K && b >= 0 && b < K && a != b, HMSG_ERR_INVALID, "hmsg_test_overlap: a pair names no cloud, or one cloud twice");
+            HMSG_REQUIRE(sizes[a] > 0 && sizes[b] > 0, HMSG_ERR_INVALID, "hmsg_test_overlap: a pair names an empty cloud (the merge never pairs one)");
+            pr[(size_t)k] = std::make_pair(a, b);
+        }
+        if (P == 0) return;
+        Merger m;
+        merger_init(m, h);
+        m.pool.alloc((size_t)std::max<long long>(total * 2, 1 << 16) * 3);
+        m.poolcore.alloc((size_t)std::max<long long>(total * 2, 1 << 16));
+        copy_in(m.pool.p, pts, (size_t)total * 24, h->stream, Up::direct);
+        m.pool_used = total;
+        // boxes: of every cloud, and of the first n_base points of every cloud that grows
+        std::vector<SegDesc> segs((size_t)K);
+        std::vector<int> base_seg((size_t)K, -1);
+        long long at = 0;
+        for (int k = 0; k < K; ++k) {
+            segs[(size_t)k].pt_base = at;
+            segs[(size_t)k].n = (int)sizes[k];
+            at += sizes[k];
+        }
+        for (int k = 0; k < K; ++k)
+            if (n_base && sizes[k] > 0 && n_base[k] < sizes[k]) {
+                base_seg[(size_t)k] = (int)segs.size();
+                SegDesc sd;
+                sd.pt_base = segs[(size_t)k].pt_base;
+                sd.n = (int)n_base[k];
+                segs.push_back(sd);
+            }
+        m.ops.bounds(m.pool.p, segs);
+        double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};          // (the handle has no map: the BLAS form's reach from the clouds' joint box)
+        bool any = false;
+        for (int k = 0; k < K; ++k) {
+            if (segs[(size_t)k].n == 0) continue;
+            for (int a = 0; a < 3; ++a) {
+                lo[a] = any ? std::min(lo[a], segs[(size_t)k].mn[a]) : segs[(size_t)k].mn[a];
+                hi[a] = any ? std::max(hi[a], segs[(size_t)k].mx[a]) : segs[(size_t)k].mx[a];
+            }
+            any = true;
+        }
+        merger_set_reach(m, lo, hi);
+        std::vector<Cloud> L((size_t)K);                      // (cloud numbers are list positions: empty clouds stay in the list)
+        auto set_from = [&](Cloud& c, const SegDesc& sd) {
+            c.off = sd.pt_base;
+            c.n = sd.n;
+            for (int a = 0; a < 3; ++a) {
+                c.mn[a] = sd.mn[a];
+                c.mx[a] = sd.mx[a];
+            }
+        };
+        for (int k = 0; k < K; ++k) {
+            set_from(L[(size_t)k], segs[(size_t)(base_seg[(size_t)k] >= 0 ? base_seg[(size_t)k] : k)]);
+            L[(size_t)k].uid = m.next_uid++;
+        }
+        m.build_indices(L);
+        m.spin.wait(m.s);                                      // (h_grids is re-used by the next call)
+        // the clouds that grow: the base grid stays, laid out on the box it was built on; what came behind it goes into a delta grid
+        for (int k = 0; k < K; ++k)
+            if (base_seg[(size_t)k] >= 0) {
+                Cloud& c = L[(size_t)k];
+                set_from(c, segs[(size_t)k]);
+                c.has_index = false;
+            }
+        m.delta_always = true;
+        m.build_indices(L);
+        std::vector<double> ratio;
+        std::vector<unsigned> raw;
+        m.overlap_ratios(L, pr, ratio, decide_th, nullptr, &raw);
+        for (size_t k = 0; k < (size_t)P; ++k) {
+            const int na = std::min(L[(size_t)pr[k].first].n, L[(size_t)pr[k].second].n);
+            const bool bounded = (raw[(size_t)P + k] & 0x80000000u) != 0;
+            const bool first_decides = decide_th >= 0.0 && (double)raw[k] / (double)na > decide_th;
+            out_counts[2 * k] = raw[k];
+            out_counts[2 * k + 1] = raw[(size_t)P + k] & 0x7fffffffu;
+            out_state[k] = first_decides ? 1 : (bounded ? 2 : 0);
+            out_ratio[k] = ratio[k];
         }
     });
 }

@@ -76,6 +76,25 @@ int hmsg_test_kmeans_lloyd(int32_t on_device, int32_t device_id, const float* X,
 int hmsg_test_group_pairs(int32_t device_id, int64_t n, const double* boxes, int32_t n_groups, const int64_t* group_off,
                           double iou_thresh, int32_t* pairs_out, int64_t capacity, int64_t* n_pairs);
 
+/* test hook: the overlap counting of instance merging (find_overlapping_ratio_faiss, utils/graph_utils.py:620-662) through the
+ * merge's own host code: the clouds go into a merger's point pool, get their overlap grids, and the pairs go through the same
+ * work lists, launches and read-back as a fold step's.  h: a created handle -- voxel_size (radius = 1.5 * voxel_size) and
+ * overlap_distance_form come from its config; it needs no map and is left as it was.
+ *   K clouds of sizes[k] points, concatenated in pts (host, f64 [sum][3]).
+ *   n_base ([K] or NULL): cloud k's first n_base[k] points (1 .. sizes[k]) go into its BASE grid, laid out on the box of those
+ *     points alone; the points behind them into a DELTA grid on the whole cloud's box -- the grids of a cloud that has grown
+ *     since it was indexed.  NULL, or n_base[k] == sizes[k]: one grid.
+ *   pairs i32 [P][2]: cloud numbers, two different non-empty clouds each (anything else: HMSG_ERR_INVALID).
+ *   decide_th < 0: value mode (hierarchical merge: both directions of every pair are counted); >= 0: decision mode (sequential
+ *     merge: only `ratio > decide_th` matters, a direction that cannot change it may be left out).
+ *   out_counts u32 [P][2]: points of the pair's SMALLER cloud (of equal sizes: the pair's first) with a point of the other cloud
+ *     closer than the radius, then the same of the larger cloud (0 where that direction was not scanned).
+ *   out_state u8 [P]: 0 the second direction was scanned, 1 left out because the first ratio alone exceeds decide_th, 2 decided by
+ *     the box bound (fewer than decide_th * n points of the larger cloud lie near the smaller one's box).
+ *   out_ratio f64 [P]: what the merge goes on with, max of the two ratios. */
+int hmsg_test_overlap(hmsg_t* h, int32_t K, const int64_t* sizes, const int64_t* n_base, const double* pts, int64_t P,
+                      const int32_t* pairs, double decide_th, uint32_t* out_counts, uint8_t* out_state, double* out_ratio);
+
 #ifdef __cplusplus
 }
 #endif
