@@ -219,23 +219,16 @@ __global__ void k_mark(const unsigned short* __restrict__ depth, const double* _
     }
 }
 
-struct VoxAcc {                 // per-slot colour / count accumulators (SoA)
-    unsigned long long* sr;
-    unsigned long long* sg;
-    unsigned long long* sb;
-    unsigned* n;
-};
-
 // ---- ordered voxel sums (A2) -------------------------------------------------------------------------------
 // Open3D's VoxelDownSample adds the points of a voxel in INPUT order (frame-major, pixel row-major here:
 // graph.py:339-348) in float64, and the nearest-neighbour decisions downstream hinge on the last bit of the
 // centroids, so the sums are taken in exactly that order:
-//   k_slots      pixel -> voxel slot (u32, kept for phase 2), colours / counts per run with integer atomics,
-//                number of runs per 4096-pixel chunk.  A run = consecutive pixels of one image row (inside one
-//                64-pixel wave slice) that fall into the same voxel (~8 pixels).
+//   k_slots      pixel -> voxel slot (u32, kept for phase 2), number of runs per 4096-pixel chunk.  A run = consecutive
+//                pixels of one image row (inside one 64-pixel wave slice) that fall into the same voxel (~8 pixels).
 //   k_emit_runs  run records (key = slot, value = frame << 32 | row << 20 | first column << 8 | length) in input order
 //   stable sort by slot (hmsg_sort.hip), segment starts
-//   k_accum_ordered  one lane per voxel walks its runs in order: back-project again, s += p, centroid = s / n
+//   k_accum_ordered  one wave per voxel walks its runs in order: back-project again, s += p, centroid = s / n; the voxel's
+//                colour sums (integers: exact in any order) and its pixel count ride along, colour = (sum / 255) / n
 #define RUN_CHUNK 4096
 __device__ __forceinline__ unsigned pixel_slot(const unsigned short* __restrict__ depth, const double* __restrict__ T /* the frame's pose */,
                                                const CamK& cam, float scale, size_t i, int x, int y, const GridGeom& g,
@@ -249,64 +242,51 @@ __device__ __forceinline__ unsigned pixel_slot(const unsigned short* __restrict_
     return rank[lin >> 6] + (unsigned)__popcll(word & ((1ull << (lin & 63)) - 1ull));
 }
 
-__global__ void __launch_bounds__(256) k_slots(const unsigned short* __restrict__ depth, const unsigned char* __restrict__ rgb,
-                                               const double* __restrict__ pose, CamK cam, float scale, int H, int W, int F,
-                                               GridGeom g, const unsigned long long* __restrict__ bitmap,
-                                               const unsigned* __restrict__ rank, VoxAcc acc, unsigned* __restrict__ slots,
-                                               unsigned* __restrict__ chunk_runs) {
+// Where the runs of a wave's 64 pixels begin and end, stated once for k_slots (which counts them) and k_emit_runs (which writes
+// them): a run begins where the slot changes, at column 0 and at lane 0; it ends on the lane before the next beginning and on lane
+// 63.  Runs of invalid pixels (slot 0xffffffff) have no tail: they are not counted and not emitted.  A wave collective: every lane
+// of the wave calls it (pixels beyond the scene: slot 0xffffffff, x = 0).
+struct RunEdges {
+    unsigned long long heads, tails;   // one bit per lane
+    bool tail;                         // this lane ends a run of valid pixels
+};
+__device__ __forceinline__ RunEdges run_edges(unsigned slot, int x, int lane) {
+    const unsigned prev = __shfl_up(slot, 1);
+    const bool head = lane == 0 || prev != slot || x == 0;
+    RunEdges e;
+    e.heads = __ballot(head);
+    e.tail = (lane == 63 || ((e.heads >> (lane + 1)) & 1ull)) && slot != 0xffffffffu;
+    e.tails = __ballot(e.tail);
+    return e;
+}
+
+__global__ void __launch_bounds__(256) k_slots(const unsigned short* __restrict__ depth, const double* __restrict__ pose, CamK cam,
+                                               float scale, int H, int W, int F, GridGeom g,
+                                               const unsigned long long* __restrict__ bitmap, const unsigned* __restrict__ rank,
+                                               unsigned* __restrict__ slots, unsigned* __restrict__ chunk_runs) {
     __shared__ unsigned s_runs;
     if (threadIdx.x == 0) s_runs = 0u;
     __syncthreads();
     const size_t HW = (size_t)H * W;
     const size_t total = HW * F;
     const int lane = threadIdx.x & 63;
-    unsigned myruns = 0;
+    unsigned myruns = 0;                                             // (wave-uniform)
     const PixWalk pw = pix_walk((size_t)blockIdx.x * RUN_CHUNK, HW, W);
     const size_t left = total - (size_t)blockIdx.x * RUN_CHUNK;
     const unsigned fl = pix_last_frame(pw, (unsigned)(left < (size_t)RUN_CHUNK ? left : (size_t)RUN_CHUNK));
     for (int it = 0; it < RUN_CHUNK / 256; ++it) {
         const size_t i = (size_t)blockIdx.x * RUN_CHUNK + (size_t)it * 256 + threadIdx.x;
-        const bool in_range = i < total;
         unsigned slot = 0xffffffffu;
-        unsigned cr = 0, cg = 0, cb = 0, cn = 0;
         int x = 0;
-        if (in_range) {
+        if (i < total) {
             int f, y;
             pix_at(pw, (unsigned)it * 256u + threadIdx.x, f, x, y);
             for (unsigned ff = pw.f0; ff <= fl; ++ff)                // (uniform: the chunk's frames, one or two; pose at a uniform address)
                 if ((unsigned)f == ff) slot = pixel_slot(depth, pose + (size_t)ff * 16, cam, scale, i, x, y, g, bitmap, rank);
             slots[i] = slot;
-            if (slot != 0xffffffffu) {
-                const unsigned char* c = rgb + i * 3;
-                cr = c[0];
-                cg = c[1];
-                cb = c[2];
-                cn = 1;
-            }
         }
-        // segmented inclusive scan over runs of equal slot within an image row (integer sums: exact in any order)
-        const unsigned prev = __shfl_up(slot, 1);
-        int flag = (lane == 0 || prev != slot || x == 0) ? 1 : 0;
-        const int head = flag;
-        for (int d = 1; d < 64; d <<= 1) {
-            unsigned tr = __shfl_up(cr, d), tg = __shfl_up(cg, d), tb = __shfl_up(cb, d), tn = __shfl_up(cn, d);
-            int tf = __shfl_up(flag, d);
-            if (lane >= d && !flag) {
-                cr += tr; cg += tg; cb += tb; cn += tn;
-                flag = tf;
-            }
-        }
-        const int nhead = __shfl_down(head, 1);
-        const bool tail = lane == 63 || nhead != 0;
-        if (tail && slot != 0xffffffffu) {
-            atomicAdd(&acc.sr[slot], (unsigned long long)cr);
-            atomicAdd(&acc.sg[slot], (unsigned long long)cg);
-            atomicAdd(&acc.sb[slot], (unsigned long long)cb);
-            atomicAdd(&acc.n[slot], cn);
-            ++myruns;
-        }
+        myruns += (unsigned)__popcll(run_edges(slot, x, lane).tails);
     }
-    myruns = (unsigned)wave_sum_i32((int)myruns);
     if (lane == 0 && myruns) atomicAdd(&s_runs, myruns);
     __syncthreads();
     if (threadIdx.x == 0) chunk_runs[blockIdx.x] = s_runs;
@@ -327,12 +307,9 @@ __global__ void __launch_bounds__(256) k_emit_runs(const unsigned* __restrict__ 
         const unsigned slot = in_range ? slots[i] : 0xffffffffu;
         int pf = 0, x = 0, py = 0;
         if (in_range) pix_at(pw, (unsigned)it * 256u + threadIdx.x, pf, x, py);
-        const unsigned prev = __shfl_up(slot, 1);
-        const bool head = lane == 0 || prev != slot || x == 0;
-        const unsigned long long heads = __ballot(head);
-        const int nhead = __shfl_down(head ? 1 : 0, 1);
-        const bool tail = (lane == 63 || nhead != 0) && slot != 0xffffffffu;
-        const unsigned long long tails = __ballot(tail);
+        const RunEdges e = run_edges(slot, x, lane);
+        const unsigned long long heads = e.heads, tails = e.tails;
+        const bool tail = e.tail;
         if (lane == 0) s_w[w] = (unsigned)__popcll(tails);
         __syncthreads();
         unsigned base = s_run;
@@ -367,15 +344,19 @@ __global__ void __launch_bounds__(256) k_emit_runs(const unsigned* __restrict__ 
 // HMSG_DEBUG_ACCUM_WAVES=1, kept as the comparison route of the tests.)
 template <bool LDS_SUM>
 __global__ void __launch_bounds__(256) k_accum_ordered(const unsigned short* __restrict__ depth, const double* __restrict__ pose,
-                                                       CamK cam, float scale, int W, size_t HW, long long V,
-                                                       const unsigned* __restrict__ off, const unsigned long long* __restrict__ runs,
-                                                       const unsigned* __restrict__ cnt, double* __restrict__ pts) {
+                                                       const unsigned char* __restrict__ rgb, CamK cam, float scale, int W, size_t HW,
+                                                       long long V, const unsigned* __restrict__ off,
+                                                       const unsigned long long* __restrict__ runs, double* __restrict__ pts,
+                                                       double* __restrict__ cols) {
     __shared__ double s_pt[LDS_SUM ? 4 : 1][LDS_SUM ? 64 * 3 : 1];
     const int lane = threadIdx.x & 63;
     double* const my_pt = s_pt[LDS_SUM ? (threadIdx.x >> 6) : 0];
     const long long v = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     if (v >= V) return;
     double sx = 0.0, sy = 0.0, sz = 0.0;
+    // colour sums of the pixels this lane back-projects (one per pack: 64-bit, so no count of packs can overflow them) and the
+    // voxel's pixel count = the sum of its run lengths (uniform)
+    unsigned long long cr = 0ull, cg = 0ull, cb = 0ull, npx = 0ull;
     const unsigned r0 = off[v], r1 = off[v + 1];
     for (unsigned rb = r0; rb < r1; rb += 64) {
         // lane q holds run rb + q of this group of 64 runs; inclusive prefix of the run lengths
@@ -411,8 +392,14 @@ __global__ void __launch_bounds__(256) k_accum_ordered(const unsigned short* __r
                 const int f = (int)(rec >> 32);
                 const int y = (int)((rec >> 20) & 0xfffull), x0 = (int)((rec >> 8) & 0xfffull);
                 const int x = x0 + (lane - start);
-                backproject(depth[(size_t)f * HW + (size_t)y * W + x], x, y, cam, scale, pose + (size_t)f * 16, wx, wy, wz);
+                const size_t i = (size_t)f * HW + (size_t)y * W + x;
+                backproject(depth[i], x, y, cam, scale, pose + (size_t)f * 16, wx, wy, wz);
+                const unsigned char* const c = rgb + i * 3;
+                cr += c[0];
+                cg += c[1];
+                cb += c[2];
             }
+            npx += (unsigned long long)npix;
             if (LDS_SUM) {
                 // (one wave, its own slice of LDS: the LDS queue keeps a wave's accesses in order, the barrier keeps the compiler from
                 //  moving them across each other)
@@ -433,14 +420,21 @@ __global__ void __launch_bounds__(256) k_accum_ordered(const unsigned short* __r
             q0 = q1;
         }
     }
+    for (int o = 32; o > 0; o >>= 1) {                // one reduction per voxel, behind its last pack
+        cr += __shfl_xor(cr, o);
+        cg += __shfl_xor(cg, o);
+        cb += __shfl_xor(cb, o);
+    }
+    const double n = (double)npx;
     if (LDS_SUM) {
-        if (lane < 3) pts[v * 3 + lane] = __ddiv_rn(sx, (double)cnt[v]);
+        if (lane < 3) pts[v * 3 + lane] = __ddiv_rn(sx, n);
     } else if (lane == 0) {
-        const double n = (double)cnt[v];
         pts[v * 3 + 0] = __ddiv_rn(sx, n);
         pts[v * 3 + 1] = __ddiv_rn(sy, n);
         pts[v * 3 + 2] = __ddiv_rn(sz, n);
     }
+    // mean colour in [0, 1] from the exact integer sum: (sum / 255) / n, these two divisions in this order
+    if (lane < 3) cols[v * 3 + lane] = ((double)(lane == 0 ? cr : lane == 1 ? cg : cb) / 255.0) / n;
 }
 
 // slot -> cell coordinates (one thread per bitmap word)
@@ -463,15 +457,6 @@ __global__ void k_slot_cells(const unsigned long long* __restrict__ bitmap, cons
         cell[(size_t)s * 3 + 2] = iz;
         ++s;
     }
-}
-
-__global__ void k_finalize(VoxAcc acc, long long V, double* __restrict__ cols) {
-    long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= V) return;
-    double n = (double)acc.n[s];
-    cols[s * 3 + 0] = ((double)acc.sr[s] / 255.0) / n;
-    cols[s * 3 + 1] = ((double)acc.sg[s] / 255.0) / n;
-    cols[s * 3 + 2] = ((double)acc.sb[s] / 255.0) / n;
 }
 
 // ------------------------------------------------------------------------------------------ radius outlier
@@ -737,21 +722,16 @@ void hmsg_build_map(hmsg_ctx* h) {
     unsigned long long V0 = hmsg_bitmap_rank(h->bitmap.p, h->rank.p, (size_t)g.nwords, s, h->scan_tmp);
     h->V0 = (long long)V0;
 
-    DevBuf<unsigned long long> srgb;
-    DevBuf<unsigned> sn, slots, chunk_runs;
-    srgb.alloc(V0 * 3);
-    sn.alloc(V0);
-    srgb.zero(s);
-    sn.zero(s);
+    DevBuf<unsigned> slots, chunk_runs;
     slots.alloc(total);
     const unsigned nchunks = cdiv(total, RUN_CHUNK);
     chunk_runs.alloc((size_t)nchunks + 1);
-    VoxAcc acc{srgb.p, srgb.p + V0, srgb.p + 2 * V0, sn.p};
     {
-        ProfScope ps(h->prof, s, "k_slots", (double)total * 9.0 + (double)V0 * 28.0);
-        hipLaunchKernelGGL(k_slots, dim3(nchunks), dim3(256), 0, s, (const unsigned short*)h->depth.p,
-                           (const unsigned char*)h->rgb.p, (const double*)h->pose.p, h->cam, scale, H, W, F, g,
-                           (const unsigned long long*)h->bitmap.p, (const unsigned*)h->rank.p, acc, slots.p, chunk_runs.p);
+        // bytes: depth read (2) + slot written (4) per pixel; the bitmap and rank words of the occupied cells stay in cache
+        ProfScope ps(h->prof, s, "k_slots", (double)total * 6.0);
+        hipLaunchKernelGGL(k_slots, dim3(nchunks), dim3(256), 0, s, (const unsigned short*)h->depth.p, (const double*)h->pose.p,
+                           h->cam, scale, H, W, F, g, (const unsigned long long*)h->bitmap.p, (const unsigned*)h->rank.p, slots.p,
+                           chunk_runs.p);
     }
     HMSG_CHECK_LAUNCH();
     unsigned long long nruns = 0;
@@ -781,15 +761,24 @@ void hmsg_build_map(hmsg_ctx* h) {
     {
         // HMSG_DEBUG_ACCUM_WAVES=1: every lane carries the sums (the form until round 5)
         static const bool lds_sum = getenv("HMSG_DEBUG_ACCUM_WAVES") == nullptr;
-        ProfScope ps(h->prof, s, "k_accum_ordered", (double)total * 2.0 + (double)nruns * 8.0 + (double)V0 * 32.0);
+        // bytes: depth (2) + colour (3) per pixel, a record per run, per voxel its run offset (4) and the point and colour rows (2 x 24)
+        ProfScope ps(h->prof, s, "k_accum_ordered", (double)total * 5.0 + (double)nruns * 8.0 + (double)V0 * 52.0);
         hipLaunchKernelGGL(lds_sum ? k_accum_ordered<true> : k_accum_ordered<false>, dim3(cdiv(V0 * 64, 256)), dim3(256), 0, s,
-                           (const unsigned short*)h->depth.p, (const double*)h->pose.p, h->cam, scale, W, (size_t)H * W, (long long)V0,
-                           (const unsigned*)run_off.p, (const unsigned long long*)sb.res_vals, (const unsigned*)sn.p, pts0.p);
+                           (const unsigned short*)h->depth.p, (const double*)h->pose.p, (const unsigned char*)h->rgb.p, h->cam, scale, W,
+                           (size_t)H * W, (long long)V0, (const unsigned*)run_off.p, (const unsigned long long*)sb.res_vals, pts0.p,
+                           cols0.p);
         HMSG_CHECK_LAUNCH();
         if (getenv("HMSG_DEBUG_ACCUM_STATS")) {     // development aid: how the pixels are spread over the voxels
-            std::vector<unsigned> hc((size_t)V0);
-            HIP_TRY(hipMemcpyAsync(hc.data(), sn.p, (size_t)V0 * 4, hipMemcpyDeviceToHost, s));
+            std::vector<unsigned> ho((size_t)V0 + 1), hc((size_t)V0);
+            std::vector<unsigned long long> hr((size_t)nruns);
+            HIP_TRY(hipMemcpyAsync(ho.data(), run_off.p, ((size_t)V0 + 1) * 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(hr.data(), sb.res_vals, (size_t)nruns * 8, hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
+            for (size_t v = 0; v < (size_t)V0; ++v) {                 // a voxel's pixels = the lengths of its runs
+                unsigned n = 0;
+                for (unsigned r = ho[v]; r < ho[v + 1]; ++r) n += (unsigned)(hr[r] & 255ull);
+                hc[v] = n;
+            }
             std::sort(hc.begin(), hc.end());
             double tot = 0;
             for (unsigned c : hc) tot += c;
@@ -804,8 +793,6 @@ void hmsg_build_map(hmsg_ctx* h) {
             }
         }
     }
-    hipLaunchKernelGGL(k_finalize, dim3(cdiv(V0, 256)), dim3(256), 0, s, acc, (long long)V0, cols0.p);
-    HMSG_CHECK_LAUNCH();
 
     // remove_radius_outlier (graph.py:355-358)
     DevBuf<unsigned> keep, newidx;

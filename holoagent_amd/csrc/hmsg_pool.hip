@@ -207,14 +207,11 @@ __global__ void k_pool_init(const unsigned* __restrict__ ncount, long long N, in
     // lowest core row of the instance: a label that has reached it cannot drop further
     if (is_core && (int)(i - sg.row_base) < seg_first[k]) atomicMin(&seg_first[k], (int)(i - sg.row_base));
 }
-__global__ void k_pool_prop(const unsigned* __restrict__ adj, const PoolSeg* __restrict__ segs, const int* __restrict__ seg_of_row,
-                            const unsigned* __restrict__ ncount, int minpts, long long N, int* __restrict__ label,
-                            int* __restrict__ changed, const int* __restrict__ seg_first, int first_round,
-                            const unsigned* __restrict__ list /* rows still on their way (k_pool_list), or nullptr: every row */) {
-    const int lane = threadIdx.x & 63;
-    long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    if (i >= N) return;                                       // (N: rows, or entries of the list)
-    if (list) i = list[i];
+// One wave takes one core row through a propagation round.
+__device__ __forceinline__ void pool_prop_row(const unsigned* __restrict__ adj, const PoolSeg* __restrict__ segs,
+                                              const int* __restrict__ seg_of_row, const unsigned* __restrict__ ncount, int minpts,
+                                              long long i, int* __restrict__ label, int* __restrict__ changed,
+                                              const int* __restrict__ seg_first, int first_round, int lane) {
     if (ncount[i] < (unsigned)minpts) return;                 // wave-uniform
     const int k = seg_of_row[i];
     int best = label[i];
@@ -247,15 +244,25 @@ __global__ void k_pool_prop(const unsigned* __restrict__ adj, const PoolSeg* __r
             const int w = w0 + lane;
             unsigned bits = w < sg.nw ? row[w] : 0u;
             while (bits && best != lowest) {
-                int b = __ffs(bits) - 1;
-                bits &= bits - 1;
-                long long j = sg.row_base + (long long)w * 32 + b;
-                if (ncount[j] >= (unsigned)minpts) {
-                    // plain (L1-cacheable) load: a stale label is an older, larger one -- it only delays the drop to
-                    // a later launch, and the host loop runs until a whole round changes nothing
-                    const int lj = label[j];
-                    best = lj < best ? lj : best;
+                // Eight neighbours a trip, their labels fetched side by side: taken one at a time the loads are ONE dependent chain
+                // through `best` (the loop's condition), 32 round trips for a dense word -- and a row of a cluster that is not its
+                // instance's first never meets `lowest`, so it walks all of its neighbours in every round.  A row that is not a core
+                // row keeps the label -1 for good (k_pool_init; only core rows are ever written), which the unsigned comparison
+                // leaves out without a look at its count.
+                // plain (L1-cacheable) loads: a stale label is an older, larger one -- it only delays the drop to a later launch,
+                // and the host loop runs until a whole round changes nothing
+                int lj[8];
+#pragma unroll
+                for (int q = 0; q < 8; ++q) {
+                    lj[q] = -1;
+                    if (bits) {
+                        const int b = __ffs(bits) - 1;
+                        bits &= bits - 1;
+                        lj[q] = label[sg.row_base + (long long)w * 32 + b];
+                    }
                 }
+#pragma unroll
+                for (int q = 0; q < 8; ++q) best = (unsigned)lj[q] < (unsigned)best ? lj[q] : best;
             }
             if (__any(best == lowest)) break;
         }
@@ -269,27 +276,45 @@ __global__ void k_pool_prop(const unsigned* __restrict__ adj, const PoolSeg* __r
         *changed = 1;
     }
 }
+// A round over N rows, or over the N entries of `list` (k_pool_list).  With `n_list` the number of entries is read on the device:
+// the round behind k_pool_list is launched before the host has seen the count, with a grid of fixed size whose waves stride over
+// the list.  (A grid sized for its rows gives every wave one row.)
+__global__ void k_pool_prop(const unsigned* __restrict__ adj, const PoolSeg* __restrict__ segs, const int* __restrict__ seg_of_row,
+                            const unsigned* __restrict__ ncount, int minpts, long long N, int* __restrict__ label,
+                            int* __restrict__ changed, const int* __restrict__ seg_first, int first_round,
+                            const unsigned* __restrict__ list /* rows still on their way, or nullptr: every row */,
+                            const unsigned* __restrict__ n_list /* entries of the list, or nullptr: N */) {
+    const int lane = threadIdx.x & 63;
+    const long long nwaves = ((long long)gridDim.x * blockDim.x) >> 6;
+    if (n_list) N = (long long)*n_list;
+    for (long long e = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6; e < N; e += nwaves)
+        pool_prop_row(adj, segs, seg_of_row, ncount, minpts, list ? (long long)list[e] : e, label, changed, seg_first, first_round, lane);
+}
 // pointer jumping between propagation rounds: a core row's label is the (relative) index of a core row of the same
 // component that is not larger than its own, so label[label[i]] is one too -- following the chain to its end makes
 // the propagation converge in O(log diameter) rounds instead of O(diameter).  (Races only read older, larger labels.)
 __global__ void k_pool_jump(const PoolSeg* __restrict__ segs, const int* __restrict__ seg_of_row, const unsigned* __restrict__ ncount,
-                            int minpts, long long N, int* __restrict__ label, const unsigned* __restrict__ list) {
-    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N) return;
-    if (list) i = list[i];
-    if (ncount[i] < (unsigned)minpts) return;
-    const long long base = segs[seg_of_row[i]].row_base;
-    int l = label[i];
-    for (int hop = 0; hop < 64; ++hop) {
-        const int p = label[base + l];
-        if (p >= l) break;
-        l = p;
+                            int minpts, long long N, int* __restrict__ label, const unsigned* __restrict__ list,
+                            const unsigned* __restrict__ n_list /* as in k_pool_prop */) {
+    if (n_list) N = (long long)*n_list;
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < N; e += (long long)gridDim.x * blockDim.x) {
+        const long long i = list ? (long long)list[e] : e;
+        if (ncount[i] < (unsigned)minpts) continue;
+        const long long base = segs[seg_of_row[i]].row_base;
+        int l = label[i];
+        for (int hop = 0; hop < 64; ++hop) {
+            const int p = label[base + l];
+            if (p >= l) break;
+            l = p;
+        }
+        if (l < label[i]) atomicMin(&label[i], l);
     }
-    if (l < label[i]) atomicMin(&label[i], l);
 }
 // The core rows that have not reached their instance's lowest core row yet.  A row that has is finished for good (nothing lower
-// exists in its instance), and after the first two rounds that is most of them: the later rounds run over this list instead of
-// starting a wave per row of the scene only to find it done (950 000 waves a round at configs[1], 1.1 ms).
+// exists in its instance), and after the first round that is most of them: the later rounds run over this list instead of
+// starting a wave per row of the scene only to find it done.  (configs[1]: 476 000 rows, 177 000 of them open for good -- the
+// rows of a cluster that is not its instance's first never meet the instance's lowest core row; they are what a later round
+// costs, profiles/map_write_side.json.)
 __global__ void k_pool_list(const PoolSeg* __restrict__ segs, const int* __restrict__ seg_of_row, const unsigned* __restrict__ ncount,
                             int minpts, long long N, const int* __restrict__ label, const int* __restrict__ seg_first,
                             unsigned* __restrict__ list, unsigned* __restrict__ n_list) {
@@ -426,32 +451,40 @@ void pool_cluster(hipStream_t s, const PoolSeg* d_ps, long long R, int minpts, c
                        minpts, label, d_ps, seg_of_row, seg_first);
     HMSG_CHECK_LAUNCH();
     // (two rounds before the first look at the flag -- the first one is cheap and always changes something --, then one round
-    //  per look: a round over rows that no longer change costs 1.2 ms, a look 20 us.  Round 6: behind those two rounds the rows
-    //  that are still on their way are listed, and the later rounds run over the list.)
+    //  per look: a round over rows that no longer change costs 0.5 ms, a look 20 us.  Behind the FIRST round the rows that are
+    //  still on their way are listed, and every later round runs over the list: the second one with the count still on the device
+    //  (a grid of fixed size strides over the list), the others sized by the count the first look brings back.)
     DevBuf<unsigned> open_list;
     open_list.alloc((size_t)std::max<long long>(R, 1) + 1);                            // [0] the count, the rows behind it
     const unsigned* d_list = nullptr;
     unsigned n_open = 0;
     static const bool list_wanted = getenv("HMSG_DEBUG_POOL_ALL_ROWS") == nullptr;   // HMSG_DEBUG_POOL_ALL_ROWS=1: every round over every row (until round 5)
+    const auto round = [&](size_t rows, unsigned wave_blocks, int first_round, const unsigned* list, const unsigned* n_list) {
+        // (wave_blocks: the grid of k_pool_prop -- a wave per row, or the fixed grid of the round that reads its count itself)
+        hipLaunchKernelGGL(k_pool_prop, dim3(wave_blocks), dim3(256), 0, s, adj, d_ps, seg_of_row, ncount, minpts, (long long)rows,
+                           label, d_changed, seg_first, first_round, list, n_list);
+        hipLaunchKernelGGL(k_pool_jump, dim3(n_list ? wave_blocks : cdiv(rows, 256)), dim3(256), 0, s, d_ps, seg_of_row, ncount, minpts,
+                           (long long)rows, label, list, n_list);
+    };
     for (int it = 0; it < 100000; ++it) {
         HIP_TRY(hipMemsetAsync(d_changed, 0, 4, s));
-        const size_t rows = d_list ? (size_t)n_open : (size_t)R;
-        for (int rep = 0; rep < (it == 0 ? 2 : 1) && rows; ++rep) {
-            hipLaunchKernelGGL(k_pool_prop, dim3(cdiv(rows * 64, 256)), dim3(256), 0, s, adj,
-                               d_ps, seg_of_row, ncount,
-                               minpts, (long long)rows, label, d_changed, seg_first, (it == 0 && rep == 0) ? 1 : 0, d_list);
-            hipLaunchKernelGGL(k_pool_jump, dim3(cdiv(rows, 256)), dim3(256), 0, s, d_ps,
-                               seg_of_row, ncount, minpts, (long long)rows, label, d_list);
+        if (it == 0 && R > 0) {
+            round((size_t)R, cdiv((size_t)R * 64, 256), 1, nullptr, nullptr);
+            if (list_wanted) {
+                HIP_TRY(hipMemsetAsync(open_list.p, 0, 4, s));
+                hipLaunchKernelGGL(k_pool_list, dim3(cdiv((size_t)R, 256)), dim3(256), 0, s, d_ps, seg_of_row,
+                                   ncount, minpts, (long long)R, label, seg_first,
+                                   open_list.p + 1, open_list.p);
+                // (at most 2^17 waves: starting them costs under 0.1 ms, and a list that long still gives every wave a row or two)
+                round((size_t)R, std::min(cdiv((size_t)R * 64, 256), 32768u), 0, open_list.p + 1, open_list.p);
+                HIP_TRY(hipMemcpyAsync(&n_open, open_list.p, 4, hipMemcpyDeviceToHost, s));
+            } else {
+                round((size_t)R, cdiv((size_t)R * 64, 256), 0, nullptr, nullptr);
+            }
+        } else if (const size_t rows = d_list ? (size_t)n_open : (size_t)R) {
+            round(rows, cdiv(rows * 64, 256), 0, d_list, nullptr);
         }
         HMSG_CHECK_LAUNCH();
-        if (it == 0 && list_wanted) {
-            HIP_TRY(hipMemsetAsync(open_list.p, 0, 4, s));
-            hipLaunchKernelGGL(k_pool_list, dim3(cdiv((size_t)R, 256)), dim3(256), 0, s, d_ps, seg_of_row,
-                               ncount, minpts, (long long)R, label, seg_first,
-                               open_list.p + 1, open_list.p);
-            HMSG_CHECK_LAUNCH();
-            HIP_TRY(hipMemcpyAsync(&n_open, open_list.p, 4, hipMemcpyDeviceToHost, s));
-        }
         int ch = 0;
         HIP_TRY(hipMemcpyAsync(&ch, d_changed, 4, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
