@@ -223,6 +223,7 @@ _SIGS = {
     "hmsg_test_group_pairs": (C.c_int, [C.c_int32, C.c_int64, _P, C.c_int32, _P, C.c_double, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "hmsg_test_overlap": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int64, _P, C.c_double, _P, _P, _P]),
     "hmsg_test_pool_rows": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_double, C.c_int32, _P]),
+    "hmsg_test_graph_early_objects": (C.c_int, [_P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)
 

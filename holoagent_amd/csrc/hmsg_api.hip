@@ -184,6 +184,7 @@ void hmsg_destroy(hmsg_t* h) {
         hmsg_fold_pipe_abort(h);
     } catch (...) {
     }
+    hmsg_graph_early_abort(h);           // (a graph that outlives its scene keeps no pointer to it)
     h->fold_cache.trim();
     if (h->stream) {
         (void)hipStreamSynchronize(h->stream);
@@ -202,6 +203,8 @@ int hmsg_reset(hmsg_t* h) {
         HIP_TRY(hipStreamSynchronize(h->stream));
         hmsg_kd_join(h);
         hmsg_fold_pipe_abort(h);
+        hmsg_graph_early_abort(h);
+        ++h->inst_epoch;
         h->n_tie_queries = 0;
         h->n_frames = h->n_feat_frames = h->n_fused = 0;
         h->n_offered = 0;
@@ -459,6 +462,8 @@ int hmsg_merge_tree_local(hmsg_t* h, int32_t total_frames, double* th_next, int6
         long long l = 0, i = 0;
         HMSG_NOT_RESTORED(h, "hmsg_merge_tree_local");
         hmsg_fold_pipe_abort(h);
+        hmsg_graph_early_abort(h);
+        ++h->inst_epoch;
         release_frame_store_if_large(h);
         hmsg_merge_tree_local_impl(h, total_frames, th_next, &l, &i);
         *lists_now = l;
@@ -470,6 +475,8 @@ int hmsg_merge_tree_join(hmsg_t* h, int32_t n_ext, const int64_t* ext_sizes, con
     if (!h) return HMSG_ERR_INVALID;
     return hmsg_boundary(h, [&] {
         HMSG_NOT_RESTORED(h, "hmsg_merge_tree_join");
+        hmsg_graph_early_abort(h);
+        ++h->inst_epoch;
         hmsg_merge_tree_join_impl(h, n_ext, (const long long*)ext_sizes, ext_points, th, final_pass);
     });
 }
@@ -592,6 +599,7 @@ int hmsg_merge_instances(hmsg_t* h) {
     return hmsg_boundary(h, [&] {
         HMSG_NOT_RESTORED(h, "hmsg_merge_instances");
         release_frame_store_if_large(h);
+        ++h->inst_epoch;
         hmsg_merge(h);
     });
 }

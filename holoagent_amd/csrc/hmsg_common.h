@@ -702,6 +702,12 @@ struct hmsg_ctx {
     DevCache fold_cache;           // the worker's allocator cache between scenes (its thread-local one while it runs)
     bool restored = false;         // map, instances and pooled features came from hmsg_restore_stage: no frame store, no bitmap / rank / cand
     bool inst_denoised = false;    // the per-object pcd_denoise_dbscan(0.05, 10) of graph.py:1589-1591 has run
+    // the object stage of a graph in flight, run beside the pooling (hmsg_scene_graph.hip: EarlyObjects)
+    struct hmsg_graph* early_graph = nullptr;   // the graph hmsg_graph_begin registered here; cleared by its finish / destroy and by every abort point
+    unsigned long long inst_epoch = 0;          // bumped whenever `inst` changes (reset, merge, restore, denoise): an early result made from another list is stale
+    int early_last = 0;                         // test hook: what became of the last registration (HMSG_EARLY_*)
+    std::shared_ptr<void> early_ops;            // that stage's CloudOps, kept from scene to scene (hmsg_denoise_compute): its pinned buffers
+                                                // must not be freed beside the pooling -- hipHostFree waits for the whole device
     std::vector<hmsg_node> nodes;  // object nodes (hmsg_build_object_nodes)
     // room clouds of the last hmsg_room_clouds call, resident: per room the selected floor points (indices into the storey's
     // crop), room offsets, floor point -> map point
@@ -827,8 +833,34 @@ void hmsg_fold_pipe_feed(hmsg_ctx* h, int f0, int nfr);   // hmsg_merge.hip: mas
 void hmsg_fold_pipe_abort(hmsg_ctx* h);                  // hmsg_merge.hip
 void hmsg_merge_tree_local_impl(hmsg_ctx* h, int total_frames, double* th_next, long long* lists_now, long long* my_index);
 void hmsg_merge_tree_join_impl(hmsg_ctx* h, int n_ext, const long long* ext_sizes, const double* ext_pts, double th, int final_pass);
+// the per-object DBSCAN in two steps: the clustering of `in` on stream s into a value of its own (false: nothing to do, `out` is
+// untouched), and the swap into the handle.  hmsg_denoise_inst = both, on the handle's stream and list.
+// keep (optional): where the batch's CloudOps lives between calls (made on first use) instead of being built and freed by the call.
+bool hmsg_denoise_compute(hipStream_t s, const InstanceSet& in, double eps, int min_points, InstanceSet& out,
+                          std::shared_ptr<void>* keep = nullptr);                                                 // hmsg_merge.hip
+void hmsg_denoise_commit(hmsg_ctx* h, InstanceSet& out);                                                          // hmsg_merge.hip
 void hmsg_denoise_inst(hmsg_ctx* h, double eps, int min_points);   // hmsg_merge.hip
+void hmsg_room_share_on(hipStream_t s, const InstanceSet& inst, int R, const long long* vert_off, const double* verts_xz, double radius,
+                        double* share_out);                           // hmsg_merge.hip
 void hmsg_room_share(hmsg_ctx* h, int R, const long long* vert_off, const double* verts_xz, double radius,
                      double* share_out);                              // hmsg_merge.hip
+// the floor / room assignment of hmsg_build_object_nodes on a given instance list: nodes with label -1 (hmsg_graph.hip)
+void hmsg_object_nodes_on(hipStream_t s, const InstanceSet& inst, int n_floors, const double* floor_zero, const double* floor_height, int n_rooms,
+                          const int32_t* room_floor, const int64_t* vert_off, const double* verts_xz, const double* share,
+                          std::vector<hmsg_node>& nodes);
+// per instance of the handle: arg-max label into h->node_label (-1 without a vocabulary)                       (hmsg_graph.hip)
+void hmsg_node_labels(hmsg_ctx* h, int n_labels, const float* label_feats);
+// the device part of hmsg_object_views on a given instance list                                                 (hmsg_graph.hip)
+void hmsg_object_views_on(hipStream_t s, const InstanceSet& inst, int32_t n_views, const double* pose_inv, const int32_t* wh, const double* K,
+                          int64_t n_pairs, const int32_t* pair_inst, const int32_t* pair_view, double min_visible_ratio, double max_depth,
+                          uint8_t* visible, double* mean_depth);
+// The object stage of the registered graph beside the pooling (hmsg_scene_graph.hip).  start: from hmsg_pool_instances, on a host
+// thread and a stream of its own (nothing happens without a registered, unfinished graph or with HMSG_GRAPH_EARLY_OBJECTS=0);
+// join: wait for that thread (the result stays with the graph for its finish); abort: join, drop the result, forget the graph.
+enum { HMSG_EARLY_NEVER_MADE = 0, HMSG_EARLY_CONSUMED = 1, HMSG_EARLY_DISCARDED = 2, HMSG_EARLY_PENDING = 3 };
+int hmsg_graph_early_mode();                            // HMSG_GRAPH_EARLY_OBJECTS: 0 off, 1 (default) in front of pooling, 2 behind k_pool_gram's launch
+void hmsg_graph_early_start(hmsg_ctx* h);
+void hmsg_graph_early_join(hmsg_ctx* h) noexcept;
+void hmsg_graph_early_abort(hmsg_ctx* h) noexcept;
 void hmsg_pool(hmsg_ctx* h);            // hmsg_pool.hip
 long long hmsg_voxel_ds(hmsg_ctx* h, const double* pts, long long n, double vs, double* out);   // hmsg_merge.hip

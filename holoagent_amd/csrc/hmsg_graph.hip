@@ -17,6 +17,97 @@
 
 #include <cmath>
 
+// per instance of the handle: the label whose text feature is most similar to its pooled feature
+void hmsg_node_labels(hmsg_ctx* h, int n_labels, const float* label_feats) {
+    const int N = (int)h->inst.off.size() - 1, D = h->cfg.feat_dim;
+    h->node_label.assign((size_t)std::max(N, 0), -1);
+    if (N <= 0 || n_labels <= 0) return;
+    // labels: S = emb . text^T on the device (float32 values in float64 arithmetic, as NodeIndex.similarity)
+    hmsg_index_t* ix = nullptr;
+    std::vector<int32_t> zero((size_t)n_labels, 0);
+    HMSG_REQUIRE(hmsg_index_create(h->cfg.device_id, D, n_labels, label_feats, 0, zero.data(), &ix) == HMSG_OK, HMSG_ERR_HIP,
+                 "hmsg_build_object_nodes: label table");
+    std::vector<double> S((size_t)N * n_labels);
+    int rc = hmsg_similarity(ix, N, h->inst_feats.p, S.data());
+    hmsg_index_destroy(ix);
+    HMSG_REQUIRE(rc == HMSG_OK, HMSG_ERR_HIP, "hmsg_build_object_nodes: label similarity");
+    for (int i = 0; i < N; ++i) {
+        int best = 0;
+        for (int l = 1; l < n_labels; ++l)
+            if (S[(size_t)i * n_labels + l] > S[(size_t)i * n_labels + best]) best = l;     // np.argmax: first maximum
+        h->node_label[(size_t)i] = best;
+    }
+}
+
+// floors and rooms of every instance of `inst` (the label comes later: -1 here); reads the list's points on s
+void hmsg_object_nodes_on(hipStream_t s, const InstanceSet& inst, int n_floors, const double* floor_zero, const double* floor_height, int n_rooms,
+                          const int32_t* room_floor, const int64_t* vert_off, const double* verts_xz, const double* share,
+                          std::vector<hmsg_node>& nodes) {
+    const int N = (int)inst.off.size() - 1;
+    nodes.clear();
+    // room vertex centroids (np.mean(axis=0): rows added in order)
+    std::vector<double> rc((size_t)n_rooms * 2, 0.0);
+    for (int r = 0; r < n_rooms; ++r) {
+        double sx = 0.0, sz = 0.0;
+        for (long long v = vert_off[r]; v < vert_off[r + 1]; ++v) {
+            sx += verts_xz[v * 2];
+            sz += verts_xz[v * 2 + 1];
+        }
+        const double n = (double)(vert_off[r + 1] - vert_off[r]);
+        rc[(size_t)r * 2] = sx / n;
+        rc[(size_t)r * 2 + 1] = sz / n;
+    }
+    std::vector<int> counter((size_t)n_rooms, 0);
+    const double margin = 0.2;
+    std::vector<double> pts;
+    for (int f = 0; f < n_floors; ++f) {
+        std::vector<int> rooms_f;
+        for (int r = 0; r < n_rooms; ++r)
+            if (room_floor[r] == f) rooms_f.push_back(r);
+        for (int i = 0; i < N; ++i) {
+            const long long n_i = inst.off[(size_t)i + 1] - inst.off[(size_t)i];
+            if (n_i < 10) continue;
+            const double ymin = inst.box[(size_t)i * 6 + 1], ymax = inst.box[(size_t)i * 6 + 4];
+            if (!(ymin > floor_zero[f] - margin && ymax < floor_zero[f] + floor_height[f] + margin)) continue;
+            if (rooms_f.empty()) continue;
+            double sum = 0.0;
+            for (int r : rooms_f) sum += share[(size_t)i * n_rooms + r];
+            int best = rooms_f[0];
+            if (sum == 0.0) {          // no room vertex near the object: nearest room centre to the x/z centroid
+                pts.resize((size_t)n_i * 3);
+                HIP_TRY(hipMemcpyAsync(pts.data(), inst.pts.p + (size_t)inst.off[(size_t)i] * 3, (size_t)n_i * 24, hipMemcpyDeviceToHost, s));
+                HIP_TRY(hipStreamSynchronize(s));
+                double cx = 0.0, cz = 0.0;
+                for (long long k = 0; k < n_i; ++k) {
+                    cx += pts[(size_t)k * 3];
+                    cz += pts[(size_t)k * 3 + 2];
+                }
+                cx /= (double)n_i;
+                cz /= (double)n_i;
+                double bv = 0.0;
+                bool have = false;
+                for (int r : rooms_f) {
+                    const double dx = rc[(size_t)r * 2] - cx, dz = rc[(size_t)r * 2 + 1] - cz;
+                    const double v = -std::sqrt(dx * dx + dz * dz);     // -np.linalg.norm
+                    if (!have || v > bv) {
+                        bv = v;
+                        best = r;
+                        have = true;
+                    }
+                }
+            } else {
+                double bv = share[(size_t)i * n_rooms + best];
+                for (int r : rooms_f)
+                    if (share[(size_t)i * n_rooms + r] > bv) {
+                        bv = share[(size_t)i * n_rooms + r];
+                        best = r;
+                    }
+            }
+            nodes.push_back(hmsg_node{i, f, best, counter[(size_t)best]++, -1, (int64_t)n_i});
+        }
+    }
+}
+
 extern "C" {
 
 int hmsg_build_object_nodes(hmsg_t* h, int32_t n_floors, const double* floor_zero, const double* floor_height, int32_t n_rooms,
@@ -28,7 +119,6 @@ int hmsg_build_object_nodes(hmsg_t* h, int32_t n_floors, const double* floor_zer
         HMSG_REQUIRE(n_floors >= 0 && n_rooms >= 0 && (n_floors == 0 || (floor_zero && floor_height)) &&
                          (n_rooms == 0 || (room_floor && vert_off && verts_xz)) && (n_labels == 0 || label_feats),
                      HMSG_ERR_INVALID, "hmsg_build_object_nodes: bad argument");
-        const int D = h->cfg.feat_dim;
         DbgLaps laps("object nodes", h->stream);
         if (!h->inst_denoised) {
             hmsg_denoise_inst(h, 0.05, 10);
@@ -37,89 +127,14 @@ int hmsg_build_object_nodes(hmsg_t* h, int32_t n_floors, const double* floor_zer
         laps.lap("per-object DBSCAN");
         const int N = (int)h->inst.off.size() - 1;
         h->nodes.clear();
-        h->node_label.assign((size_t)std::max(N, 0), -1);
+        hmsg_node_labels(h, n_labels, label_feats);
         if (N <= 0) return;
-        // labels: S = emb . text^T on the device (float32 values in float64 arithmetic, as NodeIndex.similarity)
-        if (n_labels > 0) {
-            hmsg_index_t* ix = nullptr;
-            std::vector<int32_t> zero((size_t)n_labels, 0);
-            HMSG_REQUIRE(hmsg_index_create(h->cfg.device_id, D, n_labels, label_feats, 0, zero.data(), &ix) == HMSG_OK, HMSG_ERR_HIP,
-                         "hmsg_build_object_nodes: label table");
-            std::vector<double> S((size_t)N * n_labels);
-            int rc = hmsg_similarity(ix, N, h->inst_feats.p, S.data());
-            hmsg_index_destroy(ix);
-            HMSG_REQUIRE(rc == HMSG_OK, HMSG_ERR_HIP, "hmsg_build_object_nodes: label similarity");
-            for (int i = 0; i < N; ++i) {
-                int best = 0;
-                for (int l = 1; l < n_labels; ++l)
-                    if (S[(size_t)i * n_labels + l] > S[(size_t)i * n_labels + best]) best = l;     // np.argmax: first maximum
-                h->node_label[(size_t)i] = best;
-            }
-        }
         laps.lap("label similarity");
         std::vector<double> share((size_t)N * std::max(n_rooms, 1), 0.0);
         if (n_rooms > 0) hmsg_room_share(h, n_rooms, (const long long*)vert_off, verts_xz, 0.2, share.data());
         laps.lap("room shares");
-        // room vertex centroids (np.mean(axis=0): rows added in order)
-        std::vector<double> rc((size_t)n_rooms * 2, 0.0);
-        for (int r = 0; r < n_rooms; ++r) {
-            double sx = 0.0, sz = 0.0;
-            for (long long v = vert_off[r]; v < vert_off[r + 1]; ++v) {
-                sx += verts_xz[v * 2];
-                sz += verts_xz[v * 2 + 1];
-            }
-            const double n = (double)(vert_off[r + 1] - vert_off[r]);
-            rc[(size_t)r * 2] = sx / n;
-            rc[(size_t)r * 2 + 1] = sz / n;
-        }
-        std::vector<int> counter((size_t)n_rooms, 0);
-        const double margin = 0.2;
-        std::vector<double> pts;
-        for (int f = 0; f < n_floors; ++f) {
-            std::vector<int> rooms_f;
-            for (int r = 0; r < n_rooms; ++r)
-                if (room_floor[r] == f) rooms_f.push_back(r);
-            for (int i = 0; i < N; ++i) {
-                const long long n_i = h->inst.off[(size_t)i + 1] - h->inst.off[(size_t)i];
-                if (n_i < 10) continue;
-                const double ymin = h->inst.box[(size_t)i * 6 + 1], ymax = h->inst.box[(size_t)i * 6 + 4];
-                if (!(ymin > floor_zero[f] - margin && ymax < floor_zero[f] + floor_height[f] + margin)) continue;
-                if (rooms_f.empty()) continue;
-                double sum = 0.0;
-                for (int r : rooms_f) sum += share[(size_t)i * n_rooms + r];
-                int best = rooms_f[0];
-                if (sum == 0.0) {          // no room vertex near the object: nearest room centre to the x/z centroid
-                    pts.resize((size_t)n_i * 3);
-                    HIP_TRY(hipMemcpy(pts.data(), h->inst.pts.p + (size_t)h->inst.off[(size_t)i] * 3, (size_t)n_i * 24, hipMemcpyDeviceToHost));
-                    double cx = 0.0, cz = 0.0;
-                    for (long long k = 0; k < n_i; ++k) {
-                        cx += pts[(size_t)k * 3];
-                        cz += pts[(size_t)k * 3 + 2];
-                    }
-                    cx /= (double)n_i;
-                    cz /= (double)n_i;
-                    double bv = 0.0;
-                    bool have = false;
-                    for (int r : rooms_f) {
-                        const double dx = rc[(size_t)r * 2] - cx, dz = rc[(size_t)r * 2 + 1] - cz;
-                        const double v = -std::sqrt(dx * dx + dz * dz);     // -np.linalg.norm
-                        if (!have || v > bv) {
-                            bv = v;
-                            best = r;
-                            have = true;
-                        }
-                    }
-                } else {
-                    double bv = share[(size_t)i * n_rooms + best];
-                    for (int r : rooms_f)
-                        if (share[(size_t)i * n_rooms + r] > bv) {
-                            bv = share[(size_t)i * n_rooms + r];
-                            best = r;
-                        }
-                }
-                h->nodes.push_back(hmsg_node{i, f, best, counter[(size_t)best]++, h->node_label[(size_t)i], (int64_t)n_i});
-            }
-        }
+        hmsg_object_nodes_on(h->stream, h->inst, n_floors, floor_zero, floor_height, n_rooms, room_floor, vert_off, verts_xz, share.data(), h->nodes);
+        for (hmsg_node& nd : h->nodes) nd.label = h->node_label[(size_t)nd.instance];
         laps.lap("floors / rooms (host)");
     });
 }
@@ -667,6 +682,40 @@ __global__ void __launch_bounds__(256) k_object_views(const double* __restrict__
     }
 }
 
+void hmsg_object_views_on(hipStream_t s, const InstanceSet& inst, int32_t n_views, const double* pose_inv, const int32_t* wh, const double* K,
+                          int64_t n_pairs, const int32_t* pair_inst, const int32_t* pair_view, double min_visible_ratio, double max_depth,
+                          uint8_t* visible, double* mean_depth) {
+    if (n_pairs == 0) return;
+    const long long NI = (long long)inst.off.size() - 1;
+    std::vector<ViewPair> hp((size_t)n_pairs);
+    for (int64_t k = 0; k < n_pairs; ++k) {
+        HMSG_REQUIRE(pair_inst[k] >= 0 && pair_inst[k] < NI && pair_view[k] >= 0 && pair_view[k] < n_views, HMSG_ERR_INVALID,
+                     "hmsg_object_views: pair out of range");
+        const long long p0 = inst.off[(size_t)pair_inst[k]], p1 = inst.off[(size_t)pair_inst[k] + 1];
+        hp[(size_t)k] = ViewPair{p0, (int)(p1 - p0), pair_view[k]};
+    }
+    DevBuf<ViewPair> d_pairs;
+    DevBuf<double> d_pose, d_K, d_md;
+    DevBuf<int> d_wh;
+    DevBuf<unsigned char> d_vis;
+    d_pairs.alloc((size_t)n_pairs);
+    d_pose.alloc((size_t)n_views * 16);
+    d_K.alloc(9);
+    d_wh.alloc((size_t)n_views * 2);
+    d_md.alloc((size_t)n_pairs);
+    d_vis.alloc((size_t)n_pairs);
+    HIP_TRY(hipMemcpyAsync(d_pairs.p, hp.data(), (size_t)n_pairs * sizeof(ViewPair), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_pose.p, pose_inv, (size_t)n_views * 128, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_K.p, K, 72, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_wh.p, wh, (size_t)n_views * 8, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_object_views, dim3((unsigned)n_pairs), dim3(256), 0, s, (const double*)inst.pts.p, (const ViewPair*)d_pairs.p,
+                       (const double*)d_pose.p, (const int*)d_wh.p, (const double*)d_K.p, min_visible_ratio, max_depth, d_vis.p, d_md.p);
+    HMSG_CHECK_LAUNCH();
+    HIP_TRY(hipStreamSynchronize(s));
+    d2h_bounce(visible, d_vis.p, (size_t)n_pairs);
+    d2h_bounce(mean_depth, d_md.p, (size_t)n_pairs * 8);
+}
+
 extern "C" int hmsg_object_views(hmsg_t* h, int32_t n_views, const double* pose_inv, const int32_t* wh, const double* K, int64_t n_pairs,
                                  const int32_t* pair_inst, const int32_t* pair_view, double min_visible_ratio, double max_depth,
                                  uint8_t* visible, double* mean_depth) {
@@ -675,35 +724,6 @@ extern "C" int hmsg_object_views(hmsg_t* h, int32_t n_views, const double* pose_
         HMSG_REQUIRE(h->merged, HMSG_ERR_INVALID, "hmsg_object_views: run hmsg_merge_instances first");
         HMSG_REQUIRE(n_views >= 0 && n_pairs >= 0 && n_pairs < (1ll << 31) && (n_pairs == 0 || (pose_inv && wh && K && pair_inst && pair_view && visible && mean_depth)),
                      HMSG_ERR_INVALID, "hmsg_object_views: bad argument");
-        if (n_pairs == 0) return;
-        const long long NI = (long long)h->inst.off.size() - 1;
-        std::vector<ViewPair> hp((size_t)n_pairs);
-        for (int64_t k = 0; k < n_pairs; ++k) {
-            HMSG_REQUIRE(pair_inst[k] >= 0 && pair_inst[k] < NI && pair_view[k] >= 0 && pair_view[k] < n_views, HMSG_ERR_INVALID,
-                         "hmsg_object_views: pair out of range");
-            const long long p0 = h->inst.off[(size_t)pair_inst[k]], p1 = h->inst.off[(size_t)pair_inst[k] + 1];
-            hp[(size_t)k] = ViewPair{p0, (int)(p1 - p0), pair_view[k]};
-        }
-        hipStream_t s = h->stream;
-        DevBuf<ViewPair> d_pairs;
-        DevBuf<double> d_pose, d_K, d_md;
-        DevBuf<int> d_wh;
-        DevBuf<unsigned char> d_vis;
-        d_pairs.alloc((size_t)n_pairs);
-        d_pose.alloc((size_t)n_views * 16);
-        d_K.alloc(9);
-        d_wh.alloc((size_t)n_views * 2);
-        d_md.alloc((size_t)n_pairs);
-        d_vis.alloc((size_t)n_pairs);
-        HIP_TRY(hipMemcpyAsync(d_pairs.p, hp.data(), (size_t)n_pairs * sizeof(ViewPair), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_pose.p, pose_inv, (size_t)n_views * 128, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_K.p, K, 72, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_wh.p, wh, (size_t)n_views * 8, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_object_views, dim3((unsigned)n_pairs), dim3(256), 0, s, (const double*)h->inst.pts.p, (const ViewPair*)d_pairs.p,
-                           (const double*)d_pose.p, (const int*)d_wh.p, (const double*)d_K.p, min_visible_ratio, max_depth, d_vis.p, d_md.p);
-        HMSG_CHECK_LAUNCH();
-        HIP_TRY(hipStreamSynchronize(s));
-        d2h_bounce(visible, d_vis.p, (size_t)n_pairs);
-        d2h_bounce(mean_depth, d_md.p, (size_t)n_pairs * 8);
+        hmsg_object_views_on(h->stream, h->inst, n_views, pose_inv, wh, K, n_pairs, pair_inst, pair_view, min_visible_ratio, max_depth, visible, mean_depth);
     });
 }

@@ -2624,34 +2624,52 @@ extern "C" int hmsg_test_overlap(hmsg_t* h, int32_t K, const int64_t* sizes, con
 
 // A10 first step (graph.py:1589-1591): every instance re-denoised with pcd_denoise_dbscan(eps, min_points),
 // in place (the pooled features were computed before, as in the reference).
-void hmsg_denoise_inst(hmsg_ctx* h, double eps, int min_points) {
-    HMSG_REQUIRE(h->merged, HMSG_ERR_INVALID, "hmsg_denoise_instances: run hmsg_merge_instances first");
-    const int K = (int)h->inst.off.size() - 1;
-    if (K <= 0 || h->inst.total == 0) return;
-    CloudOps ops;
-    ops.s = h->stream;
+// The clustering reads `in` and writes `out` only, on s: the object stage of a graph runs it beside the pooling, which reads the
+// same list at that time (hmsg_scene_graph.hip: EarlyObjects).
+bool hmsg_denoise_compute(hipStream_t s, const InstanceSet& in, double eps, int min_points, InstanceSet& out, std::shared_ptr<void>* keep) {
+    const int K = (int)in.off.size() - 1;
+    if (K <= 0 || in.total == 0) return false;
+    // Beside the pooling the batch's scratch outlives the call: a CloudOps that goes takes its pinned result and staging buffers with
+    // it, and hipHostFree waits until the whole device is idle -- measured: the stage stood still behind the DBSCAN until k_pool_gram
+    // and the rest of the pooling were through, 25 ms.
+    std::shared_ptr<void> own;
+    if (!keep) keep = &own;
+    if (!*keep) *keep = std::make_shared<CloudOps>();
+    CloudOps& ops = *static_cast<CloudOps*>(keep->get());
+    ops.s = s;
     std::vector<SegDesc> segs(K);
     for (int k = 0; k < K; ++k) {
-        segs[k].pt_base = h->inst.off[k];
-        segs[k].n = (int)(h->inst.off[k + 1] - h->inst.off[k]);
+        segs[k].pt_base = in.off[k];
+        segs[k].n = (int)(in.off[k + 1] - in.off[k]);
     }
-    ops.bounds(h->inst.pts.p, segs);
-    DevBuf<double> out;
-    out.alloc((size_t)h->inst.total * 3);
+    ops.bounds(in.pts.p, segs);
+    out.pts.alloc((size_t)in.total * 3);
     std::vector<DbscanResult> res;
-    long long total = ops.dbscan_keep_largest(h->inst.pts.p, segs, eps, min_points, out.p, res);
-    out.swap(h->inst.pts);
-    h->inst.off.assign(1, 0);
-    h->inst.box.clear();
+    long long total = ops.dbscan_keep_largest(in.pts.p, segs, eps, min_points, out.pts.p, res);
+    out.off.assign(1, 0);
+    out.box.clear();
     long long acc = 0;
     for (int k = 0; k < K; ++k) {
         acc += res[k].n_out;
-        h->inst.off.push_back(acc);
-        for (int a = 0; a < 3; ++a) h->inst.box.push_back(res[k].mn[a]);
-        for (int a = 0; a < 3; ++a) h->inst.box.push_back(res[k].mx[a]);
+        out.off.push_back(acc);
+        for (int a = 0; a < 3; ++a) out.box.push_back(res[k].mn[a]);
+        for (int a = 0; a < 3; ++a) out.box.push_back(res[k].mx[a]);
     }
-    h->inst.total = total;
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    out.total = total;
+    HIP_TRY(hipStreamSynchronize(s));
+    return true;
+}
+void hmsg_denoise_commit(hmsg_ctx* h, InstanceSet& out) {
+    out.pts.swap(h->inst.pts);
+    h->inst.off.swap(out.off);
+    h->inst.box.swap(out.box);
+    h->inst.total = out.total;
+    ++h->inst_epoch;
+}
+void hmsg_denoise_inst(hmsg_ctx* h, double eps, int min_points) {
+    HMSG_REQUIRE(h->merged, HMSG_ERR_INVALID, "hmsg_denoise_instances: run hmsg_merge_instances first");
+    InstanceSet out;
+    if (hmsg_denoise_compute(h->stream, h->inst, eps, min_points, out)) hmsg_denoise_commit(h, out);
 }
 
 // ------------------------------------------------------------------------------------------ A10: object -> room share
@@ -2735,10 +2753,9 @@ __global__ void k_sh_query(const ShGrid* __restrict__ gr, const ShTask* __restri
     if (local) atomicAdd(&counts[blockIdx.y], local);
 }
 
-void hmsg_room_share(hmsg_ctx* h, int R, const long long* vert_off, const double* verts_xz, double radius, double* share_out) {
-    HMSG_REQUIRE(h->merged, HMSG_ERR_INVALID, "hmsg_instance_room_share: run hmsg_merge_instances first");
-    hipStream_t s = h->stream;
-    const int N = (int)h->inst.off.size() - 1;
+void hmsg_room_share_on(hipStream_t s, const InstanceSet& inst, int R, const long long* vert_off, const double* verts_xz, double radius,
+                        double* share_out) {
+    const int N = (int)inst.off.size() - 1;
     for (long long i = 0; i < (long long)N * R; ++i) share_out[i] = 0.0;
     if (N <= 0 || R <= 0) return;
     const double cell = radius * (1.0 + 1e-9);
@@ -2760,12 +2777,12 @@ void hmsg_room_share(hmsg_ctx* h, int R, const long long* vert_off, const double
     int maxn = 0;
     for (int i = 0; i < N; ++i) {
         ShGrid& q = g[i];
-        q.pt_off = h->inst.off[i];
-        q.n = (int)(h->inst.off[i + 1] - h->inst.off[i]);
+        q.pt_off = inst.off[i];
+        q.n = (int)(inst.off[i + 1] - inst.off[i]);
         q.cell = cell;
         q.pad = 0;
         q.cell_off = ncell;
-        const double* bx = &h->inst.box[(size_t)i * 6];
+        const double* bx = &inst.box[(size_t)i * 6];
         q.ox = bx[0] - 1e-9;
         q.oz = bx[2] - 1e-9;
         q.gx = q.n ? (int)std::floor((bx[3] - q.ox) / cell) + 1 : 1;
@@ -2791,7 +2808,7 @@ void hmsg_room_share(hmsg_ctx* h, int R, const long long* vert_off, const double
     cells.alloc((size_t)ncell);
     cursor.alloc((size_t)ncell);
     counts.alloc(tasks.size());
-    sorted.alloc((size_t)std::max<long long>(h->inst.total, 1) * 2);
+    sorted.alloc((size_t)std::max<long long>(inst.total, 1) * 2);
     const long long nv = vert_off[R];
     d_verts.alloc((size_t)std::max<long long>(nv, 1) * 2);
     d_voff.alloc(R + 1);
@@ -2803,10 +2820,10 @@ void hmsg_room_share(hmsg_ctx* h, int R, const long long* vert_off, const double
     cursor.zero(s);
     counts.zero(s);
     dim3 grid(std::max(1u, std::min(cdiv(maxn, 256), 256u)), N);
-    hipLaunchKernelGGL(k_sh_count, grid, dim3(256), 0, s, (const double*)h->inst.pts.p, (const ShGrid*)d_g.p, cells.p);
+    hipLaunchKernelGGL(k_sh_count, grid, dim3(256), 0, s, (const double*)inst.pts.p, (const ShGrid*)d_g.p, cells.p);
     HMSG_CHECK_LAUNCH();
     hmsg_scan_u32(cells.p, cells.p, (size_t)ncell, s, scan_tmp, nullptr);
-    hipLaunchKernelGGL(k_sh_fill, grid, dim3(256), 0, s, (const double*)h->inst.pts.p, (const ShGrid*)d_g.p, (const unsigned*)cells.p,
+    hipLaunchKernelGGL(k_sh_fill, grid, dim3(256), 0, s, (const double*)inst.pts.p, (const ShGrid*)d_g.p, (const unsigned*)cells.p,
                        cursor.p, sorted.p);
     for (size_t t0 = 0; t0 < tasks.size(); t0 += 32768) {
         unsigned nt = (unsigned)std::min<size_t>(32768, tasks.size() - t0);
@@ -2820,6 +2837,10 @@ void hmsg_room_share(hmsg_ctx* h, int R, const long long* vert_off, const double
     HIP_TRY(hipStreamSynchronize(s));
     for (size_t k = 0; k < tasks.size(); ++k)
         share_out[(size_t)tasks[k].inst * R + tasks[k].room] = (double)hc[k] / (double)g[tasks[k].inst].n;
+}
+void hmsg_room_share(hmsg_ctx* h, int R, const long long* vert_off, const double* verts_xz, double radius, double* share_out) {
+    HMSG_REQUIRE(h->merged, HMSG_ERR_INVALID, "hmsg_instance_room_share: run hmsg_merge_instances first");
+    hmsg_room_share_on(h->stream, h->inst, R, vert_off, verts_xz, radius, share_out);
 }
 
 // ------------------------------------------------------------------------------------------ A9: camera -> room

@@ -521,7 +521,8 @@ void pool_launch_mean_f32(hipStream_t s, const float* X, int D, const PoolSeg* d
 // gathered from the feature table `feats` ([.][D], device) with nan_to_num, and every instance goes through the cosine DBSCAN and the
 // mean over its largest cluster -> out (device, [K][D]); an instance without a valid row gives zeros.
 static void pool_rows(hipStream_t s, DevBuf<unsigned>& scan_tmp, Prof* prof, DbgLaps& laps, const int* idx, const unsigned* valid,
-                      long long P, const std::vector<int>& dn, const float* feats, int D, double eps, int minpts, float* out) {
+                      long long P, const std::vector<int>& dn, const float* feats, int D, double eps, int minpts, float* out,
+                      const std::function<void()>* behind_gram = nullptr) {
     const int K = (int)dn.size();
     DevBuf<unsigned> pos;
     pos.alloc((size_t)std::max<long long>(P, 1));
@@ -611,6 +612,7 @@ static void pool_rows(hipStream_t s, DevBuf<unsigned>& scan_tmp, Prof* prof, Dbg
             hipLaunchKernelGGL(k_pool_gram, dim3((unsigned)tiles), dim3(256), 0, s, (const float*)Xn.p, D, (const PoolSeg*)d_ps.p, K,
                                (float)eps, adj.p, ncount.p);
         }
+        if (behind_gram) (*behind_gram)();        // (host work that may start once the Gram is enqueued; nothing of this stream)
         laps.lap("k_pool_gram");
         pool_cluster(s, (const PoolSeg*)d_ps.p, (long long)R, minpts, (const unsigned*)adj.p, (const unsigned*)ncount.p,
                      (const int*)seg_of_row.p, label.p, seg_first.p, d_changed.p, flabel.p, csize.p, cfirst.p, best.p, &laps);
@@ -635,6 +637,20 @@ void hmsg_pool(hmsg_ctx* h) {
     HMSG_REQUIRE(h->merged, HMSG_ERR_INVALID, "hmsg_pool_instances: run hmsg_merge_instances first");
     const int K = (int)h->inst.off.size() - 1;
     const int D = c.feat_dim;
+    // The object stage of a graph in flight needs the merged instances and nothing of the pooling: it starts here, on a thread and a
+    // stream of its own, and is joined when this call leaves (either way), so no thread of the library runs while the caller owns
+    // the handle.  It reads h->inst and writes none of it; what it made waits in the graph for hmsg_graph_finish.
+    struct EarlyJoin {
+        hmsg_ctx* h;
+        ~EarlyJoin() { hmsg_graph_early_join(h); }
+    } early_join{h};
+    const int early_mode = hmsg_graph_early_mode();
+    bool early_started = false;
+    const std::function<void()> start_early = [&] {
+        if (!early_started) hmsg_graph_early_start(h);
+        early_started = true;
+    };
+    if (early_mode == 1) start_early();
     h->inst_feats.alloc((size_t)std::max(K, 1) * D);
     if (K == 0) {
         h->pooled = true;
@@ -674,7 +690,8 @@ void hmsg_pool(hmsg_ctx* h) {
     hmsg_dump("pool_ds", ds.p, (size_t)P * 24, s);
     hmsg_dump("pool_idx", idx.p, (size_t)P * 4, s);
     hmsg_dump("pool_valid", valid.p, (size_t)P * 4, s);
-    pool_rows(s, ops.scan_tmp, &h->prof, laps, idx.p, valid.p, P, dn, h->feats.p, D, c.feat_dbscan_eps, c.feat_dbscan_min, h->inst_feats.p);
+    pool_rows(s, ops.scan_tmp, &h->prof, laps, idx.p, valid.p, P, dn, h->feats.p, D, c.feat_dbscan_eps, c.feat_dbscan_min, h->inst_feats.p,
+              early_mode == 2 ? &start_early : nullptr);
     h->pooled = true;
 }
 

@@ -132,6 +132,8 @@ extern "C" int hmsg_restore_stage(hmsg_t* h, int64_t V, const double* map_xyz, c
         HMSG_REQUIRE(!h->restored, HMSG_ERR_INVALID, "hmsg_restore_stage: the handle was restored already (hmsg_reset first)");
         HMSG_REQUIRE(h->n_frames == 0 && h->n_offered == 0 && !h->map_ready && !h->merged && !h->tree_partial && !h->fold_pipe, HMSG_ERR_INVALID,
                      "hmsg_restore_stage: the handle holds frames or a map (hmsg_reset first)");
+        hmsg_graph_early_abort(h);
+        ++h->inst_epoch;
         HMSG_REQUIRE(V >= 1 && V <= 0x7fffffffll && map_xyz && n_inst >= 0 && n_inst <= 0x7fffffffll && inst_off && K, HMSG_ERR_INVALID,
                      "hmsg_restore_stage: bad argument (a map of 1 .. 2^31 - 1 points, inst_off and K are needed)");
         // ---- the offsets: checked on the host before anything is sized by them

@@ -20,10 +20,12 @@
 #include <sys/stat.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <map>
+#include <memory>
 #include <string>
 #include <mutex>
 #include <thread>
@@ -89,6 +91,29 @@ struct GObject {
     std::vector<float> emb32;
 };
 
+// What the object stage makes without the pooled features (graph.py:1582-1736 minus the labels): the View nodes, the per-object
+// DBSCAN as a value of its own, object nodes with label -1, and the view <-> object test of every (object, view of its room) pair.
+// hmsg_graph_finish takes it over -- from the early stage that ran beside the pooling, or from its own run of the same steps.
+struct ObjStage {
+    std::vector<GView> views;
+    std::vector<std::vector<int>> room_views;   // per room: its views (global indices)
+    InstanceSet den;                            // the denoised instances, not yet in the handle
+    bool have_den = false;                      // false: the handle's list is the denoised one already (or there is nothing to denoise)
+    std::vector<hmsg_node> nodes;               // label -1
+    std::vector<int32_t> pair_inst, pair_view;
+    std::vector<int> pair_obj;
+    std::vector<uint8_t> vis;
+    std::vector<double> md;
+};
+// the stage beside the pooling: a host thread and a stream of its own (hmsg_pool_instances starts and joins it)
+struct EarlyObjects {
+    std::thread th;
+    bool ok = false;                            // ran to the end: `st` is complete
+    unsigned long long epoch = 0;               // hmsg_ctx::inst_epoch it was made from
+    double run_ms = 0;
+    ObjStage st;
+};
+
 }  // namespace
 
 struct hmsg_shard_ws;                       // (hmsg_query_sharded.hip)
@@ -133,7 +158,13 @@ struct hmsg_graph {
     std::vector<long long> obj_pts_off;
     bool have_obj_pts = false;
     hipStream_t view_stream = nullptr;      // the stream of the distance kernels
+    // the object stage beside the pooling: `registered` says that h->early_graph points here (the scene clears both when it goes first)
+    bool registered = false;
+    std::unique_ptr<EarlyObjects> early;
+    int early_state = HMSG_EARLY_NEVER_MADE;
+    double t_early_ms = 0, t_early_wait_ms = 0;
     ~hmsg_graph() {
+        if (registered && h) hmsg_graph_early_abort(h);
         for (auto& t : workers)
             if (t.joinable()) t.join();
         if (ix) hmsg_index_destroy(ix);
@@ -496,17 +527,14 @@ void build_view_lists(hmsg_graph* g) {
 }
 
 // ---- stage 3: View nodes (:1176-1189), objects (:1582-1736), edges (:1752-1775)
-void graph_finish(hmsg_graph* g, int32_t n_labels, const float* label_feats, const char* const* label_names) {
-    hmsg_ctx* h = g->h;
-    DbgLaps laps("graph_finish", h->stream);
-    join_workers(g);
-    laps.lap("join workers");
+// views: per floor, rooms in order, the room's images in order; the running index counts across the floor's rooms
+void make_views(const hmsg_graph* g, std::vector<GView>& views, std::vector<std::vector<int>>& room_views) {
     const int skip = std::max(1, g->prm.skip_frames);
-    // views: per floor, rooms in order, the room's images in order; the running index counts across the floor's rooms
+    room_views.assign(g->rooms.size(), {});
     for (size_t fi = 0; fi < g->floors.size(); ++fi) {
         int view_index = 0;
         for (int ri : g->floors[fi].rooms) {
-            GRoom& rm = g->rooms[(size_t)ri];
+            const GRoom& rm = g->rooms[(size_t)ri];
             for (int img : rm.imgs) {
                 GView v;
                 v.id = g->floors[fi].id + "_" + std::to_string(rm.index_in_floor) + "_" + std::to_string(view_index++);
@@ -517,29 +545,44 @@ void graph_finish(hmsg_graph* g, int32_t n_labels, const float* label_feats, con
                     v.img_path = g->img_paths[(size_t)img];
                     v.have_path = true;
                 }
-                rm.views.push_back((int)g->views.size());
-                g->views.push_back(std::move(v));
+                room_views[(size_t)ri].push_back((int)views.size());
+                views.push_back(std::move(v));
             }
         }
     }
-    laps.lap("view nodes");
-    // objects
+}
+// the floors and rooms as hmsg_build_object_nodes takes them
+struct RoomTables {
     std::vector<double> fz, fh, verts;
     std::vector<int32_t> room_floor;
-    std::vector<int64_t> voff(1, 0);
-    for (auto& fl : g->floors) fz.push_back(fl.f.zero_level), fh.push_back(fl.f.height);
+    std::vector<int64_t> voff;
+};
+void room_tables(const hmsg_graph* g, RoomTables& t) {
+    t.voff.assign(1, 0);
+    for (auto& fl : g->floors) t.fz.push_back(fl.f.zero_level), t.fh.push_back(fl.f.height);
     for (auto& rm : g->rooms) {
-        room_floor.push_back(rm.floor);
-        verts.insert(verts.end(), rm.verts.begin(), rm.verts.end());
-        voff.push_back(voff.back() + (int64_t)(rm.verts.size() / 2));
+        t.room_floor.push_back(rm.floor);
+        t.verts.insert(t.verts.end(), rm.verts.begin(), rm.verts.end());
+        t.voff.push_back(t.voff.back() + (int64_t)(rm.verts.size() / 2));
     }
-    need(hmsg_build_object_nodes(h, (int32_t)g->floors.size(), fz.data(), fh.data(), (int32_t)g->rooms.size(), room_floor.data(), voff.data(), verts.data(),
-                                 label_feats ? n_labels : 0, label_feats),
-         h, "hmsg_build_object_nodes");
-    laps.lap("hmsg_build_object_nodes");
-    const int64_t N = hmsg_num_nodes(h);
-    std::vector<hmsg_node> nodes((size_t)std::max<int64_t>(N, 1));
-    if (N) need(hmsg_get_nodes(h, nodes.data(), nullptr), h, "hmsg_get_nodes");
+}
+// the camera of every view: world -> camera matrix, image size
+void view_cameras(const hmsg_graph* g, const hmsg_ctx* h, const std::vector<GView>& views, std::vector<double>& pinv, std::vector<int32_t>& wh) {
+    const int skip = std::max(1, g->prm.skip_frames);
+    const size_t NV = views.size();
+    pinv.resize(NV * 16);
+    wh.resize(NV * 2);
+    const int W = g->prm.image_width > 0 ? g->prm.image_width : h->cfg.width, H = g->prm.image_height > 0 ? g->prm.image_height : h->cfg.height;
+    for (size_t v = 0; v < NV; ++v) {
+        const size_t fr = (size_t)(views[v].img / skip);
+        if (g->have_inv) memcpy(&pinv[v * 16], &g->poses_inv[fr * 16], 128);
+        else inv4(&g->poses[fr * 16], &pinv[v * 16]);
+        wh[v * 2] = W;
+        wh[v * 2 + 1] = H;
+    }
+}
+// one GObject per node, in node order
+void add_objects(hmsg_graph* g, const std::vector<hmsg_node>& nodes, int64_t N, int32_t n_labels, const char* const* label_names) {
     for (int64_t k = 0; k < N; ++k) {
         const hmsg_node& nd = nodes[(size_t)k];
         GObject o;
@@ -554,49 +597,162 @@ void graph_finish(hmsg_graph* g, int32_t n_labels, const float* label_feats, con
         rm.objects.push_back((int)g->objects.size());
         g->objects.push_back(std::move(o));
     }
-    laps.lap("object nodes (host)");
-    // view <-> object topology (:1712-1734): every (object, view of its room) pair in object order
-    std::vector<int32_t> pair_inst, pair_view;
-    std::vector<int> pair_obj;
-    for (size_t k = 0; k < g->objects.size(); ++k)
-        for (int v : g->rooms[(size_t)g->objects[k].room].views) {
-            pair_obj.push_back((int)k);
-            pair_inst.push_back(g->objects[k].instance);
-            pair_view.push_back(v);
+}
+// the visible pairs into the objects' view lists, their best views and the views' object lists
+void link_views(hmsg_graph* g, const std::vector<int>& pair_obj, const std::vector<int32_t>& pair_view, const std::vector<uint8_t>& vis,
+                const std::vector<double>& md) {
+    std::vector<double> best_d(g->objects.size(), 0.0);
+    for (size_t p = 0; p < pair_obj.size(); ++p) {
+        if (!vis[p]) continue;
+        GObject& o = g->objects[(size_t)pair_obj[p]];
+        o.views.push_back(pair_view[p]);
+        // best view = the first strictly smallest mean depth, scanning from inf (:1727-1731): a non-finite mean never wins
+        if (md[p] < (o.best_view < 0 ? INFINITY : best_d[(size_t)pair_obj[p]])) {
+            o.best_view = pair_view[p];
+            best_d[(size_t)pair_obj[p]] = md[p];
         }
-    if (!pair_obj.empty()) {
-        const size_t NV = g->views.size();
-        std::vector<double> pinv(NV * 16);
-        std::vector<int32_t> wh(NV * 2);
-        const int W = g->prm.image_width > 0 ? g->prm.image_width : h->cfg.width, H = g->prm.image_height > 0 ? g->prm.image_height : h->cfg.height;
-        for (size_t v = 0; v < NV; ++v) {
-            const size_t fr = (size_t)(g->views[v].img / skip);
-            if (g->have_inv) memcpy(&pinv[v * 16], &g->poses_inv[fr * 16], 128);
-            else inv4(&g->poses[fr * 16], &pinv[v * 16]);
-            wh[v * 2] = W;
-            wh[v * 2 + 1] = H;
-        }
-        HMSG_REQUIRE(h->have_K, HMSG_ERR_INVALID, "hmsg_graph_finish: no camera intrinsics (hmsg_add_frames)");
-        std::vector<uint8_t> vis(pair_obj.size());
-        std::vector<double> md(pair_obj.size());
-        need(hmsg_object_views(h, (int32_t)NV, pinv.data(), wh.data(), h->K, (int64_t)pair_obj.size(), pair_inst.data(), pair_view.data(),
-                               g->prm.min_visible_ratio, g->prm.max_view_depth, vis.data(), md.data()),
-             h, "hmsg_object_views");
-        laps.lap("hmsg_object_views");
-        std::vector<double> best_d(g->objects.size(), 0.0);
-        for (size_t p = 0; p < pair_obj.size(); ++p) {
-            if (!vis[p]) continue;
-            GObject& o = g->objects[(size_t)pair_obj[p]];
-            o.views.push_back(pair_view[p]);
-            // best view = the first strictly smallest mean depth, scanning from inf (:1727-1731): a non-finite mean never wins
-            if (md[p] < (o.best_view < 0 ? INFINITY : best_d[(size_t)pair_obj[p]])) {
-                o.best_view = pair_view[p];
-                best_d[(size_t)pair_obj[p]] = md[p];
-            }
-            g->views[(size_t)pair_view[p]].objects.push_back(pair_obj[p]);   // (pairs come in object order: ascending per view)
-        }
+        g->views[(size_t)pair_view[p]].objects.push_back(pair_obj[p]);   // (pairs come in object order: ascending per view)
     }
-    laps.lap("view lists (host)");
+}
+
+// The part of the object stage that needs nothing of the pooling, on stream s against the handle's merged instances, which it only
+// reads: neither the graph nor the handle is written (but for the stage's own scratch, h->early_ops), everything goes into `st`.
+void object_stage(const hmsg_graph* g, hmsg_ctx* h, hipStream_t s, ObjStage& st) {
+    DbgLaps laps("early objects", s);
+    make_views(g, st.views, st.room_views);
+    laps.lap("view nodes");
+    RoomTables t;
+    room_tables(g, t);
+    st.have_den = !h->inst_denoised && hmsg_denoise_compute(s, h->inst, 0.05, 10, st.den, &h->early_ops);
+    laps.lap("per-object DBSCAN");
+    const InstanceSet& inst = st.have_den ? st.den : h->inst;
+    const int N = (int)inst.off.size() - 1, R = (int)g->rooms.size();
+    if (N > 0) {
+        std::vector<double> share((size_t)N * std::max(R, 1), 0.0);
+        if (R > 0) hmsg_room_share_on(s, inst, R, (const long long*)t.voff.data(), t.verts.data(), 0.2, share.data());
+        laps.lap("room shares");
+        hmsg_object_nodes_on(s, inst, (int)g->floors.size(), t.fz.data(), t.fh.data(), R, t.room_floor.data(), t.voff.data(), t.verts.data(), share.data(),
+                             st.nodes);
+        laps.lap("floors / rooms (host)");
+    }
+    // view <-> object topology (:1712-1734): every (object, view of its room) pair in object order; object k is node k
+    for (size_t k = 0; k < st.nodes.size(); ++k)
+        for (int v : st.room_views[(size_t)st.nodes[k].room]) {
+            st.pair_obj.push_back((int)k);
+            st.pair_inst.push_back(st.nodes[k].instance);
+            st.pair_view.push_back(v);
+        }
+    if (!st.pair_obj.empty()) {
+        std::vector<double> pinv;
+        std::vector<int32_t> wh;
+        view_cameras(g, h, st.views, pinv, wh);
+        HMSG_REQUIRE(h->have_K, HMSG_ERR_INVALID, "hmsg_graph_finish: no camera intrinsics (hmsg_add_frames)");
+        st.vis.resize(st.pair_obj.size());
+        st.md.resize(st.pair_obj.size());
+        hmsg_object_views_on(s, inst, (int32_t)st.views.size(), pinv.data(), wh.data(), h->K, (int64_t)st.pair_obj.size(), st.pair_inst.data(),
+                             st.pair_view.data(), g->prm.min_visible_ratio, g->prm.max_view_depth, st.vis.data(), st.md.data());
+        laps.lap("hmsg_object_views");
+    }
+}
+
+std::atomic<int> g_early_threads{0};        // early-stage threads started and not yet joined (test hook)
+
+void early_drop(hmsg_graph* g, hmsg_ctx* h) {
+    g->early.reset();
+    g->early_state = HMSG_EARLY_DISCARDED;
+    h->early_last = HMSG_EARLY_DISCARDED;
+}
+void early_unregister(hmsg_graph* g, hmsg_ctx* h) {
+    if (h->early_graph == g) h->early_graph = nullptr;
+    g->registered = false;
+}
+
+// the early result when it is there, complete, and made from the instances the handle holds now
+std::unique_ptr<EarlyObjects> early_take(hmsg_graph* g) {
+    hmsg_ctx* h = g->h;
+    if (!g->registered || h->early_graph != g) return nullptr;
+    const double t0 = now_ms();
+    hmsg_graph_early_join(h);               // (hmsg_pool_instances joined it on leaving: nothing to wait for)
+    g->t_early_wait_ms += now_ms() - t0;
+    if (!g->early) return nullptr;
+    if (!g->early->ok || g->early->epoch != h->inst_epoch) {
+        early_drop(g, h);
+        return nullptr;
+    }
+    return std::move(g->early);
+}
+
+void graph_finish(hmsg_graph* g, int32_t n_labels, const float* label_feats, const char* const* label_names) {
+    hmsg_ctx* h = g->h;
+    DbgLaps laps("graph_finish", h->stream);
+    std::unique_ptr<EarlyObjects> early = early_take(g);
+    if (laps.on)
+        fprintf(stderr, "[hmsg graph_finish] early objects %s: the stage ran %.3f ms, the caller waited %.3f ms for it\n",
+                early ? "taken" : "not there", g->t_early_ms, g->t_early_wait_ms);
+    join_workers(g);
+    laps.lap("join workers");
+    if (early) {
+        // the stage ran beside the pooling: what is left is the commit of its instances, the labels, and the lists
+        ObjStage& st = early->st;
+        for (size_t r = 0; r < g->rooms.size(); ++r) g->rooms[r].views.insert(g->rooms[r].views.end(), st.room_views[r].begin(), st.room_views[r].end());
+        for (auto& v : st.views) g->views.push_back(std::move(v));
+        laps.lap("view nodes");
+        if (!h->inst_denoised) {
+            if (st.have_den) hmsg_denoise_commit(h, st.den);
+            h->inst_denoised = true;
+        }
+        g->early_state = h->early_last = HMSG_EARLY_CONSUMED;
+        h->nodes.clear();
+        hmsg_node_labels(h, label_feats ? n_labels : 0, label_feats);
+        h->nodes = std::move(st.nodes);
+        for (hmsg_node& nd : h->nodes) nd.label = h->node_label[(size_t)nd.instance];
+        laps.lap("label similarity");
+        add_objects(g, h->nodes, (int64_t)h->nodes.size(), n_labels, label_names);
+        laps.lap("object nodes (host)");
+        link_views(g, st.pair_obj, st.pair_view, st.vis, st.md);
+        laps.lap("view lists (host)");
+    } else {
+        std::vector<std::vector<int>> room_views;
+        make_views(g, g->views, room_views);
+        for (size_t r = 0; r < g->rooms.size(); ++r) g->rooms[r].views.insert(g->rooms[r].views.end(), room_views[r].begin(), room_views[r].end());
+        laps.lap("view nodes");
+        // objects
+        RoomTables t;
+        room_tables(g, t);
+        need(hmsg_build_object_nodes(h, (int32_t)g->floors.size(), t.fz.data(), t.fh.data(), (int32_t)g->rooms.size(), t.room_floor.data(), t.voff.data(),
+                                     t.verts.data(), label_feats ? n_labels : 0, label_feats),
+             h, "hmsg_build_object_nodes");
+        laps.lap("hmsg_build_object_nodes");
+        const int64_t N = hmsg_num_nodes(h);
+        std::vector<hmsg_node> nodes((size_t)std::max<int64_t>(N, 1));
+        if (N) need(hmsg_get_nodes(h, nodes.data(), nullptr), h, "hmsg_get_nodes");
+        add_objects(g, nodes, N, n_labels, label_names);
+        laps.lap("object nodes (host)");
+        // view <-> object topology (:1712-1734): every (object, view of its room) pair in object order
+        std::vector<int32_t> pair_inst, pair_view;
+        std::vector<int> pair_obj;
+        for (size_t k = 0; k < g->objects.size(); ++k)
+            for (int v : g->rooms[(size_t)g->objects[k].room].views) {
+                pair_obj.push_back((int)k);
+                pair_inst.push_back(g->objects[k].instance);
+                pair_view.push_back(v);
+            }
+        if (!pair_obj.empty()) {
+            const size_t NV = g->views.size();
+            std::vector<double> pinv;
+            std::vector<int32_t> wh;
+            view_cameras(g, h, g->views, pinv, wh);
+            HMSG_REQUIRE(h->have_K, HMSG_ERR_INVALID, "hmsg_graph_finish: no camera intrinsics (hmsg_add_frames)");
+            std::vector<uint8_t> vis(pair_obj.size());
+            std::vector<double> md(pair_obj.size());
+            need(hmsg_object_views(h, (int32_t)NV, pinv.data(), wh.data(), h->K, (int64_t)pair_obj.size(), pair_inst.data(), pair_view.data(),
+                                   g->prm.min_visible_ratio, g->prm.max_view_depth, vis.data(), md.data()),
+                 h, "hmsg_object_views");
+            laps.lap("hmsg_object_views");
+            link_views(g, pair_obj, pair_view, vis, md);
+        }
+        laps.lap("view lists (host)");
+    }
     for (auto& o : g->objects) {
         for (int v : o.views) o.view_ids.push_back(g->views[(size_t)v].id);
         if (o.best_view >= 0) o.best_view_id = g->views[(size_t)o.best_view].id, o.have_best = true;
@@ -607,6 +763,7 @@ void graph_finish(hmsg_graph* g, int32_t n_labels, const float* label_feats, con
             v.texts.push_back(g->objects[(size_t)k].name);
         }
     if (g->prm.merge_objects_graph && !g->objects.empty()) {
+        std::vector<hmsg_node> nodes(g->objects.size());
         std::vector<float> node_emb(g->objects.size() * (size_t)g->D);
         need(hmsg_get_nodes(h, nodes.data(), node_emb.data()), h, "hmsg_get_nodes");
         graph_merge_objects(g, node_emb);
@@ -615,6 +772,8 @@ void graph_finish(hmsg_graph* g, int32_t n_labels, const float* label_feats, con
     // edges (create_graph_new): a freshly built View carries an int room index, so no Room - View edge (view_room = -1)
     std::vector<int32_t> obj_room, view_room(g->views.size(), -1), vobj;
     std::vector<int64_t> vooff(1, 0);
+    std::vector<int32_t> room_floor;
+    for (auto& rm : g->rooms) room_floor.push_back(rm.floor);
     for (auto& o : g->objects) obj_room.push_back(o.room);
     for (auto& v : g->views) {
         vobj.insert(vobj.end(), v.objects.begin(), v.objects.end());
@@ -871,6 +1030,88 @@ hmsg_json_field num0(const char* key, const double* v) { return hmsg_json_field{
 
 }  // namespace
 
+// ---------------------------------------------------------------------------------- the object stage beside the pooling
+// hmsg_pool_instances is MFMA-bound and asks little of the memory system; the per-object DBSCAN, the room shares and the view test
+// are bound by L2 latency and atomics and need only the merged instances and the room level.  The stage therefore runs while the
+// pooling does, on a host thread and a normal-priority stream of its own, and leaves its result in the graph; the handle is not
+// written before hmsg_graph_finish commits (between the two calls every getter answers as it did before).
+int hmsg_graph_early_mode() {
+    const char* e = getenv("HMSG_GRAPH_EARLY_OBJECTS");        // (read at every call: the A/B switch inside one build)
+    if (!e || !*e) return 1;
+    return e[0] == '0' ? 0 : (e[0] == '2' ? 2 : 1);
+}
+
+void hmsg_graph_early_start(hmsg_ctx* h) {
+    hmsg_graph* g = h->early_graph;
+    if (!g || !g->registered || g->h != h || !g->begun || g->finished || g->failed || !h->merged || h->restored) return;
+    if (hmsg_graph_early_mode() == 0) return;
+    if (g->early) {
+        if (g->early->th.joinable()) return;                              // (running: hmsg_pool_instances is not re-entered)
+        if (g->early->ok && g->early->epoch == h->inst_epoch) return;     // a second pooling of the same instances: the result stands
+        g->early.reset();
+    }
+    g->early.reset(new EarlyObjects());
+    EarlyObjects* e = g->early.get();
+    e->epoch = h->inst_epoch;
+    ++g_early_threads;
+    e->th = std::thread([g, h, e] {
+        const double t0 = now_ms();
+        hipStream_t s = nullptr;
+        // the merge fold's allocator cache is idle (its worker was joined before h->merged was set) and warm: the stage's scratch comes
+        // from it and goes back to it, apart from the calling thread's cache
+        dev_cache().swap_state(h->fold_cache);
+        try {
+            if (getenv("HMSG_DEBUG_EARLY_OBJECTS_THROW")) throw hmsg_error{HMSG_ERR_INVALID, "early object stage: HMSG_DEBUG_EARLY_OBJECTS_THROW"};
+            HIP_TRY(hipSetDevice(h->cfg.device_id));
+            HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));     // normal priority: the Gram beside it is the critical part
+            join_workers(g);                                                 // the views come from the room level
+            object_stage(g, h, s, e->st);
+            HIP_TRY(hipStreamSynchronize(s));
+            e->ok = true;
+        } catch (...) {          // not reported: hmsg_graph_finish recomputes, and an error surfaces where it does without this stage
+            if (s) (void)hipStreamSynchronize(s);
+            (void)hipGetLastError();
+            e->st.den.pts.release();      // (into the cache it came from)
+        }
+        if (s) {
+            (void)hipStreamSynchronize(s);
+            (void)hipStreamDestroy(s);
+        }
+        h->fold_cache.swap_state(dev_cache());
+        e->run_ms = now_ms() - t0;
+    });
+}
+
+void hmsg_graph_early_join(hmsg_ctx* h) noexcept {
+    hmsg_graph* g = h->early_graph;
+    if (!g || !g->early || !g->early->th.joinable()) return;
+    const double t0 = now_ms();
+    g->early->th.join();
+    --g_early_threads;
+    g->t_early_ms = g->early->run_ms;
+    const bool ok = g->early->ok;
+    if (getenv("HMSG_DEBUG_TIMING"))
+        fprintf(stderr, "[hmsg early objects] the stage ran %.3f ms (%s); joining it took %.3f ms\n", g->early->run_ms, ok ? "complete" : "gave up",
+                now_ms() - t0);
+    if (ok) g->early_state = h->early_last = HMSG_EARLY_PENDING;
+    else early_drop(g, h);          // (hmsg_graph_finish recomputes; an error surfaces there, where it does without this stage)
+}
+
+void hmsg_graph_early_abort(hmsg_ctx* h) noexcept {
+    hmsg_graph* g = h->early_graph;
+    if (!g) return;
+    hmsg_graph_early_join(h);
+    if (!g->finished) early_drop(g, h);
+    early_unregister(g, h);
+}
+
+extern "C" int hmsg_test_graph_early_objects(const hmsg_graph_t* g, const hmsg_t* h, int32_t* state, int32_t* live_threads) {
+    if (!g && !h) return HMSG_ERR_INVALID;
+    if (state) *state = g ? g->early_state : h->early_last;
+    if (live_threads) *live_threads = g_early_threads.load();
+    return HMSG_OK;
+}
+
 // ================================================================================================= C ABI
 extern "C" {
 
@@ -977,6 +1218,12 @@ int hmsg_graph_begin(hmsg_t* h, const hmsg_graph_params* prm, int32_t n_frames, 
         delete g;
         return rc;
     }
+    // the scene knows its graph in flight, so that hmsg_pool_instances can start the object stage beside itself; a graph begun on
+    // the scene before loses its place (and whatever its stage had made): it finishes by its own run of the stage
+    hmsg_graph_early_abort(h);
+    h->early_graph = g;
+    g->registered = true;
+    h->early_last = HMSG_EARLY_NEVER_MADE;
     *out = g;
     return HMSG_OK;
 }
@@ -994,8 +1241,11 @@ int hmsg_graph_finish(hmsg_graph_t* g, int32_t n_labels, const float* label_feat
             graph_finish(g, n_labels, label_feats, label_names);
         } catch (...) {
             g->failed = true;
+            g->early.reset();
+            early_unregister(g, g->h);
             throw;
         }
+        early_unregister(g, g->h);
         g->t_finish_ms = now_ms() - t0;
     });
 }

@@ -95,6 +95,21 @@ int hmsg_test_group_pairs(int32_t device_id, int64_t n, const double* boxes, int
 int hmsg_test_overlap(hmsg_t* h, int32_t K, const int64_t* sizes, const int64_t* n_base, const double* pts, int64_t P,
                       const int32_t* pairs, double decide_th, uint32_t* out_counts, uint8_t* out_state, double* out_ratio);
 
+/* test hook: what became of the object stage that hmsg_pool_instances runs beside itself for the graph begun on its scene
+ * (hmsg_graph_begin registers the graph with the scene; HMSG_GRAPH_EARLY_OBJECTS=0 switches the stage off).
+ *   g != NULL: the graph's own record; g == NULL: the record of the scene h, i.e. of the graph registered on it last (for a graph
+ *   that is gone).  A graph that outlived its scene is asked with h == NULL.
+ *   state: 0 never made -- no stage ran for the graph, hmsg_graph_finish did (or will do) all of it itself;
+ *          1 consumed   -- hmsg_graph_finish took the stage's result over;
+ *          2 discarded  -- the registration ended before a finish could take a result: by hmsg_reset, hmsg_destroy,
+ *                          hmsg_restore_stage, hmsg_merge_tree_*, another hmsg_graph_begin on the scene or the graph's destroy
+ *                          (whatever the stage had made by then is dropped, its thread joined), or the result was incomplete or
+ *                          made from other instances than the scene holds at the finish;
+ *          3 pending    -- the stage ran to its end beside hmsg_pool_instances and its result waits in the graph for the finish.
+ *   live_threads: threads of the stage, over all scenes of the process, that were started and are not joined yet -- 0 whenever no
+ *   hmsg_pool_instances call is running. */
+int hmsg_test_graph_early_objects(const hmsg_graph_t* g, const hmsg_t* h, int32_t* state, int32_t* live_threads);
+
 #ifdef __cplusplus
 }
 #endif
