@@ -107,6 +107,9 @@ _SIGS = {
     "hmsg_map_size_unfiltered": (C.c_int64, [_P]),
     "hmsg_get_map_points": (C.c_int, [_P, _P, _P]),
     "hmsg_add_frame_features": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
+    "hmsg_add_frame_features_rle": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    "hmsg_rle_to_bitsets": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    "hmsg_rle_to_masks": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     "hmsg_get_frame_num_masks": (C.c_int32, [_P, C.c_int32]),
     "hmsg_fuse_frames": (C.c_int, [_P]),
     "hmsg_get_map_feats": (C.c_int, [_P, _P, _P]),
@@ -441,6 +444,26 @@ class Scene:
         nm = None if n_masks is None else np.ascontiguousarray(n_masks, dtype=np.int32)
         self._ck(self.L.c.hmsg_add_frame_features(self.h, first, n, M, _ptr(masks), _ptr(f_g), _ptr(f_masked), _ptr(f_crop),
                                                   _ptr(nm)))
+
+    def add_frame_features_rle(self, first, rles, f_g, f_masked, f_crop):
+        """The same hand-over with the masks as SAM's uncompressed run-length records (holoagent_amd/rle.py; include/hmsg.h:
+        hmsg_add_frame_features_rle): rles = (counts u32, run_off i64 [T + 1], n_masks i32 [n]) as rle.pack makes them -- numpy
+        arrays or torch device tensors -- or a list (frames) of lists (masks) of counts, which is packed here.  f_g [n, D],
+        f_masked / f_crop [n, M, D] with M >= every frame's mask count.  No dense mask is built."""
+        if isinstance(rles, (list,)) or (isinstance(rles, tuple) and len(rles) != 3):
+            from . import rle as _rle
+            rles = _rle.pack(rles)
+        counts, run_off, n_masks = rles
+        if isinstance(counts, np.ndarray) or not hasattr(counts, "data_ptr"):
+            counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        if isinstance(run_off, np.ndarray) or not hasattr(run_off, "data_ptr"):
+            run_off = np.ascontiguousarray(run_off, dtype=np.int64)
+        if isinstance(n_masks, np.ndarray) or not hasattr(n_masks, "data_ptr"):
+            n_masks = np.ascontiguousarray(n_masks, dtype=np.int32)
+        n, M = int(f_masked.shape[0]), int(f_masked.shape[1])
+        assert int(n_masks.shape[0]) == n, "n_masks: one entry per frame of f_masked"
+        self._ck(self.L.c.hmsg_add_frame_features_rle(self.h, first, n, M, _ptr(counts), _ptr(run_off), _ptr(n_masks), _ptr(f_g),
+                                                      _ptr(f_masked), _ptr(f_crop)))
 
     def frame_num_masks(self, frame):
         return int(self.L.c.hmsg_get_frame_num_masks(self.h, frame))
@@ -1377,6 +1400,45 @@ def crop_all_bounding_boxs(image, masks, bbox_margin=0, size=512, plain=True, ma
     if rc != 0:
         raise HmsgError(f"hmsg_crop_resize_batch failed ({rc})")
     return o_plain, o_masked
+
+
+def _rle_one_frame(fn, rles, H, W, out_dtype, device_id, lib_):
+    L = lib_ or lib()
+    if isinstance(rles, list):
+        from . import rle as _rle
+        counts, run_off, _ = _rle.pack([rles])
+    else:
+        counts, run_off = rles[0], rles[1]
+    on_dev = hasattr(counts, "data_ptr") and getattr(counts, "is_cuda", False)
+    if not on_dev:
+        counts, run_off = np.ascontiguousarray(counts, dtype=np.uint32), np.ascontiguousarray(run_off, dtype=np.int64)
+    M = int(run_off.shape[0]) - 1
+    NW = (max(M, 1) + 63) // 64
+    shape = (H * W, NW) if out_dtype == "bits" else (M, H, W)
+    if on_dev:
+        import torch
+        device_id = counts.device.index or 0
+        # (torch has no uint64 arithmetic: the words travel as int64 with the same bits)
+        out = torch.empty(shape, dtype=torch.int64 if out_dtype == "bits" else torch.uint8, device=counts.device)
+    else:
+        out = np.empty(shape, np.uint64 if out_dtype == "bits" else np.uint8)
+    rc = getattr(L.c, fn)(int(device_id), int(H), int(W), M, _ptr(counts) if M else None, _ptr(run_off), _ptr(out) if int(np.prod(shape)) else None)
+    if rc != 0:
+        raise HmsgError(f"{fn} failed ({rc}): malformed run-length masks (the message is on stderr)")
+    return out
+
+
+def rle_to_bitsets(rles, H, W, device_id=0, lib_: "HmsgLib | None" = None):
+    """One frame's run-length masks -> per-pixel membership bitsets [H * W, NW] (include/hmsg.h: hmsg_rle_to_bitsets): bit i & 63
+    of word i >> 6 of pixel y * W + x says that mask i covers it.  rles: a list of counts (one per mask) or (counts, run_off) as
+    rle.pack makes them, numpy arrays (returns numpy uint64) or torch device tensors (returns a device tensor, int64 bits)."""
+    return _rle_one_frame("hmsg_rle_to_bitsets", rles, H, W, "bits", device_id, lib_)
+
+
+def rle_to_masks(rles, H, W, device_id=0, lib_: "HmsgLib | None" = None):
+    """One frame's run-length masks -> dense uint8 [M, H, W] (0 / 1) made on the device (include/hmsg.h: hmsg_rle_to_masks): with
+    device tensors in, the dense masks the crop calls read never exist on the host.  rles as in rle_to_bitsets."""
+    return _rle_one_frame("hmsg_rle_to_masks", rles, H, W, "masks", device_id, lib_)
 
 
 def _clip_params(L, size, f16, mean, std):

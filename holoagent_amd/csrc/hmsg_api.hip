@@ -2,13 +2,14 @@
 #include "hmsg_boundary.h"
 #include "hmsg_ckdtree.h"
 #include "hmsg_nn.h"
+#include "hmsg_rle.h"
 
 #include <algorithm>
 #include <cstring>
 #include <stdexcept>
 
-void hmsg_bitset_and_fp(hmsg_ctx* h, int first, int n, int M, const unsigned char* d_masks, const float* d_fg,
-                        const float* d_fm, const float* d_fc, const int* d_nmask);   // hmsg_fuse.hip
+void hmsg_bitset(hmsg_ctx* h, int first, int n, int M, const unsigned char* d_masks, const int* d_nmask);   // hmsg_fuse.hip
+void hmsg_fp_tables(hmsg_ctx* h, int first, int n, int M, const float* d_fg, const float* d_fm, const float* d_fc, const int* d_nmask);
 
 // ---- bit-equal nearest-neighbour ties: host side ----------------------------------------------------------------
 __global__ void k_nn_patch(const long long* __restrict__ qid, const int* __restrict__ val, unsigned n, int* __restrict__ target) {
@@ -364,69 +365,114 @@ int hmsg_get_map_points(const hmsg_t* hc, double* xyz, double* rgb) {
     });
 }
 
+// A hand-over of encoder outputs for frames [first, first + n), whichever form the masks come in: the order and state checks,
+// the per-frame mask counts, the frames without any mask, the F tables staged chunk by chunk, k_fp, and the handle's
+// bookkeeping.  `fn` names the entry point in the messages.  The masks' side is three callbacks:
+//   plan(nm)            once, after the checks and before anything of the handle is written (nm: masks per frame);
+//   chunk(c0) -> nc     how many frames the chunk that starts at frame c0 of the hand-over takes;
+//   bits(c0, nc, d_nm)  the membership bitsets of these frames into h->bits, on h->stream (d_nm: their counts on the device).
+extern "C++" template <typename Plan, typename Chunk, typename Bits>
+static void add_frame_features(hmsg_ctx* h, const std::string& fn, int first, int n, int M, bool have_masks, const float* F_g,
+                               const float* F_masked, const float* F_crop, const int32_t* n_masks, Plan&& plan, Chunk&& chunk,
+                               Bits&& bits) {
+    HMSG_REQUIRE(n >= 0 && F_g, HMSG_ERR_INVALID, fn + ": null argument");
+    HMSG_REQUIRE(!h->restored, HMSG_ERR_INVALID,
+                 fn + ": the handle was restored from stage artefacts (hmsg_restore_stage): no frames, no voxel bitmap");
+    HMSG_REQUIRE(M >= 0 && M <= h->cfg.max_masks, HMSG_ERR_INVALID, "M out of range (cfg.max_masks, <= 256)");
+    HMSG_REQUIRE(M == 0 || (have_masks && F_masked && F_crop), HMSG_ERR_INVALID, fn + ": null argument");
+    HMSG_REQUIRE(first == h->n_feat_frames, HMSG_ERR_INVALID, "frames must be handed over in order (first == #frames so far)");
+    HMSG_REQUIRE(first + n <= h->n_frames, HMSG_ERR_INVALID, "features for a frame without geometry");
+    HMSG_REQUIRE(!h->frames_released, HMSG_ERR_INVALID, fn + ": the frame store was released (hmsg_reset first)");
+    if (n == 0) return;
+    const size_t HW = (size_t)h->cfg.height * h->cfg.width;
+    const int D = h->cfg.feat_dim;
+    const size_t NW = (size_t)h->NW, MS = (size_t)h->MS;
+    // per-frame mask counts (host copy kept: the 3-D mask store holds nmask[f] clouds for frame f)
+    std::vector<int> nm((size_t)n, M);
+    if (n_masks) {
+        read_in(nm.data(), n_masks, (size_t)n * 4);
+        for (int f = 0; f < n; ++f)
+            HMSG_REQUIRE(nm[(size_t)f] >= 0 && nm[(size_t)f] <= M, HMSG_ERR_INVALID,
+                         "n_masks[f] must be in [0, M] (frame " + std::to_string(f) + " of the hand-over)");
+    }
+    if (M > 0) plan(nm);
+    if (h->bits.n < (size_t)h->cfg.max_frames * HW * NW) h->bits.alloc((size_t)h->cfg.max_frames * HW * NW);
+    if (h->fp.n < (size_t)h->cfg.max_frames * MS * D) h->fp.alloc((size_t)h->cfg.max_frames * MS * D);
+    DevBuf<int> d_nm;
+    d_nm.alloc((size_t)n);
+    HIP_TRY(hipMemcpyAsync(d_nm.p, nm.data(), (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+    if (M == 0) {   // no mask in any of these frames: empty bitsets, no F_p rows
+        HIP_TRY(hipMemsetAsync(h->bits.p + (size_t)first * HW * NW, 0, (size_t)n * HW * NW * 8, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        h->nmask.insert(h->nmask.end(), nm.begin(), nm.end());
+        h->n_feat_frames += n;
+        return;
+    }
+    DevBuf<float> st_f;
+    for (int c0 = 0; c0 < n;) {
+        const int nc = std::max(1, std::min((int)chunk(c0), n - c0));
+        const float *dg = F_g + (size_t)c0 * D, *dfm = F_masked + (size_t)c0 * M * D, *dfc = F_crop + (size_t)c0 * M * D;
+        bits(c0, nc, (const int*)d_nm.p + c0);
+        if (!hmsg_is_device_ptr(F_g) || !hmsg_is_device_ptr(F_masked) || !hmsg_is_device_ptr(F_crop)) {
+            st_f.ensure((size_t)nc * (2 * M + 1) * D);
+            float* g = st_f.p;
+            float* fm = g + (size_t)nc * D;
+            float* fc = fm + (size_t)nc * M * D;
+            copy_in(g, dg, (size_t)nc * D * 4, h->stream, Up::direct);
+            copy_in(fm, dfm, (size_t)nc * M * D * 4, h->stream, Up::direct);
+            copy_in(fc, dfc, (size_t)nc * M * D * 4, h->stream, Up::direct);
+            dg = g;
+            dfm = fm;
+            dfc = fc;
+        }
+        hmsg_fp_tables(h, first + c0, nc, M, dg, dfm, dfc, d_nm.p + c0);
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        c0 += nc;
+    }
+    h->nmask.insert(h->nmask.end(), nm.begin(), nm.end());
+    h->n_feat_frames += n;
+}
+
 int hmsg_add_frame_features(hmsg_t* h, int32_t first, int32_t n, int32_t M, const uint8_t* masks, const float* F_g,
                             const float* F_masked, const float* F_crop, const int32_t* n_masks) {
     if (!h) return HMSG_ERR_INVALID;
     return hmsg_boundary(h, [&] {
-        HMSG_REQUIRE(n >= 0 && F_g, HMSG_ERR_INVALID, "hmsg_add_frame_features: null argument");
-        HMSG_NOT_RESTORED(h, "hmsg_add_frame_features");
-        HMSG_REQUIRE(M >= 0 && M <= h->cfg.max_masks, HMSG_ERR_INVALID, "M out of range (cfg.max_masks, <= 256)");
-        HMSG_REQUIRE(M == 0 || (masks && F_masked && F_crop), HMSG_ERR_INVALID, "hmsg_add_frame_features: null argument");
-        HMSG_REQUIRE(first == h->n_feat_frames, HMSG_ERR_INVALID, "frames must be handed over in order (first == #frames so far)");
-        HMSG_REQUIRE(first + n <= h->n_frames, HMSG_ERR_INVALID, "features for a frame without geometry");
-        HMSG_REQUIRE(!h->frames_released, HMSG_ERR_INVALID, "hmsg_add_frame_features: the frame store was released (hmsg_reset first)");
-        if (n == 0) return;
         const size_t HW = (size_t)h->cfg.height * h->cfg.width;
-        const int D = h->cfg.feat_dim;
-        const size_t NW = (size_t)h->NW, MS = (size_t)h->MS;
-        if (h->bits.n < (size_t)h->cfg.max_frames * HW * NW) h->bits.alloc((size_t)h->cfg.max_frames * HW * NW);
-        if (h->fp.n < (size_t)h->cfg.max_frames * MS * D) h->fp.alloc((size_t)h->cfg.max_frames * MS * D);
-        // per-frame mask counts (host copy kept: the 3-D mask store holds nmask[f] clouds for frame f)
-        std::vector<int> nm((size_t)n, M);
-        if (n_masks) {
-            read_in(nm.data(), n_masks, (size_t)n * 4);
-            for (int v : nm) HMSG_REQUIRE(v >= 0 && v <= M, HMSG_ERR_INVALID, "n_masks[f] must be in [0, M]");
-        }
-        DevBuf<int> d_nm;
-        d_nm.alloc((size_t)n);
-        HIP_TRY(hipMemcpyAsync(d_nm.p, nm.data(), (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
-        if (M == 0) {   // no mask in any of these frames: empty bitsets, no F_p rows
-            HIP_TRY(hipMemsetAsync(h->bits.p + (size_t)first * HW * NW, 0, (size_t)n * HW * NW * 8, h->stream));
-            HIP_TRY(hipStreamSynchronize(h->stream));
-            h->nmask.insert(h->nmask.end(), nm.begin(), nm.end());
-            h->n_feat_frames += n;
-            return;
-        }
-        const bool dev = hmsg_is_device_ptr(masks);
-        const int chunk = dev ? n : std::max(1, (int)(((size_t)512 << 20) / ((size_t)M * HW)));
+        const bool dev = masks && hmsg_is_device_ptr(masks);
+        const int chunk = dev ? std::max(n, 1) : std::max(1, (int)(((size_t)512 << 20) / ((size_t)std::max(M, 1) * HW)));
         DevBuf<unsigned char> st_m;
-        DevBuf<float> st_f;
-        for (int c0 = 0; c0 < n; c0 += chunk) {
-            int nc = std::min(chunk, n - c0);
-            const unsigned char* dm = masks + (size_t)c0 * M * HW;
-            const float *dg = F_g + (size_t)c0 * D, *dfm = F_masked + (size_t)c0 * M * D, *dfc = F_crop + (size_t)c0 * M * D;
-            if (!dev) {
-                st_m.ensure((size_t)nc * M * HW);
-                HIP_TRY(hipMemcpyAsync(st_m.p, dm, (size_t)nc * M * HW, hipMemcpyHostToDevice, h->stream));
-                dm = st_m.p;
-            }
-            if (!hmsg_is_device_ptr(F_g) || !hmsg_is_device_ptr(F_masked) || !hmsg_is_device_ptr(F_crop)) {
-                st_f.ensure((size_t)nc * (2 * M + 1) * D);
-                float* g = st_f.p;
-                float* fm = g + (size_t)nc * D;
-                float* fc = fm + (size_t)nc * M * D;
-                copy_in(g, dg, (size_t)nc * D * 4, h->stream, Up::direct);
-                copy_in(fm, dfm, (size_t)nc * M * D * 4, h->stream, Up::direct);
-                copy_in(fc, dfc, (size_t)nc * M * D * 4, h->stream, Up::direct);
-                dg = g;
-                dfm = fm;
-                dfc = fc;
-            }
-            hmsg_bitset_and_fp(h, first + c0, nc, M, dm, dg, dfm, dfc, d_nm.p + c0);
-            HIP_TRY(hipStreamSynchronize(h->stream));
-        }
-        h->nmask.insert(h->nmask.end(), nm.begin(), nm.end());
-        h->n_feat_frames += n;
+        add_frame_features(
+            h, "hmsg_add_frame_features", first, n, M, masks != nullptr, F_g, F_masked, F_crop, n_masks, [](const std::vector<int>&) {},
+            [&](int) { return chunk; },
+            [&](int c0, int nc, const int* d_nm) {
+                const unsigned char* dm = masks + (size_t)c0 * M * HW;
+                if (!dev) {
+                    st_m.ensure((size_t)nc * M * HW);
+                    HIP_TRY(hipMemcpyAsync(st_m.p, dm, (size_t)nc * M * HW, hipMemcpyHostToDevice, h->stream));
+                    dm = st_m.p;
+                }
+                hmsg_bitset(h, first + c0, nc, M, dm, d_nm);
+            });
+    });
+}
+
+int hmsg_add_frame_features_rle(hmsg_t* h, int32_t first, int32_t n, int32_t M, const uint32_t* counts, const int64_t* run_off,
+                                const int32_t* n_masks, const float* F_g, const float* F_masked, const float* F_crop) {
+    if (!h) return HMSG_ERR_INVALID;
+    return hmsg_boundary(h, [&] {
+        HMSG_REQUIRE(n_masks || n <= 0, HMSG_ERR_INVALID, "hmsg_add_frame_features_rle: n_masks is required");
+        const size_t HW = (size_t)h->cfg.height * h->cfg.width;
+        // (the F tables of a chunk are staged too: the same 512 MB bound as the dense call's)
+        const int max_fr = std::max(1, (int)std::min<size_t>(32768, ((size_t)512 << 20) / ((size_t)(2 * std::max(M, 1) + 1) * h->cfg.feat_dim * 4)));
+        hmsg_rle_handover r;
+        int next = 0;
+        add_frame_features(
+            h, "hmsg_add_frame_features_rle", first, n, M, run_off != nullptr, F_g, F_masked, F_crop, n_masks,
+            [&](const std::vector<int>& nm) { hmsg_rle_begin(r, h->cfg.height, h->cfg.width, n, nm.data(), counts, run_off, max_fr, h->stream, &h->prof); },
+            [&](int c0) { return r.chunk_first[(size_t)next + 1] - c0; },
+            [&](int c0, int, const int*) {
+                hmsg_rle_decode(r, next++, M, h->NW, h->bits.p + (size_t)(first + c0) * HW * h->NW, h->stream, &h->prof);
+            });
     });
 }
 

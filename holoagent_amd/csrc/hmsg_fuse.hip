@@ -906,11 +906,9 @@ void hmsg_fuse(hmsg_ctx* h) {
     h->feats_final = true;
 }
 
-// hand-over of the encoder outputs of frames [first, first+n): membership bitsets + F_p tables
-void hmsg_bitset_and_fp(hmsg_ctx* h, int first, int n, int M, const unsigned char* d_masks, const float* d_fg,
-                        const float* d_fm, const float* d_fc, const int* d_nmask) {
+// hand-over of the encoder outputs of frames [first, first+n): membership bitsets from dense masks ...
+void hmsg_bitset(hmsg_ctx* h, int first, int n, int M, const unsigned char* d_masks, const int* d_nmask) {
     const size_t HW = (size_t)h->cfg.height * h->cfg.width;
-    const int D = h->cfg.feat_dim;
     const size_t chunks = (HW + 15) / 16;
     {
         ProfScope ps(h->prof, h->stream, "k_bitset", (double)n * (double)HW * (M + 8.0 * h->NW));
@@ -918,6 +916,10 @@ void hmsg_bitset_and_fp(hmsg_ctx* h, int first, int n, int M, const unsigned cha
                            d_nmask, h->NW, h->bits.p + (size_t)first * HW * h->NW);
     }
     HMSG_CHECK_LAUNCH();
+}
+// ... and their F_p tables (whichever way the bitsets were made)
+void hmsg_fp_tables(hmsg_ctx* h, int first, int n, int M, const float* d_fg, const float* d_fm, const float* d_fc, const int* d_nmask) {
+    const int D = h->cfg.feat_dim;
     const float wm = (float)h->cfg.clip_masked_weight, wc = (float)(1.0 - h->cfg.clip_masked_weight);
     hipLaunchKernelGGL(k_fp, dim3(n), dim3(256), 0, h->stream, d_fg, d_fm, d_fc, M, D, wm, wc, d_nmask, h->MS,
                        h->fp.p + (size_t)first * h->MS * D);

@@ -137,3 +137,29 @@ def embed_frame_reference_inputs(L, enc, image, seg, bbox, torch, bbox_margin=50
     with torch.no_grad():
         f = torch.nn.functional.normalize(enc(x).float(), dim=-1)
     return f[:1].contiguous(), f[1:1 + M].contiguous(), f[1 + M:].contiguous()
+
+
+def handoff_frame_rle(L, scene, enc, frame, image, rles, bbox, torch, bbox_margin=50.0, crop_size=512, size=224, f16=True, mean=None,
+                      std=None):
+    """The hand-off of one frame whose masks SAM returned run-length coded (output_mode="uncompressed_rle"; holoagent_amd/rle.py):
+    hmsg_rle_to_masks expands the records ON THE DEVICE into the uint8 [M, H, W] the crop kernels read, hmsg_frame_encoder_inputs
+    makes the 1 + 2 M encoder inputs, the module runs once, and the frame goes to the scene by hmsg_add_frame_features_rle with the
+    same records -- no dense mask is built on the host or crosses to the device.  image u8 [H, W, 3]: a device tensor; rles =
+    (counts, run_off) of the frame's M masks as rle.pack makes them (numpy arrays: uploaded here, a few KB; or device tensors);
+    bbox: SAM's XYWH records, host, [M, 4].  Returns (f_g, f_masked, f_crop, seg): the features handed over and the device masks."""
+    from ._lib import rle_to_masks
+    H, W = image.shape[:2]
+    dev = image.device
+
+    def on_dev(a, np_dtype):
+        if hasattr(a, "data_ptr"):
+            return a.contiguous()
+        a = np.ascontiguousarray(a, dtype=np_dtype)
+        return torch.from_numpy(a.view(np.int32) if np_dtype is np.uint32 else a).to(dev)       # (uint32 travels as its bits)
+    counts, run_off = on_dev(rles[0], np.uint32), on_dev(rles[1], np.int64)
+    M = int(run_off.shape[0]) - 1
+    seg = rle_to_masks((counts, run_off), H, W, device_id=dev.index or 0, lib_=L)                # device in, device out
+    f_g, f_masked, f_crop = embed_frame_reference_inputs(L, enc, image, seg, bbox, torch, bbox_margin, crop_size, size, f16, mean, std)
+    n_masks = torch.tensor([M], dtype=torch.int32, device=dev)
+    scene.add_frame_features_rle(frame, (counts, run_off, n_masks), f_g, f_masked[None], f_crop[None])
+    return f_g, f_masked, f_crop, seg

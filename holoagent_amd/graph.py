@@ -30,6 +30,7 @@ from scipy.ndimage import gaussian_filter1d
 from scipy.signal import find_peaks
 from scipy.spatial import cKDTree
 
+from . import rle as _rle
 from ._lib import HmsgLib, NodeIndex, Scene, lib as _default_lib
 
 CLIP_DIM = {"ViT-B-32": 512, "ViT-L-14": 768, "ViT-H-14": 1024}     # utils/constants.py:3-7
@@ -642,18 +643,24 @@ class Graph:
                 outs.append(self.encoders.extract(np.asarray(rgb_i)))
             # SAM returns a different number of masks for every frame: rows are padded to the batch maximum and the
             # real counts are handed over with them (sam_clip_feats_extractor.py:167-169 softmaxes over the frame's own)
-            n_masks = np.array([np.asarray(o["masks"]).shape[0] for o in outs], np.int32)
+            rle_batch = all(_rle.is_rle_records(o["masks"]) for o in outs)
+            n_masks = np.array([len(o["masks"]) if rle_batch else np.asarray(o["masks"]).shape[0] for o in outs], np.int32)
             M = max(int(n_masks.max()), 1)
 
             def pad(a, tail):
                 out = np.zeros((M,) + tail, a.dtype)
                 out[: a.shape[0]] = a.reshape((a.shape[0],) + tail)
                 return out
-            masks = np.ascontiguousarray(np.stack([pad(np.asarray(o["masks"]).astype(np.uint8), (H, W)) for o in outs]))
             fg = np.ascontiguousarray(np.stack([np.asarray(o["f_g"], np.float32).reshape(-1) for o in outs]))
             fm = np.ascontiguousarray(np.stack([pad(np.asarray(o["f_masked"], np.float32), (D,)) for o in outs]))
             fc = np.ascontiguousarray(np.stack([pad(np.asarray(o["f_crop"], np.float32), (D,)) for o in outs]))
-            sc.add_frame_features(n_done, masks, fg, fm, fc, n_masks)
+            if rle_batch:
+                # SAM in output_mode="uncompressed_rle": the records go over as they are (hmsg_add_frame_features_rle), no
+                # [B][M][H][W] array is built -- at 720p and M = 100 that array is 2.9 GB per batch, the records a few MB
+                sc.add_frame_features_rle(n_done, [[_rle.from_sam(m, H, W) for m in o["masks"]] for o in outs], fg, fm, fc)
+            else:
+                masks = np.ascontiguousarray(np.stack([pad(np.asarray(o["masks"]).astype(np.uint8), (H, W)) for o in outs]))
+                sc.add_frame_features(n_done, masks, fg, fm, fc, n_masks)
             self._view_feats.extend(np.asarray(o["f_g"], np.float32).reshape(1, -1) for o in outs)
             n_done += len(outs)
         # the room level (floors, room regions, room clouds, camera -> room table on the device; KMeans views on a host thread)

@@ -143,6 +143,24 @@ int hmsg_get_map_points(const hmsg_t* h, double* xyz /*[V][3]*/, double* rgb /*[
  * and no 3-D mask.  Frames first_frame .. first_frame+n-1 must have been added. */
 int hmsg_add_frame_features(hmsg_t* h, int32_t first_frame, int32_t n, int32_t M, const uint8_t* masks,
                             const float* F_g, const float* F_masked, const float* F_crop, const int32_t* n_masks);
+/* The same hand-over with the masks as SAM's UNCOMPRESSED RUN-LENGTH records (SamAutomaticMaskGenerator with
+ * output_mode="uncompressed_rle": segment_anything/utils/amg.py mask_to_rle_pytorch; the generator keeps every mask in this form and
+ * only expands it to bool [H][W] for output_mode="binary_mask").  No dense mask is built on either side: the records are decoded on
+ * the device straight into the per-pixel membership bitsets every later stage reads.
+ * The format: one mask of an H x W image is a list of counts c_0 .. c_{k-1} (k >= 1) whose sum is exactly H * W.  The image is read
+ * in COLUMN-major order, position t = x * H + y; run r covers positions [S_r, S_r + c_r), S_r = c_0 + .. + c_{r-1}; even runs are
+ * zeros, odd runs are ones, so a mask that starts with a one has c_0 = 0.  A zero count anywhere is an empty run.  (COCO's
+ * compressed string form, output_mode="coco_rle", is not taken.)
+ * masks of frames [first_frame, first_frame + n) as uncompressed RLE (format above).  n_masks i32 [n] is required;
+ * T = sum n_masks; run_off i64 [T + 1] are offsets into counts (mask t of the hand-over, frames in order, masks of a
+ * frame in order, owns counts[run_off[t] .. run_off[t+1])); counts u32.  M = row stride of F_masked / F_crop, as in the
+ * dense call (n_masks[f] <= M <= cfg.max_masks).  Same state afterwards as hmsg_add_frame_features with the decoded masks.
+ * counts, run_off, n_masks and the F arrays may be host or device pointers.
+ * HMSG_ERR_INVALID, the handle unchanged (no bitset written, hmsg_last_error names the mask): run_off[0] != 0, run_off not
+ * non-decreasing, a mask without counts, a mask whose counts do not sum to H * W, n_masks[f] outside [0, M]. */
+int hmsg_add_frame_features_rle(hmsg_t* h, int32_t first_frame, int32_t n, int32_t M, const uint32_t* counts,
+                                const int64_t* run_off, const int32_t* n_masks, const float* F_g, const float* F_masked,
+                                const float* F_crop);
 /* masks SAM returned for a frame (= number of 3-D masks the frame contributes) */
 int32_t hmsg_get_frame_num_masks(const hmsg_t* h, int32_t frame);
 
@@ -479,6 +497,16 @@ int hmsg_clip_preprocess_batch(int32_t device_id, const hmsg_clip_preprocess* pr
 int hmsg_frame_encoder_inputs(int32_t device_id, const hmsg_clip_preprocess* prm, int32_t H, int32_t W, const uint8_t* image,
                               int32_t M, const uint8_t* segs, const double* bbox, double bbox_margin, int32_t crop_size,
                               void* out, double* device_ms);
+/* ---- one frame's run-length masks (the records of hmsg_add_frame_features_rle: run_off i64 [M + 1], counts u32; host or device)
+ * without a handle.  Both check the records like that call and return HMSG_ERR_INVALID before anything is written.
+ * handle-less: one frame's RLE masks -> membership bitsets u64 [H*W][NW], NW = ceil(max(M,1)/64), bit (i & 63) of word i >> 6
+ * of pixel p (row-major p = y*W + x) = mask i covers p.  out in host or device memory.  M <= 256. */
+int hmsg_rle_to_bitsets(int32_t device_id, int32_t H, int32_t W, int32_t M, const uint32_t* counts, const int64_t* run_off,
+                        uint64_t* out_bits);
+/* handle-less: the dense u8 [M][H][W] (0/1) masks on the device, for hmsg_crop_resize_batch / hmsg_frame_encoder_inputs,
+ * so a host that holds RLE never builds or uploads a dense mask.  out_masks in host or device memory. */
+int hmsg_rle_to_masks(int32_t device_id, int32_t H, int32_t W, int32_t M, const uint32_t* counts, const int64_t* run_off,
+                      uint8_t* out_masks);
 
 /* ---- A11: the other node records of save_hmsg_graph (graph.py:1801-1824) -- floors/<f>.{ply,json} (floor.py:37-52),
  * rooms/<f>_<r>.{ply,json} (room.py:309-337), views/<id>.json (view.py:56-74) -- from a C / C++ host, byte for byte what
