@@ -80,6 +80,11 @@ class HmsgClipPreprocess(C.Structure):   # include/hmsg.h: hmsg_clip_preprocess
     _fields_ = [("size", C.c_int32), ("out_f16", C.c_int32), ("mean", C.c_float * 3), ("std", C.c_float * 3)]
 
 
+class HmsgSamPostParams(C.Structure):   # include/hmsg.h: hmsg_sam_post_params
+    _fields_ = [("pred_iou_thresh", C.c_float), ("stability_score_thresh", C.c_float), ("stability_score_offset", C.c_float),
+                ("mask_threshold", C.c_float), ("box_nms_thresh", C.c_float), ("min_mask_region_area", C.c_int32)]
+
+
 class HmsgError(RuntimeError):
     pass
 
@@ -110,6 +115,9 @@ _SIGS = {
     "hmsg_add_frame_features_rle": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "hmsg_rle_to_bitsets": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     "hmsg_rle_to_masks": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    "hmsg_sam_post_default_params": (None, [_P]),
+    "hmsg_sam_postprocess": (C.c_int, [C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int64, C.POINTER(C.c_int32),
+                                       C.POINTER(C.c_int64), _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_double)]),
     "hmsg_get_frame_num_masks": (C.c_int32, [_P, C.c_int32]),
     "hmsg_fuse_frames": (C.c_int, [_P]),
     "hmsg_get_map_feats": (C.c_int, [_P, _P, _P]),
@@ -227,6 +235,7 @@ _SIGS = {
     "hmsg_test_overlap": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int64, _P, C.c_double, _P, _P, _P]),
     "hmsg_test_pool_rows": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_double, C.c_int32, _P]),
     "hmsg_test_graph_early_objects": (C.c_int, [_P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "hmsg_test_sam_post_last": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
@@ -1439,6 +1448,67 @@ def rle_to_masks(rles, H, W, device_id=0, lib_: "HmsgLib | None" = None):
     """One frame's run-length masks -> dense uint8 [M, H, W] (0 / 1) made on the device (include/hmsg.h: hmsg_rle_to_masks): with
     device tensors in, the dense masks the crop calls read never exist on the host.  rles as in rle_to_bitsets."""
     return _rle_one_frame("hmsg_rle_to_masks", rles, H, W, "masks", device_id, lib_)
+
+
+def sam_post_params(lib_: "HmsgLib | None" = None, **over):
+    """hmsg_sam_post_params with SAM's defaults (hmsg_sam_post_default_params), fields overridden by keyword"""
+    L = lib_ or lib()
+    p = HmsgSamPostParams()
+    L.c.hmsg_sam_post_default_params(C.byref(p))
+    for k, v in over.items():
+        if not hasattr(p, k):
+            raise HmsgError(f"unknown hmsg_sam_post_params field {k}")
+        setattr(p, k, int(v) if k == "min_mask_region_area" else float(v))
+    return p
+
+
+def sam_postprocess(logits, iou_preds, params=None, max_out=None, counts_cap=None, return_masks=True, device_id=0,
+                    lib_: "HmsgLib | None" = None, **over):
+    """SAM's mask post-processing on the device (include/hmsg.h: hmsg_sam_postprocess): logits float32 [N, H, W] (or [P, 3, H, W]) and
+    iou_preds float32 [N] (or [P, 3]) as predict_torch(..., return_logits=True) returns them -> a dict with n, keep_idx [n], counts,
+    run_off [n + 1] (the records of hmsg_add_frame_features_rle), bbox [n, 4] float64 XYWH, area [n], stability_score [n], masks
+    uint8 [n, H, W] (with return_masks), device_ms.  numpy arrays in: numpy arrays out; torch device tensors in: the outputs are
+    device tensors (counts as int32 with uint32's bits), no mask or record crosses to the host.  params: an HmsgSamPostParams, or
+    fields by keyword (pred_iou_thresh=..., min_mask_region_area=...).  max_out / counts_cap size the output arrays (default: min(N,
+    256) masks and two counts per mask and column); when the library asks for more the call is repeated once with what it asked for."""
+    L = lib_ or lib()
+    prm = params if params is not None else sam_post_params(L, **over)
+    on_dev = hasattr(logits, "data_ptr") and getattr(logits, "is_cuda", False)
+    if on_dev:
+        import torch
+        assert logits.dtype == torch.float32 and iou_preds.dtype == torch.float32 and iou_preds.device == logits.device
+        logits, iou_preds = logits.contiguous(), iou_preds.contiguous()
+        device_id = logits.device.index or 0
+    else:
+        logits, iou_preds = np.ascontiguousarray(logits, dtype=np.float32), np.ascontiguousarray(iou_preds, dtype=np.float32)
+    H, W = (int(v) for v in logits.shape[-2:])
+    N = int(np.prod(tuple(logits.shape[:-2]))) if len(logits.shape) > 2 else 1
+    assert int(np.prod(tuple(iou_preds.shape))) == N, "iou_preds: one value per logit image"
+    if N == 0 and on_dev:                                   # (an empty tensor has no address; the library wants one and reads nothing)
+        logits, iou_preds = logits.new_zeros(1), iou_preds.new_zeros(1)
+    cap_m = int(max_out) if max_out is not None else min(max(N, 1), 256)
+    cap_c = int(counts_cap) if counts_cap is not None else cap_m * (2 * W + 2) + 64
+    for attempt in range(2):
+        def buf(shape, np_dtype, t_dtype):
+            if on_dev:
+                return torch.empty(shape, dtype=getattr(torch, t_dtype), device=logits.device)
+            return np.empty(shape, np_dtype)
+        keep, counts, run_off = buf((cap_m,), np.int32, "int32"), buf((max(cap_c, 1),), np.uint32, "int32"), buf((cap_m + 1,), np.int64, "int64")
+        bbox, area, stab = buf((cap_m, 4), np.float64, "float64"), buf((cap_m,), np.int32, "int32"), buf((cap_m,), np.float32, "float32")
+        masks = buf((max(cap_m, 1), H, W), np.uint8, "uint8") if return_masks else None
+        n, nc, ms = C.c_int32(0), C.c_int64(0), C.c_double(0.0)
+        rc = L.c.hmsg_sam_postprocess(int(device_id), C.byref(prm), N, H, W, _ptr(logits), _ptr(iou_preds), cap_m, cap_c, C.byref(n),
+                                      C.byref(nc), _ptr(keep), _ptr(counts), _ptr(run_off), _ptr(bbox), _ptr(area), _ptr(stab), _ptr(masks),
+                                      C.byref(ms))
+        if rc == 0:
+            break
+        if attempt == 0 and rc == -1 and (n.value > cap_m or nc.value > cap_c):
+            cap_m, cap_c = max(cap_m, n.value), max(cap_c, nc.value)
+            continue
+        raise HmsgError(f"hmsg_sam_postprocess failed ({rc}) (the message is on stderr)")
+    k = n.value
+    return dict(n=k, keep_idx=keep[:k], counts=counts[:nc.value], run_off=run_off[:k + 1], bbox=bbox[:k], area=area[:k],
+                stability_score=stab[:k], masks=masks[:k] if return_masks else None, device_ms=ms.value, size=(H, W))
 
 
 def _clip_params(L, size, f16, mean, std):

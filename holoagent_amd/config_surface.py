@@ -39,6 +39,20 @@ MAIN = {"device", "use_gpt", "dataset", "scene_id", "dataset_path", "depth_cut",
         "pcd_path", "feats_path", "mask_path"}
 
 
+SAM_GENERATOR = "the mask generator's own (the prompt grid and its batching, in front of the decoder: outside this path)"
+# models.sam.<key> (graph.py:191-199 hands them to SamAutomaticMaskGenerator) -> (status, what happens here)
+SAM = {
+    "pred_iou_thresh": (HONOURED, "automatic_mask_generator.py _process_batch -> hmsg_sam_post_params.pred_iou_thresh"),
+    "stability_score_thresh": (HONOURED, "automatic_mask_generator.py _process_batch -> hmsg_sam_post_params.stability_score_thresh"),
+    "min_mask_region_area": (HONOURED, "automatic_mask_generator.py postprocess_small_regions -> hmsg_sam_post_params.min_mask_region_area"),
+    "crop_n_layers": (HONOURED, "0 only: hmsg_sam_postprocess has no crop-edge filter and no cross-crop NMS"),
+    "points_per_side": (SAM_GENERATOR, "build_all_layer_point_grids"),
+    "points_per_batch": (SAM_GENERATOR, "batch_iterator over the prompt grid"),
+    "checkpoint": (COLLABORATORS, "graph.py:189 sam_model_registry"),
+    "type": (COLLABORATORS, "graph.py:189 sam_model_registry"),
+}
+
+
 def _items(node):
     if node is None:
         return []
@@ -73,3 +87,36 @@ def check_config(cfg, strict=True):
         if k == "max_masks" and not 1 <= int(v) <= 256:
             raise ValueError("pipeline.max_masks = %r: 1 .. 256" % (v,))
     return report
+
+
+def _get(node, key):
+    if node is None:
+        return None
+    return node.get(key) if isinstance(node, dict) or hasattr(node, "get") else getattr(node, key, None)
+
+
+def sam_post_params(cfg, strict=True):
+    """The `models.sam` section of a reference config -> ({field of hmsg_sam_post_params: value}, {"models.sam.<key>": status}).
+    The dict goes to holoagent_amd._lib.sam_postprocess(**fields) as it is; fields the section does not set keep SAM's defaults.
+    Raises ValueError for crop_n_layers != 0, for a value outside its range and (strict) for a key this path does not know."""
+    sam = _get(_get(cfg, "models"), "sam")
+    fields, report = {}, {}
+    for k, v in _items(sam):
+        if k not in SAM:
+            if strict:
+                raise ValueError("models.sam.%s: unknown key (known: %s)" % (k, ", ".join(sorted(SAM))))
+            report["models.sam." + k] = "unknown"
+            continue
+        report["models.sam." + k] = SAM[k][0]
+        if k == "crop_n_layers" and int(v) != 0:
+            raise ValueError("models.sam.crop_n_layers = %r: only 0 (the crop-edge filter and the NMS across crops are out of scope of "
+                             "hmsg_sam_postprocess)" % (v,))
+        if k in ("pred_iou_thresh", "stability_score_thresh"):
+            if not float(v) == float(v) or abs(float(v)) == float("inf"):
+                raise ValueError("models.sam.%s = %r: must be finite" % (k, v))
+            fields[k] = float(v)
+        if k == "min_mask_region_area":
+            if int(v) < 0:
+                raise ValueError("models.sam.min_mask_region_area = %r: must be >= 0" % (v,))
+            fields[k] = int(v)
+    return fields, report

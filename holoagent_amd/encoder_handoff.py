@@ -163,3 +163,26 @@ def handoff_frame_rle(L, scene, enc, frame, image, rles, bbox, torch, bbox_margi
     n_masks = torch.tensor([M], dtype=torch.int32, device=dev)
     scene.add_frame_features_rle(frame, (counts, run_off, n_masks), f_g, f_masked[None], f_crop[None])
     return f_g, f_masked, f_crop, seg
+
+
+def handoff_frame_logits(L, scene, enc, frame, image, logits, iou_preds, torch, sam_params=None, bbox_margin=50.0, crop_size=512, size=224,
+                         f16=True, mean=None, std=None, **sam_over):
+    """The hand-off of one frame from SAM's mask DECODER on: logits float32 [N, H, W] (or [P, 3, H, W]) and iou_preds of
+    predict_torch(..., return_logits=True) as device tensors -> hmsg_sam_postprocess makes the run-length records, boxes and scores on
+    the device (everything SamAutomaticMaskGenerator.generate does behind the decoder; include/hmsg.h) -> hmsg_rle_to_masks ->
+    hmsg_frame_encoder_inputs -> the module -> hmsg_add_frame_features_rle with the device records.  No mask and no record crosses to
+    the host; the boxes do (a few dozen numbers, read by the host side of the crop call like the reference's mask["bbox"]).
+    sam_params: an HmsgSamPostParams, or its fields by keyword (config_surface.sam_post_params(cfg)[0]).
+    Returns (f_g, f_masked, f_crop, seg, post): the features handed over, the device masks and sam_postprocess' dict."""
+    from ._lib import rle_to_masks, sam_postprocess
+    assert logits.is_cuda and iou_preds.is_cuda and image.is_cuda, "logits, iou_preds, image: device tensors"
+    H, W = image.shape[:2]
+    dev = image.device
+    post = sam_postprocess(logits, iou_preds, params=sam_params, return_masks=False, lib_=L, **sam_over)
+    counts, run_off = post["counts"].contiguous(), post["run_off"].contiguous()
+    seg = rle_to_masks((counts, run_off), H, W, device_id=dev.index or 0, lib_=L)
+    bbox = post["bbox"].cpu().numpy()
+    f_g, f_masked, f_crop = embed_frame_reference_inputs(L, enc, image, seg, bbox, torch, bbox_margin, crop_size, size, f16, mean, std)
+    n_masks = torch.tensor([post["n"]], dtype=torch.int32, device=dev)
+    scene.add_frame_features_rle(frame, (counts, run_off, n_masks), f_g, f_masked[None], f_crop[None])
+    return f_g, f_masked, f_crop, seg, post

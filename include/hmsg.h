@@ -508,6 +508,67 @@ int hmsg_rle_to_bitsets(int32_t device_id, int32_t H, int32_t W, int32_t M, cons
 int hmsg_rle_to_masks(int32_t device_id, int32_t H, int32_t W, int32_t M, const uint32_t* counts, const int64_t* run_off,
                       uint8_t* out_masks);
 
+/* ---- SAM's mask post-processing: the decoder's logits of one frame -> those records, made on the device.  Everything
+ * SamAutomaticMaskGenerator.generate does behind predict_torch for crop_n_layers = 0 (segment_anything/
+ * automatic_mask_generator.py: _process_batch, postprocess_small_regions; the reference hands its models.sam.* keys to it in
+ * graph.py:191-199 and calls it in sam_clip_feats_extractor.py:117).  Handle-less; runs on a stream of its own.
+ * Every threshold is a float32 and compared in float32, as torch compares a float32 tensor with a Python number.
+ *   1. keep iou_preds[i] > pred_iou_thresh (skipped when the threshold is <= 0);
+ *   2. calculate_stability_score (utils/amg.py): I = #{logit > mask_threshold + offset}, U = #{logit > mask_threshold - offset},
+ *      both thresholds formed in float32, score = float32(I) / float32(U); keep score >= stability_score_thresh (U = 0: NaN,
+ *      dropped; skipped when the threshold is <= 0);
+ *   3. mask = logit > mask_threshold; batched_mask_to_box: XYXY = the inclusive extremes of the set pixels, [0, 0, 0, 0] for an
+ *      empty mask.  With one crop equal to the image is_box_near_crop_edge removes nothing: there is no such filter here;
+ *   4. torchvision.ops.nms on the float32 boxes with scores iou_preds: boxes visited by decreasing score, a visited box that is
+ *      not suppressed is kept and suppresses every later box with inter / (a_i + a_j - inter) > box_nms_thresh, a = (x2 - x1) *
+ *      (y2 - y1) without + 1, inter the product of the clamped overlaps, all float32, 0 / 0 = NaN suppresses nothing;
+ *   5. min_mask_region_area > 0 only -- postprocess_small_regions: every kept mask, in that order, through remove_small_regions
+ *      (utils/amg.py) in mode "holes" (8-connected components of the complement; every one of fewer than `area` pixels becomes
+ *      foreground, border components too) and then "islands" (8-connected components of the result; if one is smaller than
+ *      `area`, only those of at least `area` pixels stay, or the largest when there is none).  A mask in which neither mode
+ *      found a small component scores 1.0, else 0.0; boxes are re-made from the new masks; a second NMS with these scores
+ *      and box_nms_thresh; a kept mask of score 0.0 takes its new pixels and box;
+ *   6. out, in the order the last NMS left: counts / run_off = the records of hmsg_add_frame_features_rle (column-major, a leading
+ *      0 when pixel (0, 0) is set), area = the sum of the odd runs, bbox_xywh = box_xyxy_to_xywh = [x1, y1, x2 - x1, y2 - y1] (one
+ *      less than the pixel extent: what mask["bbox"] holds and hmsg_crop_resize_batch is given in the reference),
+ *      stability_score and keep_idx (the row of `logits`) of the original mask.
+ * This library's own definitions, where the published sources leave a point open or nothing installed here can pin it:
+ *   - among equal NMS scores the lower position goes first (a stable sort; torch's order among ties is unspecified, and the
+ *     second NMS is all ties);
+ *   - among equally large components in the "largest component" case the one whose first pixel comes first in row-major order
+ *     wins (scipy.ndimage.label's numbering; OpenCV's is believed to be the same, unverified);
+ *   - scalar thresholds are rounded to float32.
+ * Pointers other than n_out and n_counts may be host or device memory.  Errors come before anything is written to the caller's
+ * arrays: HMSG_ERR_INVALID for a null prm / logits / iou_preds / n_out / run_off / counts, N < 0, H or W < 1, max_out < 0, a
+ * non-finite parameter, a negative area; HMSG_ERR_UNSUPPORTED for H * W >= 2^24 (the float32 counts would stop being exact).
+ * N = 0 is HMSG_OK with n_out = 0 and run_off[0] = 0.  More than max_out surviving masks, or more than counts_cap counts:
+ * HMSG_ERR_INVALID, only n_out and n_counts are written and hold what is needed (the message, on stderr like every handle-less
+ * call's, names both): call again with larger arrays.  device_ms (optional): HIP-event time from the first launch to the last.
+ * Out of scope: crop_n_layers > 0 (the crop-edge filter, the cross-crop NMS), the decoder's own up-sampling of its 256 x 256
+ * logits, float16 logits, COCO's compressed strings, the unused filter_masks of utils/sam_utils.py. */
+typedef struct {
+    float   pred_iou_thresh;        /* 0.88 */
+    float   stability_score_thresh; /* 0.95 */
+    float   stability_score_offset; /* 1.0  */
+    float   mask_threshold;         /* 0.0  (Sam.mask_threshold) */
+    float   box_nms_thresh;         /* 0.7  */
+    int32_t min_mask_region_area;   /* 0 = off (SAM's default); 100 in every config of the reference */
+} hmsg_sam_post_params;
+void hmsg_sam_post_default_params(hmsg_sam_post_params* p);   /* the values above, area 0 */
+int hmsg_sam_postprocess(int32_t device_id, const hmsg_sam_post_params* prm,
+                         int32_t N, int32_t H, int32_t W,
+                         const float* logits,      /* f32 [N][H][W]: predict_torch(..., return_logits=True), flattened over (prompt, 3) */
+                         const float* iou_preds,   /* f32 [N] */
+                         int32_t max_out, int64_t counts_cap,
+                         int32_t* n_out,           /* host */
+                         int64_t* n_counts,        /* host: counts written (or needed, see errors) */
+                         int32_t* keep_idx,        /* i32 [max_out]: row of `logits` each output mask came from */
+                         uint32_t* counts, int64_t* run_off /* [max_out + 1] */,
+                         double* bbox_xywh,        /* f64 [max_out][4], what hmsg_crop_resize_batch takes as `bbox` */
+                         int32_t* area, float* stability_score,   /* [max_out] */
+                         uint8_t* out_masks,       /* optional u8 [max_out][H][W], 0/1 */
+                         double* device_ms);
+
 /* ---- A11: the other node records of save_hmsg_graph (graph.py:1801-1824) -- floors/<f>.{ply,json} (floor.py:37-52),
  * rooms/<f>_<r>.{ply,json} (room.py:309-337), views/<id>.json (view.py:56-74) -- from a C / C++ host, byte for byte what
  * json.dump writes: one JSON object per call, fields in the order given (the reference's key order).  A field is either RAW

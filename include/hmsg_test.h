@@ -110,6 +110,11 @@ int hmsg_test_overlap(hmsg_t* h, int32_t K, const int64_t* sizes, const int64_t*
  *   hmsg_pool_instances call is running. */
 int hmsg_test_graph_early_objects(const hmsg_graph_t* g, const hmsg_t* h, int32_t* state, int32_t* live_threads);
 
+/* measurement hook: of the calling thread's last hmsg_sam_postprocess the labelling rounds (one read-back of the batch's "changed"
+ * flags each) of the holes and of the islands pass (0: the pass did not run) and the HIP-event time of the statistics kernel's
+ * launch over the logits.  Any pointer may be NULL. */
+int hmsg_test_sam_post_last(int32_t* rounds_holes, int32_t* rounds_islands, double* stats_ms);
+
 #ifdef __cplusplus
 }
 #endif
