@@ -202,6 +202,10 @@ _SIGS = {
     "hmsg_comm_recv": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int32]),
     "hmsg_merge_tree_sharded": (C.c_int, [_P, _P, C.c_int32, C.POINTER(C.c_int32)]),
     "hmsg_merge_room_objects": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_double, C.c_double, C.POINTER(C.c_int32), _P, _P, C.c_int32]),
+    "hmsg_cloud_set_overlaps": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, _P, _P, C.c_int64, _P, C.c_double, _P]),
+    "hmsg_cloud_set_overlaps_kd": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, _P, _P, C.c_int64, _P, C.c_double, _P]),
+    "hmsg_eval_object_matrices": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, _P, _P, _P, _P, C.c_double, _P, _P, C.POINTER(C.c_int64)]),
+    "hmsg_lsap": (C.c_int, [C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, C.POINTER(C.c_int32)]),
     "hmsg_write_json": (C.c_int, [C.c_char_p, C.c_int32, _P]),
     "hmsg_write_ply": (C.c_int, [C.c_char_p, _P, C.c_int64]),
     "hmsg_read_json_numbers": (C.c_int, [C.c_char_p, C.c_char_p, _P, C.c_int64, C.POINTER(C.c_int64)]),
@@ -233,6 +237,7 @@ _SIGS = {
     "hmsg_test_boundary": (C.c_int, [C.c_int32, _P, C.c_int64]),
     "hmsg_test_group_pairs": (C.c_int, [C.c_int32, C.c_int64, _P, C.c_int32, _P, C.c_double, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "hmsg_test_overlap": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int64, _P, C.c_double, _P, _P, _P]),
+    "hmsg_test_pair_overlaps": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int64, _P, C.c_double, _P]),
     "hmsg_test_pool_rows": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_double, C.c_int32, _P]),
     "hmsg_test_graph_early_objects": (C.c_int, [_P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "hmsg_test_sam_post_last": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
@@ -297,6 +302,25 @@ def _ptr(a):
             torch.cuda.current_stream(a.device).synchronize()
         return C.c_void_p(a.data_ptr())
     raise TypeError(type(a))
+
+
+def lsap(cost, maximize=False, lib_=None):
+    """scipy.optimize.linear_sum_assignment(cost, maximize) restated in the library (include/hmsg.h: hmsg_lsap): the same
+    (row_ind, col_ind), index for index, also among equally good assignments.  cost: 2-D, numpy or a torch tensor (copied to the host)."""
+    L = lib_ or lib()
+    if hasattr(cost, "detach"):
+        cost = cost.detach().cpu().numpy()
+    cost = np.ascontiguousarray(cost, np.float64)
+    if cost.ndim != 2:
+        raise HmsgError("lsap: expected a matrix (found a %d-D array)" % cost.ndim)
+    nr, nc = cost.shape
+    n = min(nr, nc)
+    row, col = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+    got = C.c_int32(0)
+    rc = L.c.hmsg_lsap(nr, nc, _ptr(cost), int(bool(maximize)), _ptr(row), _ptr(col), C.byref(got))
+    if rc != 0:
+        raise HmsgError(f"hmsg_lsap failed ({rc}) (the message is on stderr)")
+    return row[:got.value].astype(np.int64), col[:got.value].astype(np.int64)
 
 
 class Comm:
@@ -659,6 +683,45 @@ class Scene:
         self._ck(self.L.c.hmsg_merge_room_objects(self.h, n, _ptr(pts), _ptr(off), _ptr(name_id), float(overlap_threshold), float(radius),
                                                   C.byref(ng), _ptr(goff), _ptr(mem), len(mem)))
         return [mem[goff[g]:goff[g + 1]].tolist() for g in range(ng.value)]
+
+    def cloud_set_overlaps(self, ptsA, offA, ptsB, offB, pairs, radius, kd=False):
+        """find_overlapping_ratio_faiss's two counts for pairs of clouds from two sets (include/hmsg.h: hmsg_cloud_set_overlaps; kd =
+        True: find_intersection_share's float64 comparison, hmsg_cloud_set_overlaps_kd).  pts* float64 [N, 3] and off* int64 [n + 1]
+        (CSR), pairs int32 [P, 2] = (a, b): numpy arrays or contiguous torch tensors of those dtypes, on the host or the device.
+        Returns uint32 [P, 2] (numpy): points of A[a] with a witness in B[b], points of B[b] with one in A[a]."""
+        def arg(a, dt):
+            if hasattr(a, "data_ptr"):
+                if str(a.dtype).split(".")[-1] != np.dtype(dt).name or not a.is_contiguous():
+                    raise HmsgError("cloud_set_overlaps: a torch tensor must be contiguous and of dtype %s" % np.dtype(dt).name)
+                return a
+            return np.ascontiguousarray(a, dt)
+        ptsA, ptsB = arg(ptsA, np.float64), arg(ptsB, np.float64)
+        offA, offB, pairs = arg(offA, np.int64), arg(offB, np.int64), arg(pairs, np.int32)
+        nA, nB = int(offA.shape[0]) - 1, int(offB.shape[0]) - 1
+        P = int(pairs.shape[0]) if len(pairs.shape) == 2 else int(pairs.shape[0]) // 2
+        counts = np.zeros((P, 2), np.uint32)
+        fn = self.L.c.hmsg_cloud_set_overlaps_kd if kd else self.L.c.hmsg_cloud_set_overlaps
+        self._ck(fn(self.h, nA, _ptr(ptsA), _ptr(offA), nB, _ptr(ptsB), _ptr(offB), P, _ptr(pairs), float(radius), _ptr(counts)))
+        return counts
+
+    def eval_object_matrices(self, pred_clouds, gt_clouds, gt_obb_center, gt_obb_dims, radius=0.02):
+        """The two association matrices of evaluate_objects (include/hmsg.h: hmsg_eval_object_matrices): lists of float64 [n, 3]
+        clouds, the ground-truth boxes [G, 3] each.  Returns (iou [P, G], overlap [P, G], number of pairs with iou > 0)."""
+        def csr(clouds):
+            off = np.zeros(len(clouds) + 1, np.int64)
+            off[1:] = np.cumsum([len(c) for c in clouds])
+            pts = np.concatenate([np.asarray(c, np.float64).reshape(-1, 3) for c in clouds] + [np.zeros((0, 3))])
+            return np.ascontiguousarray(pts), off
+        P, G = len(pred_clouds), len(gt_clouds)
+        pp, po = csr(pred_clouds)
+        gp, go = csr(gt_clouds)
+        gc = np.ascontiguousarray(gt_obb_center, np.float64).reshape(G, 3)
+        gd = np.ascontiguousarray(gt_obb_dims, np.float64).reshape(G, 3)
+        iou, ov = np.zeros((P, G)), np.zeros((P, G))
+        n = C.c_int64(0)
+        self._ck(self.L.c.hmsg_eval_object_matrices(self.h, P, _ptr(pp), _ptr(po), G, _ptr(gp), _ptr(go), _ptr(gc), _ptr(gd), float(radius),
+                                                    _ptr(iou), _ptr(ov), C.byref(n)))
+        return iou, ov, int(n.value)
 
     def room_clouds(self, y_lo, y_hi, T, z_levels, room_xz):
         """segment_hmsg_room's room clouds on the device (include/hmsg.h: hmsg_room_clouds): room_xz = list of [n, 2] arrays;

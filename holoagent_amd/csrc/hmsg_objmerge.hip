@@ -135,9 +135,10 @@ struct PySet {
 }  // namespace
 
 // overlap[p] = find_overlapping_ratio_faiss(cloud a[p], cloud b[p], radius) for n_pairs pairs of the clouds
-// pts[start[i] .. start[i] + count[i]) (points f64, host or device memory).
+// pts[start[i] .. start[i] + count[i]) (points f64, host or device memory).  counts_out (optional, host, [n_pairs][2]): the two
+// counts behind each ratio (hmsg_test_pair_overlaps, hmsg_eval.hip).
 void hmsg_pair_overlaps(hmsg_ctx* h, const double* points, const long long* start, const int* count, int n_pairs, const int* pa, const int* pb,
-                        double radius, double* overlap) {
+                        double radius, double* overlap, unsigned* counts_out = nullptr) {
     if (n_pairs <= 0) return;
     hipStream_t s = h->stream;
     std::vector<OmTask> tasks;
@@ -170,6 +171,7 @@ void hmsg_pair_overlaps(hmsg_ctx* h, const double* points, const long long* star
     std::vector<unsigned> hc(tasks.size());
     HIP_TRY(hipMemcpyAsync(hc.data(), dc.p, hc.size() * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
+    if (counts_out) std::copy(hc.begin(), hc.end(), counts_out);
     for (int p = 0; p < n_pairs; ++p) {
         // np.max([np.sum(D1 < r2) / n1, np.sum(D2 < r2) / n2]); an empty cloud: 0 (graph_utils.py:636-637)
         const int na = count[pa[p]], nb = count[pb[p]];

@@ -399,6 +399,48 @@ int hmsg_save_objects(hmsg_t* h, const char* dir, int64_t n, const hmsg_object_r
 int hmsg_merge_room_objects(hmsg_t* h, int32_t n, const double* points, const int64_t* off, const int32_t* name_id,
                             double overlap_threshold, double radius, int32_t* n_groups, int32_t* group_off, int32_t* group_members,
                             int32_t members_capacity);
+
+/* ---- evaluation against ground truth (memory/hmsg/eval/hm3dsem_evaluator.py): its overlap counting and its assignment.
+ * find_overlapping_ratio_faiss (utils/graph_utils.py:620-662) for pairs of clouds taken from two SETS, at any radius -- what
+ * evaluate_objects asks for every predicted / ground-truth object pair whose boxes intersect (radius 0.02) and evaluate_rooms for
+ * every pair of rooms (0.05).  Set A: nA clouds, cloud a = ptsA[offA[a] .. offA[a + 1]) (f64 [.][3]; offA i64 [nA + 1], starting
+ * at 0, non-decreasing); set B likewise (the same arrays may be given for both).  pairs i32 [n_pairs][2] = (a, b).
+ *   counts[p][0] = points of A[a] that have a point of B[b] with squared float32 distance < (float)(radius * radius),
+ *   counts[p][1] = points of B[b] that have such a point of A[a];
+ * the reference's ratio is max(counts[p][0] / n_a, counts[p][1] / n_b).  Points are cast to float32 as the reference casts them;
+ * duplicate points count individually; an empty cloud gives 0 / 0.  Both distance forms of hmsg_config::overlap_distance_form are
+ * honoured with the arithmetic stated there (in the BLAS form a cloud of 20 or more QUERY points is looked up in the expanded
+ * form, |p|^2 taken once per point).  No pair is tested exhaustively: both sets are sorted once by (cloud, cell) on a lattice whose
+ * cell side is the reach (widened in the BLAS form like the merge's grids), and a query point searches the 27 cells around its own
+ * in the other cloud's range.  The counts are integers added with integer atomics: two calls give the same answer.
+ * ptsA / ptsB / offA / offB / pairs / counts may be host or device memory.  n_pairs == 0: success, nothing is launched.
+ * HMSG_ERR_INVALID with counts untouched: offsets that do not start at 0 or decrease, a pair that names no cloud, a radius that
+ * is not positive.  (HMSG_ERR_INVALID after counts were zeroed: a coordinate that is not finite.) */
+int hmsg_cloud_set_overlaps(hmsg_t* h, int32_t nA, const double* ptsA, const int64_t* offA, int32_t nB, const double* ptsB,
+                            const int64_t* offB, int64_t n_pairs, const int32_t* pairs, double radius, uint32_t* counts);
+/* The same probe with find_intersection_share's comparison (utils/graph_utils.py:160-189: cKDTree.query(k = 1,
+ * distance_upper_bound = radius) on float64 points): a witness has float64 (dx*dx + dy*dy) + dz*dz < radius * radius, strict -- a
+ * point at exactly the radius does not count.  find_intersection_share(map = A[a], obj = B[b]) = counts[p][0] / n_b. */
+int hmsg_cloud_set_overlaps_kd(hmsg_t* h, int32_t nA, const double* ptsA, const int64_t* offA, int32_t nB, const double* ptsB,
+                               const int64_t* offB, int64_t n_pairs, const int32_t* pairs, double radius, uint32_t* counts);
+/* The two association matrices of evaluate_objects (hm3dsem_evaluator.py:429-458), P predicted objects (clouds, CSR) against G
+ * ground-truth objects (clouds, CSR, and obb_center / obb_dims f64 [G][3]): iou[p][g] = get_3d_iou(gt box, predicted box)
+ * (utils/eval_utils.py:169-200, float64), the predicted box being find_box_center_and_dims of the eight corners of the cloud's
+ * axis-aligned box in Open3D's corner order (the centre is their mean added in that order, the dims their ptp; an empty cloud has
+ * Open3D's box at the origin); overlap[p][g] = find_overlapping_ratio_faiss(pred, gt, radius) where iou > 0 -- through
+ * hmsg_cloud_set_overlaps, the reference calls it with 0.02 -- and 0 elsewhere.  iou / overlap f64 [P][G] (either may be NULL),
+ * *n_gated (optional) = pairs with iou > 0.  Arrays host or device memory.  P == 0 or G == 0: HMSG_ERR_INVALID (the reference's
+ * metrics divide by zero there).  What follows in the reference -- hmsg_lsap(P, G, matrix, 1, ...) and the thresholds -- is the
+ * caller's for now. */
+int hmsg_eval_object_matrices(hmsg_t* h, int32_t P, const double* pred_pts, const int64_t* pred_off, int32_t G, const double* gt_pts,
+                              const int64_t* gt_off, const double* gt_obb_center, const double* gt_obb_dims, double radius,
+                              double* iou, double* overlap, int64_t* n_gated);
+/* scipy.optimize.linear_sum_assignment(cost, maximize) restated on the host (csrc/hmsg_lsap_host.h; the solver of Crouse 2016):
+ * cost f64 [nr][nc] row-major; row_ind / col_ind i32 [min(nr, nc)], rows ascending; *n_assigned = min(nr, nc).  The answer is
+ * scipy's index for index, also among equally good assignments (the evaluator's matrices are mostly zeros, and its semantic
+ * metrics walk every assigned pair).  HMSG_ERR_INVALID (message on stderr): NaN or -inf costs, no feasible assignment. */
+int hmsg_lsap(int32_t nr, int32_t nc, const double* cost, int32_t maximize, int32_t* row_ind, int32_t* col_ind, int32_t* n_assigned);
+
 /* N2, load side: the object table of a saved graph straight into a retrieval index.  For every stem <dir>/<stem>.json is
  * read and its "embedding" array parsed as float64 (object.py:75-91 load; graph.py:1892-1987 load_hmsg_graph), rows in
  * the order given; room_of_node as for hmsg_index_create (declared below).  feat_dim (optional) receives the row length.

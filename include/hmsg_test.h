@@ -95,6 +95,13 @@ int hmsg_test_group_pairs(int32_t device_id, int64_t n, const double* boxes, int
 int hmsg_test_overlap(hmsg_t* h, int32_t K, const int64_t* sizes, const int64_t* n_base, const double* pts, int64_t P,
                       const int32_t* pairs, double decide_th, uint32_t* out_counts, uint8_t* out_state, double* out_ratio);
 
+/* test / measurement hook: the exhaustive overlap route of Room.merge_objects (hmsg_pair_overlaps, csrc/hmsg_objmerge.hip: every
+ * point of one cloud against every point of the other) on the clouds points[off[i] .. off[i + 1]) (f64, host or device memory; off
+ * i64 [n + 1] and pairs i32 [n_pairs][2] on the host): counts u32 [n_pairs][2] (host) as hmsg_cloud_set_overlaps defines them, with
+ * both clouds of a pair taken from the one set.  What hmsg_cloud_set_overlaps is compared with and timed against. */
+int hmsg_test_pair_overlaps(hmsg_t* h, int32_t n, const double* points, const int64_t* off, int64_t n_pairs, const int32_t* pairs,
+                            double radius, uint32_t* counts);
+
 /* test hook: what became of the object stage that hmsg_pool_instances runs beside itself for the graph begun on its scene
  * (hmsg_graph_begin registers the graph with the scene; HMSG_GRAPH_EARLY_OBJECTS=0 switches the stage off).
  *   g != NULL: the graph's own record; g == NULL: the record of the scene h, i.e. of the graph registered on it last (for a graph
