@@ -42,6 +42,7 @@ struct hmsg_error {
 
 // np.sum of a short float64 array as numpy adds it (pairwise_sum below its 128-element block: eight running sums over
 // the leading multiple of 8, combined as a tree, then the tail in order) -- kernel weights are normalised by such a sum
+// (hmsg_floors_host.h, which must stay free of HIP, keeps a copy as floors_host::np_sum: change both together)
 static inline double np_sum_f64(const double* a, size_t n) {
     if (n < 8) {
         double r = 0.0;          // (numpy starts from a[0]; adding it to 0.0 first is exact)

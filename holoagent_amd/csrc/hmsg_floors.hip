@@ -6,13 +6,19 @@
 // gaussian_filter1d on the int64 counts (:645; int64 in -> int64 out, truncated), np.percentile(.., 90), scipy's
 // find_peaks(distance = 0.2 / 0.01, height = that percentile) (:648-651), the 1-D DBSCAN(eps = 1, min_samples = 1)
 // chaining of the peak heights and the reference's pick / adjust rules (:680-741).  The Python mirror
-// (holoagent_amd/graph.py segment_floors_manually) calls numpy / scipy for the same steps; tests hold the two equal.
+// (holoagent_amd/graph.py segment_floors_manually) calls numpy / scipy for the same steps; tests hold the two equal.  The
+// host half lives in hmsg_floors_host.h (no HIP; driven alone by tests/host_cpp/floors_host.cpp).
 //
-// One documented freedom: find_peaks orders peaks of equal height with numpy's default argsort (introsort / AVX-512
-// network, not stable); here ties are ordered by position.  It matters only when two equally high peaks sit within
-// 20 bins of each other.
+// Two library-defined orders, because scipy and the reference sort with numpy's default argsort (introsort / AVX-512 network,
+// not stable: what it does with EQUAL values depends on the numpy build and the CPU) and smoothed counts are small integers:
+//   - find_peaks' distance rule: among peaks of equal height the one at the higher position goes first.  It matters when two
+//     equally high peaks sit within 20 bins of each other;
+//   - the pick of a chain's highest peak(s), np.argsort(smooth[pk])[-take:]: among equal heights the higher positions are kept.
+//     It matters whenever a chain has more peaks than it may keep and the last one kept has an equal among those dropped.
+// Both are a stable ascending sort of the heights read from its end; the mirror does the same (kind="stable").
 #include "hmsg_cloudops.h"
 #include "hmsg_boundary.h"
+#include "hmsg_floors_host.h"
 
 #include <cmath>
 
@@ -95,75 +101,6 @@ __global__ void __launch_bounds__(256) k_fl_crop(const double* __restrict__ pts,
     }
 }
 
-// scipy.ndimage.gaussian_filter1d(int64 counts, sigma): radius int(4 sigma + 0.5), weights exp(-x^2 / (2 sigma^2)) / sum,
-// correlate1d with mode "reflect" (d c b a | a b c d), symmetric taps paired, result truncated to int64
-std::vector<long long> gaussian_filter1d_i64(const std::vector<long long>& x, double sigma) {
-    const int n = (int)x.size(), r = (int)(4.0 * sigma + 0.5);
-    std::vector<double> w((size_t)(2 * r + 1));
-    for (int i = -r; i <= r; ++i) w[(size_t)(i + r)] = std::exp(-0.5 / (sigma * sigma) * (double)(i * i));
-    const double sum = np_sum_f64(w.data(), w.size());
-    for (auto& v : w) v /= sum;
-    auto at = [&](int i) {
-        if (n == 1) return (double)x[0];
-        while (i < 0 || i >= n) i = i < 0 ? -i - 1 : 2 * n - 1 - i;
-        return (double)x[(size_t)i];
-    };
-    std::vector<long long> out((size_t)n);
-    for (int i = 0; i < n; ++i) {
-        double acc = at(i) * w[(size_t)r];
-        for (int j = -r; j < 0; ++j) acc += (at(i + j) + at(i - j)) * w[(size_t)(j + r)];
-        out[(size_t)i] = (long long)acc;
-    }
-    return out;
-}
-
-// np.percentile(x, q) (method "linear")
-double percentile_linear(std::vector<long long> x, double q) {
-    std::sort(x.begin(), x.end());
-    const double quant = q / 100.0;
-    const double virt = (double)x.size() * quant + (1.0 + quant * (1.0 - 1.0 - 1.0)) - 1.0;     // numpy's _compute_virtual_index(alpha = beta = 1)
-    const double prev = std::floor(virt), gamma = virt - prev;
-    const size_t i0 = (size_t)prev, i1 = std::min(i0 + 1, x.size() - 1);
-    const double a = (double)x[i0], b = (double)x[i1], d = b - a;
-    return gamma >= 0.5 ? b - d * (1.0 - gamma) : a + d * gamma;
-}
-
-// scipy.signal.find_peaks(x, distance, height): local maxima (plateau midpoints), height filter, then the distance rule by
-// descending height
-std::vector<int> find_peaks(const std::vector<long long>& x, double height, int distance) {
-    const int n = (int)x.size();
-    std::vector<int> peaks;
-    for (int i = 1; i < n - 1; ++i) {
-        if (x[(size_t)i - 1] < x[(size_t)i]) {
-            int ahead = i + 1;
-            while (ahead < n - 1 && x[(size_t)ahead] == x[(size_t)i]) ++ahead;
-            if (x[(size_t)ahead] < x[(size_t)i]) {
-                peaks.push_back((i + ahead - 1) / 2);
-                i = ahead;
-            }
-        }
-    }
-    std::vector<int> kept;
-    for (int p : peaks)
-        if (height <= (double)x[(size_t)p]) kept.push_back(p);
-    peaks.swap(kept);
-    const int m = (int)peaks.size();
-    std::vector<int> order((size_t)m);
-    for (int i = 0; i < m; ++i) order[(size_t)i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return x[(size_t)peaks[(size_t)a]] < x[(size_t)peaks[(size_t)b]]; });
-    std::vector<char> keep((size_t)m, 1);
-    for (int i = m - 1; i >= 0; --i) {
-        const int j = order[(size_t)i];
-        if (!keep[(size_t)j]) continue;
-        for (int k = j - 1; k >= 0 && peaks[(size_t)j] - peaks[(size_t)k] < distance; --k) keep[(size_t)k] = 0;
-        for (int k = j + 1; k < m && peaks[(size_t)k] - peaks[(size_t)j] < distance; ++k) keep[(size_t)k] = 0;
-    }
-    std::vector<int> out;
-    for (int i = 0; i < m; ++i)
-        if (keep[(size_t)i]) out.push_back(peaks[(size_t)i]);
-    return out;
-}
-
 }  // namespace
 
 extern "C" int hmsg_segment_floors(hmsg_t* h, hmsg_floor* out, int32_t capacity, int32_t* n_floors) {
@@ -206,52 +143,9 @@ extern "C" int hmsg_segment_floors(hmsg_t* h, hmsg_floor* out, int32_t capacity,
         std::vector<unsigned long long> hh((size_t)bins);
         HIP_TRY(hipMemcpyAsync(hh.data(), hist.p, (size_t)bins * 8, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
-        std::vector<long long> counts(hh.begin(), hh.end());
-        const double step = (ymax - ymin) / (double)bins;
-        auto edge = [&](int j) { return j == bins ? ymax : (double)j * step + ymin; };
-        // ---- peaks (:645-651)
-        const std::vector<long long> smooth = gaussian_filter1d_i64(counts, 2.0);
-        const std::vector<int> peaks = find_peaks(smooth, percentile_linear(smooth, 90.0), (int)std::ceil(0.2 / 0.01));
-        const int np_ = (int)peaks.size();
-        std::vector<double> locs((size_t)np_);
-        for (int i = 0; i < np_; ++i) locs[(size_t)i] = edge(peaks[(size_t)i]);
-        // ---- DBSCAN(eps = 1, min_samples = 1) on the peak heights = chains of gaps <= 1; sklearn numbers clusters by first
-        // appearance (peaks come in ascending order, so that is the chain order) (:680-683)
-        std::vector<int> label((size_t)np_, 0);
-        for (int i = 1; i < np_; ++i) label[(size_t)i] = label[(size_t)i - 1] + (locs[(size_t)i] - locs[(size_t)i - 1] > 1.0 ? 1 : 0);
-        const int n_lab = np_ ? label[(size_t)np_ - 1] + 1 : 0;
-        // ---- per cluster the highest peak (first and last cluster) or the two highest (:690-713)
-        std::vector<double> clustered;
-        for (int c = 0; c < n_lab; ++c) {
-            std::vector<int> pk;
-            for (int i = 0; i < np_; ++i)
-                if (label[(size_t)i] == c) pk.push_back(peaks[(size_t)i]);
-            const int take = (c == 0 || c == n_lab - 1) ? 1 : 2;
-            // np.argsort(smooth[pk])[-take:]: ascending, stable for these short lists
-            std::vector<int> ord(pk.size());
-            for (size_t i = 0; i < pk.size(); ++i) ord[i] = (int)i;
-            std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return smooth[(size_t)pk[(size_t)a]] < smooth[(size_t)pk[(size_t)b]]; });
-            for (size_t i = pk.size() > (size_t)take ? pk.size() - (size_t)take : 0; i < pk.size(); ++i) clustered.push_back(edge(pk[(size_t)ord[i]]));
-        }
-        std::sort(clustered.begin(), clustered.end());
-        // ---- a 2.5 m gap between picks gets a ceiling 0.2 m under the upper one (:716-727)
-        std::vector<double> adj;
-        for (size_t i = 0; i + 1 < clustered.size(); ++i) {
-            adj.push_back(clustered[i]);
-            if (clustered[i + 1] - clustered[i] >= 2.5) adj.push_back(clustered[i + 1] - 0.2);
-        }
-        if (!clustered.empty()) adj.push_back(clustered.back());
-        std::vector<double> slabs;
-        for (size_t i = 0; i + 1 < adj.size(); ++i) {
-            slabs.push_back(adj[i]);
-            slabs.push_back(adj[i + 1]);
-        }
-        if (slabs.empty()) {
-            slabs.push_back(ymin);
-            slabs.push_back(ymax);
-        }
-        slabs[0] = (slabs[0] + ymin) / 2.0;          // (:735-741)
-        slabs[slabs.size() - 1] = ymax;
+        // ---- peaks, chains, picks, slabs (:645-741) on the host: hmsg_floors_host.h
+        const std::vector<long long> counts(hh.begin(), hh.end());
+        const std::vector<double> slabs = floors_host::counts_to_slabs(counts, ymin, ymax).slabs;
         const int NF = (int)slabs.size() / 2;
         *n_floors = NF;
         if (capacity == 0) return;

@@ -156,6 +156,30 @@ def _box_points(pts):
                      mn + [0, ex[1], ex[2]], mn + [ex[0], 0, ex[2]], mn + [ex[0], ex[1], 0]])
 
 
+def _select_peaks_by_distance(peaks, heights, distance):
+    """The distance rule of scipy.signal.find_peaks, from its documented behaviour: peaks are visited from the highest to the
+    lowest, and every peak still kept removes its neighbours closer than ceil(distance) samples.  scipy orders the heights with
+    numpy's default argsort, which defines no order among EQUAL heights (it is not stable, and differs between numpy builds and
+    CPUs); here the order is a stable ascending sort read from its end -- among equal heights the higher position goes first,
+    as hmsg_floors_host.h has it.  `peaks` ascending positions, `heights` their heights -> the peaks kept."""
+    peaks = np.asarray(peaks, np.int64)
+    dist = int(np.ceil(distance))
+    keep = np.ones(len(peaks), bool)
+    order = np.argsort(np.asarray(heights), kind="stable")
+    for j in order[::-1]:
+        if not keep[j]:
+            continue
+        k = j - 1
+        while k >= 0 and peaks[j] - peaks[k] < dist:
+            keep[k] = False
+            k -= 1
+        k = j + 1
+        while k < len(peaks) and peaks[k] - peaks[j] < dist:
+            keep[k] = False
+            k += 1
+    return peaks[keep]
+
+
 def find_overlapping_ratio_faiss(p1, p2, radius=0.02):
     """utils/graph_utils.py:620-664 (faiss IndexFlatL2, k=1): fraction of points whose exact float32 nearest
     neighbour in the other cloud is closer than radius (float32 `(dx*dx + dy*dy) + dz*dz < radius**2`), max over
@@ -743,7 +767,10 @@ class Graph:
         bins = int(np.abs(np.max(y) - np.min(y)) / 0.01)
         hist = np.histogram(y, bins=bins)
         smooth = gaussian_filter1d(hist[0], sigma=2)                       # int64 in, int64 out (hazard 17)
-        peaks, _ = find_peaks(smooth, distance=0.2 / 0.01, height=np.percentile(smooth, 90))
+        # (the distance rule and the cluster pick below order EQUAL heights by position -- the library's definition: scipy and the
+        #  reference use numpy's default argsort there, whose answer among equals depends on the numpy build and the CPU)
+        peaks, _ = find_peaks(smooth, height=np.percentile(smooth, 90))
+        peaks = _select_peaks_by_distance(peaks, smooth[peaks], 0.2 / 0.01)
         locs = hist[1][peaks]
         # DBSCAN(eps=1, min_samples=1) on 1-D peak heights = chains of gaps <= 1 (graph.py:680-683)
         order = np.argsort(locs)
@@ -765,7 +792,7 @@ class Graph:
         for i in range(n_lab):
             pk = peaks[labels == i]
             take = 1 if (i == 0 or i == n_lab - 1) else 2
-            top = pk[np.argsort(smooth[pk])[-take:]].tolist()
+            top = pk[np.argsort(smooth[pk], kind="stable")[-take:]].tolist()
             clustered.extend(hist[1][t] for t in top)
         clustered = np.sort(clustered)
         adjusted = []
