@@ -206,6 +206,16 @@ _SIGS = {
     "hmsg_cloud_set_overlaps_kd": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, _P, _P, C.c_int64, _P, C.c_double, _P]),
     "hmsg_eval_object_matrices": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, _P, _P, _P, _P, C.c_double, _P, _P, C.POINTER(C.c_int64)]),
     "hmsg_lsap": (C.c_int, [C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, C.POINTER(C.c_int32)]),
+    "hmsg_eval_rooms": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, _P, _P, C.c_double, C.c_double, _P, _P, _P,
+                                  C.POINTER(C.c_int64)]),
+    "hmsg_eval_semantic_ranks": (C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "hmsg_eval_floors": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P]),
+    "hmsg_eval_metrics_from_matrix": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "hmsg_eval_counts_at": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_double, _P]),
+    "hmsg_eval_hydra_means": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P]),
+    "hmsg_eval_top_k": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P]),
+    "hmsg_eval_default_params": (None, [_P]),
+    "hmsg_graph_evaluate": (C.c_int, [_P, _P, _P, _P, _P]),
     "hmsg_write_json": (C.c_int, [C.c_char_p, C.c_int32, _P]),
     "hmsg_write_ply": (C.c_int, [C.c_char_p, _P, C.c_int64]),
     "hmsg_read_json_numbers": (C.c_int, [C.c_char_p, C.c_char_p, _P, C.c_int64, C.POINTER(C.c_int64)]),
@@ -321,6 +331,109 @@ def lsap(cost, maximize=False, lib_=None):
     if rc != 0:
         raise HmsgError(f"hmsg_lsap failed ({rc}) (the message is on stderr)")
     return row[:got.value].astype(np.int64), col[:got.value].astype(np.int64)
+
+
+class EvalCounts(C.Structure):
+    """hmsg_eval_counts (include/hmsg.h)"""
+    _fields_ = [("tp", C.c_int64), ("tn", C.c_int64), ("fp", C.c_int64), ("fn", C.c_int64), ("acc", C.c_double), ("prec", C.c_double),
+                ("recall", C.c_double)]
+
+    def as_dict(self):
+        return dict(tp=int(self.tp), tn=int(self.tn), fp=int(self.fp), fn=int(self.fn), acc=float(self.acc), prec=float(self.prec),
+                    recall=float(self.recall))
+
+
+class EvalGt(C.Structure):
+    """hmsg_eval_gt (include/hmsg.h)"""
+    _fields_ = [("n_floors", C.c_int32), ("floor_lower", _P), ("floor_upper", _P),
+                ("n_rooms", C.c_int32), ("room_pts", _P), ("room_off", _P), ("room_min_h", _P), ("room_max_h", _P), ("room_mean_h", _P),
+                ("n_objects", C.c_int32), ("obj_pts", _P), ("obj_off", _P), ("obj_obb_center", _P), ("obj_obb_dims", _P), ("obj_name_id", _P),
+                ("n_classes", C.c_int32), ("feat_dim", C.c_int32), ("text_feats", _P), ("class_name_id", _P)]
+
+
+class EvalParams(C.Structure):
+    """hmsg_eval_params (include/hmsg.h)"""
+    _fields_ = [("eval_metric", C.c_int32), ("room_radius", C.c_double), ("object_radius", C.c_double), ("voxel", C.c_double),
+                ("n_top_k", C.c_int32), ("top_k", _P)]
+
+
+class EvalMetrics(C.Structure):
+    """hmsg_eval_metrics (include/hmsg.h)"""
+    _fields_ = [("floors", EvalCounts), ("room_acc50", C.c_double), ("room_ap", C.c_double), ("room_prec50", C.c_double),
+                ("room_recall50", C.c_double), ("room_gt", C.c_int32), ("room_pred", C.c_int32), ("room_hydra_prec", C.c_double),
+                ("room_hydra_recall", C.c_double), ("obj_ap", C.c_double), ("obj_gt", C.c_int32), ("obj_pred", C.c_int32),
+                ("obj_iou50", EvalCounts), ("obj_top_k_auc", C.c_double), ("obj_assigned", C.c_int32)]
+
+
+def _eval_ck(rc, what):
+    if rc != 0:
+        raise HmsgError(f"{what} failed ({rc}) (the message is on stderr)")
+
+
+def _pairs32(M, row, col):
+    M = np.ascontiguousarray(M, np.float64)
+    if M.ndim != 2:
+        raise HmsgError("expected a matrix (found a %d-D array)" % M.ndim)
+    row, col = np.ascontiguousarray(row, np.int32).reshape(-1), np.ascontiguousarray(col, np.int32).reshape(-1)
+    if len(row) != len(col):
+        raise HmsgError("row_ind and col_ind differ in length")
+    return M, row, col
+
+
+def eval_floors(gt_lower, gt_upper, pred_vertices, lib_=None):
+    """evaluate_floors' counts and ratios (include/hmsg.h: hmsg_eval_floors): gt bounds [Fg] each, predicted floor vertices
+    [Fp, 8, 3].  Raises HmsgError on unequal floor counts.  -> dict(tp, tn, fp, fn, acc, prec, recall)"""
+    L = lib_ or lib()
+    lo, up = np.ascontiguousarray(gt_lower, np.float64).reshape(-1), np.ascontiguousarray(gt_upper, np.float64).reshape(-1)
+    v = np.ascontiguousarray(pred_vertices, np.float64).reshape(-1, 8, 3)
+    if len(lo) != len(up):
+        raise HmsgError("eval_floors: lower and upper bounds differ in length")
+    out = EvalCounts()
+    _eval_ck(L.c.hmsg_eval_floors(_ptr(lo), _ptr(up), len(lo), _ptr(v), len(v), C.byref(out)), "hmsg_eval_floors")
+    return out.as_dict()
+
+
+def eval_metrics_from_matrix(M, row_ind, col_ind, which_index=6, lib_=None):
+    """The threshold sweep of a matrix under an assignment (include/hmsg.h: hmsg_eval_metrics_from_matrix)
+    -> (ap, acc, prec, recall) with the last three read at which_index (recall from the sorted list)."""
+    L = lib_ or lib()
+    M, row, col = _pairs32(M, row_ind, col_ind)
+    o = [C.c_double(0) for _ in range(4)]
+    _eval_ck(L.c.hmsg_eval_metrics_from_matrix(_ptr(M), M.shape[0], M.shape[1], _ptr(row), _ptr(col), len(row), int(which_index),
+                                               *[C.byref(v) for v in o]), "hmsg_eval_metrics_from_matrix")
+    return tuple(v.value for v in o)
+
+
+def eval_counts_at(M, row_ind, col_ind, threshold=0.5, lib_=None):
+    """TP / FP / FN and the three ratios at one threshold (include/hmsg.h: hmsg_eval_counts_at)"""
+    L = lib_ or lib()
+    M, row, col = _pairs32(M, row_ind, col_ind)
+    out = EvalCounts()
+    _eval_ck(L.c.hmsg_eval_counts_at(_ptr(M), M.shape[0], M.shape[1], _ptr(row), _ptr(col), len(row), float(threshold), C.byref(out)),
+             "hmsg_eval_counts_at")
+    return out.as_dict()
+
+
+def eval_hydra_means(over_pred, over_gt, lib_=None):
+    """(hydra_prec, hydra_recall) of the two room matrices (include/hmsg.h: hmsg_eval_hydra_means)"""
+    L = lib_ or lib()
+    a, b = np.ascontiguousarray(over_pred, np.float64), np.ascontiguousarray(over_gt, np.float64)
+    if a.ndim != 2 or a.shape != b.shape:
+        raise HmsgError("eval_hydra_means: two matrices of one shape expected")
+    hp, hr = C.c_double(0), C.c_double(0)
+    _eval_ck(L.c.hmsg_eval_hydra_means(_ptr(a), _ptr(b), a.shape[0], a.shape[1], C.byref(hp), C.byref(hr)), "hmsg_eval_hydra_means")
+    return hp.value, hr.value
+
+
+def eval_top_k(rank, n_classes, top_k, lib_=None):
+    """({k: accuracy}, top_k_auc) from the ranks of hmsg_eval_semantic_ranks (include/hmsg.h: hmsg_eval_top_k)"""
+    L = lib_ or lib()
+    rank = np.ascontiguousarray(rank, np.int32).reshape(-1)
+    ks = np.ascontiguousarray(list(top_k), np.int32).reshape(-1)
+    acc = np.zeros(max(len(ks), 1))
+    auc = C.c_double(0)
+    _eval_ck(L.c.hmsg_eval_top_k(_ptr(rank), len(rank), int(n_classes), _ptr(ks), len(ks), _ptr(acc), C.byref(auc)), "hmsg_eval_top_k")
+    return {int(k): float(a) for k, a in zip(ks, acc)}, auc.value
 
 
 class Comm:
@@ -723,6 +836,58 @@ class Scene:
                                                     _ptr(iou), _ptr(ov), C.byref(n)))
         return iou, ov, int(n.value)
 
+    @staticmethod
+    def _eval_arg(a, dt, who):
+        """numpy array or contiguous torch tensor (host or device) of dtype dt"""
+        if hasattr(a, "data_ptr"):
+            if str(a.dtype).split(".")[-1] != np.dtype(dt).name or not a.is_contiguous():
+                raise HmsgError("%s: a torch tensor must be contiguous and of dtype %s" % (who, np.dtype(dt).name))
+            return a
+        return np.ascontiguousarray(a, dt)
+
+    def eval_rooms(self, pred_pts, pred_off, pred_zero_level, pred_height, gt_pts, gt_off, gt_min_h, gt_max_h, gt_mean_h, floor_lower,
+                   floor_upper, voxel=0.05, radius=0.05):
+        """The three room matrices of evaluate_rooms (include/hmsg.h: hmsg_eval_rooms).  Clouds in CSR form (float64 [N, 3], int64
+        [n + 1]), the per-room and per-floor scalars float64: numpy arrays or contiguous torch tensors of those dtypes, on the host or
+        the device.  The predicted clouds are only read (the reference flattens them in place).
+        Returns (assoc, over_pred, over_gt) float64 [P, G] (numpy) and the number of gated cells."""
+        f = lambda a: self._eval_arg(a, np.float64, "eval_rooms")
+        i = lambda a: self._eval_arg(a, np.int64, "eval_rooms")
+        pp, po, zl, ht, gp, go = f(pred_pts), i(pred_off), f(pred_zero_level), f(pred_height), f(gt_pts), i(gt_off)
+        mn, mx, me, lo, up = f(gt_min_h), f(gt_max_h), f(gt_mean_h), f(floor_lower), f(floor_upper)
+        P, G, F = int(po.shape[0]) - 1, int(go.shape[0]) - 1, int(lo.shape[0])
+        for a, n, what in ((zl, P, "pred_zero_level"), (ht, P, "pred_height"), (mn, G, "gt_min_h"), (mx, G, "gt_max_h"), (me, G, "gt_mean_h"),
+                           (up, F, "floor_upper")):
+            if int(np.prod(tuple(a.shape))) != n:
+                raise HmsgError("eval_rooms: %s has %d entries, expected %d" % (what, int(np.prod(tuple(a.shape))), n))
+        out = [np.zeros((max(P, 0), max(G, 0))) for _ in range(3)]
+        n = C.c_int64(0)
+        self._ck(self.L.c.hmsg_eval_rooms(self.h, P, _ptr(pp), _ptr(po), _ptr(zl), _ptr(ht), G, _ptr(gp), _ptr(go), _ptr(mn), _ptr(mx), _ptr(me),
+                                          F, _ptr(lo), _ptr(up), float(voxel), float(radius), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), C.byref(n)))
+        return out[0], out[1], out[2], int(n.value)
+
+    def eval_semantic_ranks(self, emb, text, class_name_id, target_name_id):
+        """Rank of the ground-truth category among the classes by cosine similarity, per assigned pair (include/hmsg.h:
+        hmsg_eval_semantic_ranks).  emb [n, D] float32 or float64, text [C, D] float32, class_name_id int32 [C], target_name_id int32
+        [n] (-1: not in the vocabulary): numpy arrays or contiguous torch tensors, host or device.  Returns int32 [n] (numpy)."""
+        if hasattr(emb, "data_ptr"):
+            f64 = str(emb.dtype).split(".")[-1] == "float64"
+            emb = self._eval_arg(emb, np.float64 if f64 else np.float32, "eval_semantic_ranks")
+        else:
+            f64 = np.asarray(emb).dtype == np.float64
+            emb = np.ascontiguousarray(emb, np.float64 if f64 else np.float32)
+        text = self._eval_arg(text, np.float32, "eval_semantic_ranks")
+        cn = self._eval_arg(class_name_id, np.int32, "eval_semantic_ranks")
+        tg = self._eval_arg(target_name_id, np.int32, "eval_semantic_ranks")
+        if len(emb.shape) != 2 or len(text.shape) != 2 or emb.shape[1] != text.shape[1]:
+            raise HmsgError("eval_semantic_ranks: emb [n, D] and text [C, D] expected")
+        n, D, Cn = int(emb.shape[0]), int(emb.shape[1]), int(text.shape[0])
+        if int(cn.shape[0]) != Cn or int(tg.shape[0]) != n:
+            raise HmsgError("eval_semantic_ranks: class_name_id / target_name_id do not fit the tables")
+        rank = np.zeros(max(n, 1), np.int32)
+        self._ck(self.L.c.hmsg_eval_semantic_ranks(self.h, n, _ptr(emb), int(f64), D, Cn, _ptr(text), _ptr(cn), _ptr(tg), _ptr(rank)))
+        return rank[:n]
+
     def room_clouds(self, y_lo, y_hi, T, z_levels, room_xz):
         """segment_hmsg_room's room clouds on the device (include/hmsg.h: hmsg_room_clouds): room_xz = list of [n, 2] arrays;
         returns (per room the ascending indices into the floor cloud, size of the floor cloud)."""
@@ -1006,6 +1171,46 @@ class SceneGraph:
         buf = C.create_string_buffer(n.value)
         self._ck(self.L.c.hmsg_graph_to_json(self.g, buf, n.value, C.byref(n)))
         return json.loads(buf.value.decode())
+
+    def evaluate(self, gt, eval_metric="overlap", top_k=(), room_radius=0.05, object_radius=0.02, voxel=0.05):
+        """The reference's evaluate_floors / _rooms / _objects of this graph in one call (include/hmsg.h: hmsg_graph_evaluate).  gt: a
+        dict of arrays -- floor_lower, floor_upper; room_clouds (list of [n, 3]), room_min_h, room_max_h, room_mean_h; obj_clouds,
+        obj_obb_center, obj_obb_dims, obj_name_id; text_feats [C, D] float32, class_name_id.  Returns the reference's three
+        dictionaries' keys: dict(floors=..., rooms=..., objects=dict(instances, instances_iou50, ins_semantics))."""
+        def csr(clouds):
+            off = np.zeros(len(clouds) + 1, np.int64)
+            off[1:] = np.cumsum([len(c) for c in clouds])
+            pts = np.concatenate([np.asarray(c, np.float64).reshape(-1, 3) for c in clouds] + [np.zeros((0, 3))])
+            return np.ascontiguousarray(pts), off
+        f64 = lambda k: np.ascontiguousarray(gt[k], np.float64)
+        i32 = lambda k: np.ascontiguousarray(gt[k], np.int32)
+        rp, ro = csr(gt["room_clouds"])
+        op, oo = csr(gt["obj_clouds"])
+        text = np.ascontiguousarray(gt["text_feats"], np.float32)
+        keep = dict(lo=f64("floor_lower"), up=f64("floor_upper"), mn=f64("room_min_h"), mx=f64("room_max_h"), me=f64("room_mean_h"),
+                    oc=f64("obj_obb_center"), od=f64("obj_obb_dims"), on=i32("obj_name_id"), cn=i32("class_name_id"))
+        g = EvalGt(len(keep["lo"]), _ptr(keep["lo"]), _ptr(keep["up"]), len(ro) - 1, _ptr(rp), _ptr(ro), _ptr(keep["mn"]), _ptr(keep["mx"]),
+                   _ptr(keep["me"]), len(oo) - 1, _ptr(op), _ptr(oo), _ptr(keep["oc"]), _ptr(keep["od"]), _ptr(keep["on"]), text.shape[0],
+                   text.shape[1], _ptr(text), _ptr(keep["cn"]))
+        ks = np.ascontiguousarray(list(top_k), np.int32)
+        prm = EvalParams()
+        self.L.c.hmsg_eval_default_params(C.byref(prm))
+        prm.eval_metric = {"iou": 0, "overlap": 1}[eval_metric]
+        prm.room_radius, prm.object_radius, prm.voxel = float(room_radius), float(object_radius), float(voxel)
+        prm.n_top_k, prm.top_k = len(ks), _ptr(ks) if len(ks) else None
+        acc = np.zeros(max(len(ks), 1))
+        m = EvalMetrics()
+        self._ck(self.L.c.hmsg_graph_evaluate(self.g, C.byref(g), C.byref(prm), C.byref(m), _ptr(acc)))
+        fl = m.floors.as_dict()
+        i50 = m.obj_iou50.as_dict()
+        return dict(
+            floors=dict(tp=fl["tp"], tn=fl["tn"], fp=fl["fp"], fn=fl["fn"], acc=fl["acc"], prec=fl["prec"], recall=fl["recall"]),
+            rooms={"acc@IoU=0.5": m.room_acc50, "ap": m.room_ap, "prec@IoU=0.5": m.room_prec50, "recall@IoU=0.5": m.room_recall50,
+                   "gt": int(m.room_gt), "pred": int(m.room_pred), "hydra_prec": m.room_hydra_prec, "hydra_recall": m.room_hydra_recall},
+            objects=dict(instances=dict(ap=m.obj_ap, gt=int(m.obj_gt), pred=int(m.obj_pred)),
+                         instances_iou50=dict(acc=i50["acc"], prec=i50["prec"], recall=i50["recall"], tp=i50["tp"], fp=i50["fp"], fn=i50["fn"],
+                                              gt=int(m.obj_gt), pred=int(m.obj_pred)),
+                         ins_semantics=dict(tp_top_k_acc={int(k): float(a) for k, a in zip(ks, acc)}, top_k_auc=m.obj_top_k_auc)))
 
     def save(self, directory):
         self._ck(self.L.c.hmsg_save(self.g, str(directory).encode()))

@@ -1689,6 +1689,188 @@ int hmsg_load(const char* dir, int32_t device_id, hmsg_graph_t** out) {
 
 }  // extern "C"
 
+// ---- hmsg_graph_evaluate: evaluate_floors / _rooms / _objects (hm3dsem_evaluator.py:193-589) of a built or a loaded graph
+namespace {
+
+struct EvalScene {                          // a loaded graph has no scene handle: a small one for the call's device work
+    hmsg_t* h = nullptr;
+    ~EvalScene() {
+        if (h) hmsg_destroy(h);
+    }
+};
+
+void graph_evaluate(hmsg_graph* g, const hmsg_eval_gt* gt, const hmsg_eval_params* prm_in, hmsg_eval_metrics* out, double* top_k_acc) {
+    HMSG_REQUIRE(gt && out, HMSG_ERR_INVALID, "hmsg_graph_evaluate: null argument");
+    HMSG_REQUIRE(g->finished && !g->failed, HMSG_ERR_INVALID, "hmsg_graph_evaluate: the graph is not finished");
+    hmsg_eval_params prm;
+    hmsg_eval_default_params(&prm);
+    if (prm_in) prm = *prm_in;
+    HMSG_REQUIRE(prm.eval_metric == HMSG_EVAL_IOU || prm.eval_metric == HMSG_EVAL_OVERLAP, HMSG_ERR_INVALID, "hmsg_graph_evaluate: unknown eval_metric");
+    HMSG_REQUIRE(prm.n_top_k >= 0 && (prm.n_top_k == 0 || (prm.top_k && top_k_acc)), HMSG_ERR_INVALID, "hmsg_graph_evaluate: a top_k list without top_k_acc");
+    hmsg_eval_metrics m;
+    memset(&m, 0, sizeof m);
+    hmsg_ctx* h = g->h;
+    EvalScene own;
+    if (!h) {
+        hmsg_config cfg;
+        hmsg_default_config(&cfg);
+        cfg.device_id = g->device;
+        cfg.feat_dim = 16, cfg.height = cfg.width = 8, cfg.max_frames = 1, cfg.max_masks = 1;
+        if (hmsg_create(&cfg, &own.h) != HMSG_OK) throw hmsg_error{HMSG_ERR_INVALID, "hmsg_graph_evaluate: cannot make a scene handle on the graph's device"};
+        h = own.h;
+    }
+    const bool built = g->h != nullptr && !g->loaded;
+    // ---- floors
+    {
+        const size_t Fp = g->floors.size();
+        std::vector<double> verts(std::max<size_t>(Fp, 1) * 24, 0.0);
+        for (size_t f = 0; f < Fp; ++f) {
+            HMSG_REQUIRE(g->floors[f].have_verts, HMSG_ERR_INVALID, "hmsg_graph_evaluate: floor " + g->floors[f].id + " has no vertices");
+            memcpy(&verts[f * 24], g->floors[f].verts, sizeof(double) * 24);
+        }
+        HMSG_REQUIRE(gt->n_floors == (int32_t)Fp && Fp > 0, HMSG_ERR_INVALID,
+                     "hmsg_graph_evaluate: " + std::to_string(gt->n_floors) + " ground-truth floors against " + std::to_string(Fp) +
+                         " predicted (the reference raises there)");
+        if (hmsg_eval_floors(gt->floor_lower, gt->floor_upper, gt->n_floors, verts.data(), (int32_t)Fp, &m.floors) != HMSG_OK)
+            throw hmsg_error{HMSG_ERR_INVALID, "hmsg_graph_evaluate: hmsg_eval_floors refused its arguments"};
+    }
+    // ---- rooms: the clouds as hmsg_save fetches them (built: selections of a storey's slab of the map; loaded: as read)
+    {
+        const int32_t P = (int32_t)g->rooms.size(), G = gt->n_rooms;
+        HMSG_REQUIRE(P > 0 && G > 0, HMSG_ERR_INVALID, "hmsg_graph_evaluate: no predicted or no ground-truth rooms");
+        std::vector<std::vector<double>> cloud((size_t)P);
+        if (built) {
+            const int64_t V = hmsg_map_size(h);
+            std::vector<double> map((size_t)std::max<int64_t>(V, 1) * 3);
+            if (V) need(hmsg_get_map_points(h, map.data(), nullptr), h, "hmsg_get_map_points");
+            for (const GFloor& fl : g->floors) {
+                std::vector<double> slab;
+                for (int64_t i = 0; i < V; ++i) {
+                    const double y = map[(size_t)i * 3 + 1];
+                    if (y >= fl.f.y_lo && y <= fl.f.y_hi) slab.insert(slab.end(), &map[(size_t)i * 3], &map[(size_t)i * 3 + 3]);
+                }
+                for (int ri : fl.rooms) {
+                    const GRoom& rm = g->rooms[(size_t)ri];
+                    cloud[(size_t)ri].reserve(rm.sel.size() * 3);
+                    for (int s : rm.sel) cloud[(size_t)ri].insert(cloud[(size_t)ri].end(), &slab[(size_t)s * 3], &slab[(size_t)s * 3 + 3]);
+                }
+            }
+        }
+        std::vector<double> pts, zl((size_t)P), ht((size_t)P);
+        std::vector<int64_t> off((size_t)P + 1, 0);
+        for (int32_t p = 0; p < P; ++p) {
+            const GRoom& rm = g->rooms[(size_t)p];
+            const std::vector<double>& c = built ? cloud[(size_t)p] : rm.pts;
+            pts.insert(pts.end(), c.begin(), c.end());
+            off[(size_t)p + 1] = (int64_t)(pts.size() / 3);
+            zl[(size_t)p] = rm.zero, ht[(size_t)p] = rm.height;
+        }
+        const size_t PG = (size_t)P * (size_t)G;
+        std::vector<double> assoc(PG), over_pred(PG), over_gt(PG);
+        need(hmsg_eval_rooms(h, P, pts.data(), off.data(), zl.data(), ht.data(), G, gt->room_pts, gt->room_off, gt->room_min_h, gt->room_max_h,
+                             gt->room_mean_h, gt->n_floors, gt->floor_lower, gt->floor_upper, prm.voxel, prm.room_radius, assoc.data(),
+                             over_pred.data(), over_gt.data(), nullptr),
+             h, "hmsg_eval_rooms");
+        std::vector<int32_t> row((size_t)std::min(P, G)), col((size_t)std::min(P, G));
+        int32_t n = 0;
+        need(hmsg_eval_hydra_means(over_pred.data(), over_gt.data(), P, G, &m.room_hydra_prec, &m.room_hydra_recall), nullptr, "hmsg_eval_hydra_means");
+        need(hmsg_lsap(P, G, assoc.data(), 1, row.data(), col.data(), &n), nullptr, "hmsg_lsap");
+        need(hmsg_eval_metrics_from_matrix(assoc.data(), P, G, row.data(), col.data(), n, 6, &m.room_ap, &m.room_acc50, &m.room_prec50, &m.room_recall50),
+             nullptr, "hmsg_eval_metrics_from_matrix");
+        m.room_gt = G, m.room_pred = P;
+    }
+    // ---- objects
+    {
+        const int32_t P = (int32_t)g->objects.size(), G = gt->n_objects, C = gt->n_classes, D = g->D;
+        HMSG_REQUIRE(P > 0 && G > 0, HMSG_ERR_INVALID, "hmsg_graph_evaluate: no predicted or no ground-truth objects");
+        HMSG_REQUIRE(C > 0 && gt->feat_dim == D && gt->text_feats && gt->class_name_id && gt->obj_name_id, HMSG_ERR_INVALID,
+                     "hmsg_graph_evaluate: the class table is missing or its feat_dim (" + std::to_string(gt->feat_dim) + ") is not the graph's (" +
+                         std::to_string(D) + ")");
+        std::vector<double> pts, emb64;
+        std::vector<float> emb32;
+        std::vector<int64_t> off((size_t)P + 1, 0);
+        if (built) {
+            const int64_t N = hmsg_num_instances(h);
+            std::vector<double> ip((size_t)std::max<long long>(h->inst.total, 1) * 3);
+            std::vector<float> feats((size_t)std::max<int64_t>(N, 1) * (size_t)D);
+            need(hmsg_get_instance_points(h, ip.data()), h, "hmsg_get_instance_points");
+            need(hmsg_get_instance_feats(h, feats.data()), h, "hmsg_get_instance_feats");
+            emb32.resize((size_t)P * (size_t)D);
+            for (int32_t p = 0; p < P; ++p) {
+                const GObject& o = g->objects[(size_t)p];
+                const std::vector<int> one = {o.instance};
+                for (int inst : (o.parts.empty() ? one : o.parts)) {
+                    HMSG_REQUIRE(inst >= 0 && inst < N, HMSG_ERR_INVALID, "hmsg_graph_evaluate: object " + o.id + " names an instance the scene no longer has");
+                    pts.insert(pts.end(), ip.begin() + (ptrdiff_t)(h->inst.off[(size_t)inst] * 3), ip.begin() + (ptrdiff_t)(h->inst.off[(size_t)inst + 1] * 3));
+                }
+                off[(size_t)p + 1] = (int64_t)(pts.size() / 3);
+                if (o.parts.size() > 1 || !o.emb32.empty()) {
+                    HMSG_REQUIRE((int32_t)o.emb32.size() == D, HMSG_ERR_INVALID, "hmsg_graph_evaluate: object " + o.id + " has no embedding");
+                    memcpy(&emb32[(size_t)p * D], o.emb32.data(), (size_t)D * 4);
+                } else {
+                    memcpy(&emb32[(size_t)p * D], &feats[(size_t)o.instance * D], (size_t)D * 4);
+                }
+            }
+        } else {
+            emb64.resize((size_t)P * (size_t)D);
+            for (int32_t p = 0; p < P; ++p) {
+                const GObject& o = g->objects[(size_t)p];
+                pts.insert(pts.end(), o.pts.begin(), o.pts.end());
+                off[(size_t)p + 1] = (int64_t)(pts.size() / 3);
+                HMSG_REQUIRE((int32_t)o.emb.size() == D, HMSG_ERR_INVALID, "hmsg_graph_evaluate: object " + o.id + " has no embedding");
+                memcpy(&emb64[(size_t)p * D], o.emb.data(), (size_t)D * 8);
+            }
+        }
+        const size_t PG = (size_t)P * (size_t)G;
+        std::vector<double> iou(PG), ov(PG);
+        need(hmsg_eval_object_matrices(h, P, pts.data(), off.data(), G, gt->obj_pts, gt->obj_off, gt->obj_obb_center, gt->obj_obb_dims, prm.object_radius,
+                                       iou.data(), ov.data(), nullptr),
+             h, "hmsg_eval_object_matrices");
+        std::vector<int32_t> row((size_t)std::min(P, G)), col((size_t)std::min(P, G));
+        int32_t n = 0;
+        need(hmsg_lsap(P, G, prm.eval_metric == HMSG_EVAL_IOU ? iou.data() : ov.data(), 1, row.data(), col.data(), &n), nullptr, "hmsg_lsap");
+        // the sweep and the recount at 0.5 read the OVERLAP matrix under either assignment (:473, :499)
+        need(hmsg_eval_metrics_from_matrix(ov.data(), P, G, row.data(), col.data(), n, 6, &m.obj_ap, nullptr, nullptr, nullptr), nullptr,
+             "hmsg_eval_metrics_from_matrix");
+        need(hmsg_eval_counts_at(ov.data(), P, G, row.data(), col.data(), n, 0.5, &m.obj_iou50), nullptr, "hmsg_eval_counts_at");
+        m.obj_gt = G, m.obj_pred = P, m.obj_assigned = n;
+        // top-k semantics of EVERY assigned pair (:567)
+        std::vector<int32_t> target((size_t)n), rank((size_t)n);
+        const size_t rb = built ? 4 : 8;
+        std::vector<unsigned char> sel((size_t)n * (size_t)D * rb);
+        const unsigned char* src = built ? (const unsigned char*)emb32.data() : (const unsigned char*)emb64.data();
+        for (int32_t k = 0; k < n; ++k) {
+            target[(size_t)k] = gt->obj_name_id[col[(size_t)k]];
+            memcpy(&sel[(size_t)k * D * rb], src + (size_t)row[(size_t)k] * D * rb, (size_t)D * rb);
+        }
+        need(hmsg_eval_semantic_ranks(h, n, sel.data(), built ? 0 : 1, D, C, gt->text_feats, gt->class_name_id, target.data(), rank.data()), h,
+             "hmsg_eval_semantic_ranks");
+        need(hmsg_eval_top_k(rank.data(), n, C, prm.top_k, prm.n_top_k, top_k_acc, &m.obj_top_k_auc), nullptr, "hmsg_eval_top_k");
+    }
+    *out = m;
+}
+
+}  // namespace
+
+extern "C" {
+
+void hmsg_eval_default_params(hmsg_eval_params* p) {
+    if (!p) return;
+    p->eval_metric = HMSG_EVAL_OVERLAP;
+    p->room_radius = 0.05;
+    p->object_radius = 0.02;
+    p->voxel = 0.05;
+    p->n_top_k = 0;
+    p->top_k = nullptr;
+}
+
+int hmsg_graph_evaluate(hmsg_graph_t* g, const hmsg_eval_gt* gt, const hmsg_eval_params* prm, hmsg_eval_metrics* out, double* top_k_acc) {
+    if (!g) return HMSG_ERR_INVALID;
+    return hmsg_boundary(&g->err, -1, [&] { graph_evaluate(g, gt, prm, out, top_k_acc); });
+}
+
+}  // extern "C"
+
 namespace {
 // hmsg_graph_index; rooms_only: the levels above the nodes into an index without a node table (a graph without objects)
 void graph_make_index(hmsg_graph* g, const double* room_name_emb, bool rooms_only, hmsg_index_t** out) {

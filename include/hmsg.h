@@ -441,6 +441,72 @@ int hmsg_eval_object_matrices(hmsg_t* h, int32_t P, const double* pred_pts, cons
  * metrics walk every assigned pair).  HMSG_ERR_INVALID (message on stderr): NaN or -inf costs, no feasible assignment. */
 int hmsg_lsap(int32_t nr, int32_t nc, const double* cost, int32_t maximize, int32_t* row_ind, int32_t* col_ind, int32_t* n_assigned);
 
+/* The three room matrices of evaluate_rooms (hm3dsem_evaluator.py:265-341), f64 [P][G], any of which may be NULL:
+ *   assoc[p][g]     = find_overlapping_ratio_faiss(pred_bev, gt_bev, radius)               (first loop nest)
+ *   over_pred[p][g] = min(find_intersection_share(gt_bev, pred_bev, radius), 1)           (second loop nest)
+ *   over_gt[p][g]   = min(find_intersection_share(pred_bev, gt_bev, radius), 1)
+ * for the pairs behind the reference's gate, 0 elsewhere: for each ground-truth floor f in order, each ground-truth room g with
+ * floor_lower[f] < gt_mean_h[g] < floor_upper[f], each predicted room p with gt_min_h[g] < pred_zero_level[p] + pred_height[p] / 2 <
+ * gt_max_h[g] (all strict).  P predicted rooms: clouds in CSR form (pred_pts f64 [.][3], pred_off i64 [P + 1]); G ground-truth rooms:
+ * bev clouds in CSR form; F ground-truth floors.  voxel / radius: the reference uses 0.05 / 0.05.  *n_gated (optional): cells
+ * behind the gate.  Arrays host or device memory.
+ * pred_bev is the predicted cloud with every y set to gt_min_h[g], then voxel_down_sample(voxel) (Open3D semantics, voxels in
+ * ascending order).  Restated with the reference's quirks:
+ *   - gt_room.bev_pcd is REPLACED by its own down-sample at every visit, in both nests, and down-sampling is not idempotent: the
+ *     j-th visit of room g in the first nest sees vds^j(gt_g), the j-th in the second vds^(n_g + j)(gt_g), n_g = g's visits in the
+ *     first nest.  A room whose mean height lies inside two floors is visited under both; the later visit overwrites the cell.
+ *     (The sequence reaches a bitwise fixed point after a few rounds; versions are computed until then.)
+ *   - the flattened y of a voxel of k points is (h + h + ... + h) / k added sequentially in float64, which is not h for most k;
+ *     it enters both distances.
+ *   - the reference writes the flattened y into the predicted graph's room cloud in place.  THIS CALL DOES NOT: pred_pts is
+ *     only read.
+ * HMSG_ERR_INVALID with the outputs untouched: P == 0 or G == 0, offsets that do not start at 0 or decrease, voxel or radius not
+ * positive, a coordinate that is not finite.  An empty predicted (or ground-truth) cloud gives 0 in all three matrices.
+ * HMSG_DEBUG_EVAL_ROOMS_PER_PAIR=1 (development) down-samples the whole flattened cloud for every pair instead of grouping every
+ * predicted room once; same bits. */
+int hmsg_eval_rooms(hmsg_t* h, int32_t P, const double* pred_pts, const int64_t* pred_off, const double* pred_zero_level,
+                    const double* pred_height, int32_t G, const double* gt_pts, const int64_t* gt_off, const double* gt_min_h,
+                    const double* gt_max_h, const double* gt_mean_h, int32_t F, const double* floor_lower, const double* floor_upper,
+                    double voxel, double radius, double* assoc, double* over_pred, double* over_gt, int64_t* n_gated);
+
+/* The ranks behind object_semantics_eval_tp_auc (hm3dsem_evaluator.py:557-589).  n assigned pairs: emb [n][D] (f32, or f64 with
+ * emb_is_f64 != 0: cast to f32 first, the reference's `.float()`), the class table text [C][D] f32, class_name_id i32 [C] (equal
+ * NAMES share an id: the reference compares names, not indices), target_name_id i32 [n] (the ground-truth object's category; -1:
+ * not in the vocabulary).  Every row is normalised in float32 as torchmetrics' pairwise_cosine_similarity does (x / ||x||); s_c is
+ * the float32 dot product of the normalised rows, summed in the kernel's own order, which does not depend on c: rows of the same
+ * bits give the same similarity.  rank_t = classes c with s_c > s_t, or s_c == s_t and c > t (a stable ascending argsort read from
+ * its end); rank[i] = min of rank_t over the classes t with the target's name id, C if there is none.  "Category among the k most
+ * similar classes" is rank[i] < k.  A row of norm zero (embedding or class) gives NaN similarities, ordered as numpy sorts them:
+ * above every number, equal among themselves -- a zero embedding ranks the classes from the table's end.
+ * Arrays host or device memory.  D <= 8192.  n == 0: success, nothing is launched. */
+int hmsg_eval_semantic_ranks(hmsg_t* h, int32_t n, const void* emb, int32_t emb_is_f64, int32_t D, int32_t C, const float* text,
+                             const int32_t* class_name_id, const int32_t* target_name_id, int32_t* rank);
+
+/* The evaluator's numbers in float64, in the reference's operation order (csrc/hmsg_eval_metrics_host.h; host arrays; a failed
+ * call's message goes to stderr). */
+typedef struct hmsg_eval_counts {
+    int64_t tp, tn, fp, fn;            /* tn is 0 throughout the reference */
+    double acc, prec, recall;
+} hmsg_eval_counts;
+/* evaluate_floors (:193-263): gt_lower / gt_upper [Fg]; pred_vertices [Fp][8][3], the bounds of a predicted floor are c_y -/+ d_y / 2
+ * of find_box_center_and_dims.  Both bound lists are flattened and sorted, inner neighbours averaged pairwise; tp = positions with
+ * |gt - pred| < 0.5.  HMSG_ERR_INVALID: no floors on a side, unequal counts (numpy raises in the reference). */
+int hmsg_eval_floors(const double* gt_lower, const double* gt_upper, int32_t Fg, const double* pred_vertices, int32_t Fp,
+                     hmsg_eval_counts* out);
+/* The threshold sweep (:364-383, :467-484) of matrix M [P][G] under the assignment (row_ind, col_ind)[n]: for t in
+ * np.linspace(0, 1, 11), TP = sum(M[row, col] > t), FP = P - TP, FN = G - TP; the recalls -- ONLY they -- are sorted; *ap =
+ * np.trapz(precisions, sorted recalls); *acc / *prec / *recall = entry which_index of the three lists (the room dictionary reads
+ * index 6; recall from the SORTED list).  Any output may be NULL. */
+int hmsg_eval_metrics_from_matrix(const double* M, int32_t P, int32_t G, const int32_t* row_ind, const int32_t* col_ind, int32_t n,
+                                  int32_t which_index, double* ap, double* acc, double* prec, double* recall);
+/* the recount at one threshold (:497-506, instances_iou50 uses 0.5) */
+int hmsg_eval_counts_at(const double* M, int32_t P, int32_t G, const int32_t* row_ind, const int32_t* col_ind, int32_t n, double threshold,
+                        hmsg_eval_counts* out);
+/* :343-356: mean over predicted rooms of over_pred's row maxima, mean over ground-truth rooms of over_gt's column maxima */
+int hmsg_eval_hydra_means(const double* over_pred, const double* over_gt, int32_t P, int32_t G, double* hydra_prec, double* hydra_recall);
+/* :585-588 from the ranks: top_k_acc[i] = (pairs with rank < top_k[i]) / n; *top_k_auc = np.trapz(accuracy at k in range(0, C, 10), k / C) */
+int hmsg_eval_top_k(const int32_t* rank, int32_t n, int32_t C, const int32_t* top_k, int32_t n_top_k, double* top_k_acc, double* top_k_auc);
+
 /* N2, load side: the object table of a saved graph straight into a retrieval index.  For every stem <dir>/<stem>.json is
  * read and its "embedding" array parsed as float64 (object.py:75-91 load; graph.py:1892-1987 load_hmsg_graph), rows in
  * the order given; room_of_node as for hmsg_index_create (declared below).  feat_dim (optional) receives the row length.
@@ -775,6 +841,60 @@ int hmsg_graph_to_json(const hmsg_graph_t* g, char* buf, int64_t capacity, int64
 int hmsg_save(hmsg_graph_t* g, const char* dir);
 int hmsg_load(const char* dir, int32_t device_id, hmsg_graph_t** out);
 int hmsg_graph_index(hmsg_graph_t* g, const double* room_name_emb, hmsg_index_t** out);
+
+/* ---- a graph against ground truth: the reference's evaluate_floors, evaluate_rooms and evaluate_objects
+ * (memory/hmsg/eval/hm3dsem_evaluator.py:193-589) in one call.  Ground truth as plain arrays (the small ones in host memory; the point
+ * arrays host or device):
+ *   floors   floor_lower / floor_upper f64 [n_floors];
+ *   rooms    bev clouds in CSR form (room_pts f64 [.][3], room_off i64 [n_rooms + 1]), room_min_h / room_max_h / room_mean_h f64;
+ *   objects  clouds in CSR form, obb_center / obb_dims f64 [n_objects][3], obj_name_id i32 [n_objects]: the category as an id of
+ *            the class table's names, -1 when the category is not in the vocabulary;
+ *   classes  text_feats f32 [n_classes][feat_dim], class_name_id i32 [n_classes]: equal NAMES share an id. */
+typedef struct hmsg_eval_gt {
+    int32_t n_floors;
+    const double *floor_lower, *floor_upper;
+    int32_t n_rooms;
+    const double* room_pts;
+    const int64_t* room_off;
+    const double *room_min_h, *room_max_h, *room_mean_h;
+    int32_t n_objects;
+    const double* obj_pts;
+    const int64_t* obj_off;
+    const double *obj_obb_center, *obj_obb_dims;
+    const int32_t* obj_name_id;
+    int32_t n_classes, feat_dim;
+    const float* text_feats;
+    const int32_t* class_name_id;
+} hmsg_eval_gt;
+enum { HMSG_EVAL_IOU = 0, HMSG_EVAL_OVERLAP = 1 };
+typedef struct hmsg_eval_params {
+    int32_t eval_metric;          /* HMSG_EVAL_*: which matrix the objects are assigned on (:460-465); the sweep is on the overlaps either way */
+    double room_radius;           /* 0.05 */
+    double object_radius;         /* 0.02 */
+    double voxel;                 /* 0.05: the rooms' bev down-sampling */
+    int32_t n_top_k;
+    const int32_t* top_k;         /* params.eval.hm3dsem.top_k_object_semantic_eval */
+} hmsg_eval_params;
+void hmsg_eval_default_params(hmsg_eval_params* p);      /* overlap, 0.05, 0.02, 0.05, no top_k list */
+/* every key of the reference's three dictionaries */
+typedef struct hmsg_eval_metrics {
+    hmsg_eval_counts floors;                              /* metrics["floors"]: tp tn fp fn acc prec recall */
+    double room_acc50, room_ap, room_prec50, room_recall50;   /* metrics["rooms"]: "acc@IoU=0.5", "ap", "prec@IoU=0.5", "recall@IoU=0.5" */
+    int32_t room_gt, room_pred;
+    double room_hydra_prec, room_hydra_recall;
+    double obj_ap;                                        /* metrics["objects"]["instances"]: ap, gt, pred */
+    int32_t obj_gt, obj_pred;
+    hmsg_eval_counts obj_iou50;                           /* ["instances_iou50"]: acc prec recall tp fp fn (gt, pred as above) */
+    double obj_top_k_auc;                                 /* ["ins_semantics"]["top_k_auc"]; "tp_top_k_acc" goes to the top_k_acc array */
+    int32_t obj_assigned;                                 /* len(col_ind) */
+} hmsg_eval_metrics;
+/* Works on a built graph (room clouds from the storeys' slabs of the map, objects from the scene's instances and pooled features --
+ * what hmsg_save writes) and on a loaded one (the clouds and float64 embeddings hmsg_load read; the device work runs on a small
+ * scene handle of the call's own).  Composes hmsg_eval_floors, hmsg_eval_rooms, hmsg_eval_object_matrices, hmsg_lsap,
+ * hmsg_eval_semantic_ranks and the metrics of csrc/hmsg_eval_metrics_host.h.  top_k_acc f64 [n_top_k] (may be NULL when n_top_k is
+ * 0); prm NULL: the defaults.  HMSG_ERR_INVALID (text in hmsg_graph_last_error): unequal floor counts, no rooms or no objects on
+ * a side, feat_dim that is not the graph's, an object without an embedding. */
+int hmsg_graph_evaluate(hmsg_graph_t* g, const hmsg_eval_gt* gt, const hmsg_eval_params* prm, hmsg_eval_metrics* out, double* top_k_acc);
 int hmsg_graph_query(hmsg_graph_t* g, const double* room_name_emb, int32_t Q, int32_t C, const float* T_obj, const int32_t* qid,
                      const float* T_room, const int32_t* floor_id, const int32_t* room_mode, int32_t k, int32_t use_negatives,
                      int32_t max_rooms, int32_t* out_sel, int32_t* out_nsel, int32_t* out_idx, int32_t* out_room, double* out_score);
