@@ -214,6 +214,11 @@ _SIGS = {
     "hmsg_eval_counts_at": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_double, _P]),
     "hmsg_eval_hydra_means": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P]),
     "hmsg_eval_top_k": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P]),
+    "hmsg_semseg_instance_labels": (C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    "hmsg_knn_labels": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int32, _P, _P]),
+    "hmsg_semseg_confusion": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int32, _P]),
+    "hmsg_semseg_metrics": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, _P]),
+    "hmsg_evaluate_semseg": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P]),
     "hmsg_eval_default_params": (None, [_P]),
     "hmsg_graph_evaluate": (C.c_int, [_P, _P, _P, _P, _P]),
     "hmsg_write_json": (C.c_int, [C.c_char_p, C.c_int32, _P]),
@@ -251,6 +256,7 @@ _SIGS = {
     "hmsg_test_pool_rows": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_double, C.c_int32, _P]),
     "hmsg_test_graph_early_objects": (C.c_int, [_P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "hmsg_test_sam_post_last": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "hmsg_test_knn_last_phase2": (C.c_int64, []),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
@@ -434,6 +440,32 @@ def eval_top_k(rank, n_classes, top_k, lib_=None):
     auc = C.c_double(0)
     _eval_ck(L.c.hmsg_eval_top_k(_ptr(rank), len(rank), int(n_classes), _ptr(ks), len(ks), _ptr(acc), C.byref(auc)), "hmsg_eval_top_k")
     return {int(k): float(a) for k, a in zip(ks, acc)}, auc.value
+
+
+class SemsegScores(C.Structure):
+    """hmsg_semseg_scores (include/hmsg.h)"""
+    _fields_ = [("miou", C.c_double), ("fmiou", C.c_double), ("acc", C.c_double), ("macc", C.c_double)]
+
+    def as_dict(self):
+        return dict(miou=float(self.miou), fmiou=float(self.fmiou), acc=float(self.acc), macc=float(self.macc))
+
+
+def semseg_metrics(confusion, ignore=(), lib_=None):
+    """metric.py's numbers from a confusion matrix [L, L] (rows ground truth, columns prediction; include/hmsg.h:
+    hmsg_semseg_metrics).  `ignore`: class indices in [0, L).  -> dict(miou, fmiou, acc, macc, per_class_iou float64 [L]: NaN for a
+    class on neither side, 0 for an ignored one)"""
+    L = lib_ or lib()
+    conf = np.ascontiguousarray(confusion, np.int64)
+    if conf.ndim != 2 or conf.shape[0] != conf.shape[1]:
+        raise HmsgError("semseg_metrics: a square matrix expected")
+    ig = np.ascontiguousarray(list(ignore), np.int32).reshape(-1)
+    out = SemsegScores()
+    pc = np.zeros(conf.shape[0], np.float64)
+    _eval_ck(L.c.hmsg_semseg_metrics(_ptr(conf), conf.shape[0], _ptr(ig) if len(ig) else None, len(ig), C.byref(out), _ptr(pc)),
+             "hmsg_semseg_metrics")
+    d = out.as_dict()
+    d["per_class_iou"] = pc
+    return d
 
 
 class Comm:
@@ -887,6 +919,91 @@ class Scene:
         rank = np.zeros(max(n, 1), np.int32)
         self._ck(self.L.c.hmsg_eval_semantic_ranks(self.h, n, _ptr(emb), int(f64), D, Cn, _ptr(text), _ptr(cn), _ptr(tg), _ptr(rank)))
         return rank[:n]
+
+    def semseg_instance_labels(self, emb, text, class_label):
+        """text_prompt + sim_2_label (include/hmsg.h: hmsg_semseg_instance_labels): the class label of the text row with the largest
+        float32 cosine, the smaller index among equal ones; a zero embedding gets class_label[0].  emb [n, D] float32 or float64, text
+        [C, D] float32, class_label int32 [C]: numpy arrays or contiguous torch tensors, host or device.  Returns int32 [n] (numpy)."""
+        if hasattr(emb, "data_ptr"):
+            f64 = str(emb.dtype).split(".")[-1] == "float64"
+            emb = self._eval_arg(emb, np.float64 if f64 else np.float32, "semseg_instance_labels")
+        else:
+            f64 = np.asarray(emb).dtype == np.float64
+            emb = np.ascontiguousarray(emb, np.float64 if f64 else np.float32)
+        text = self._eval_arg(text, np.float32, "semseg_instance_labels")
+        cl = self._eval_arg(class_label, np.int32, "semseg_instance_labels")
+        if len(emb.shape) != 2 or len(text.shape) != 2 or emb.shape[1] != text.shape[1] or int(cl.shape[0]) != int(text.shape[0]):
+            raise HmsgError("semseg_instance_labels: emb [n, D], text [C, D] and class_label [C] expected")
+        n = int(emb.shape[0])
+        out = np.zeros(max(n, 1), np.int32)
+        self._ck(self.L.c.hmsg_semseg_instance_labels(self.h, n, _ptr(emb), int(f64), int(emb.shape[1]), int(text.shape[0]), _ptr(text), _ptr(cl),
+                                                      _ptr(out)))
+        return out[:n]
+
+    def knn_labels(self, points, labels, queries, k, return_index=False, out=None, out_index=None):
+        """knn_interpolation's label transfer (include/hmsg.h: hmsg_knn_labels): points float64 [n, 3] with labels int32 [n] (-1: the
+        row is dropped), queries float64 [m, 3], 1 <= k <= 16: numpy arrays or contiguous torch tensors, host or device.  Returns int32
+        [m] (with return_index also int32 [m, k]: the neighbours' positions after the drop, in (d2, index) order), as numpy arrays -- or
+        written into `out` / `out_index` when given (numpy or torch, host or device), which are then what is returned."""
+        pts = self._eval_arg(points, np.float64, "knn_labels")
+        lab = self._eval_arg(labels, np.int32, "knn_labels")
+        q = self._eval_arg(queries, np.float64, "knn_labels")
+        n = int(np.prod(tuple(pts.shape))) // 3
+        m = int(np.prod(tuple(q.shape))) // 3
+        if int(np.prod(tuple(lab.shape))) != n:
+            raise HmsgError("knn_labels: %d points and %d labels" % (n, int(np.prod(tuple(lab.shape)))))
+        k = int(k)
+        if out is None:
+            out = np.zeros(m, np.int32)
+        if return_index and out_index is None:
+            out_index = np.zeros((m, max(k, 1)), np.int32)
+        self._ck(self.L.c.hmsg_knn_labels(self.h, n, _ptr(pts), _ptr(lab), m, _ptr(q), k, _ptr(out), _ptr(out_index) if return_index else None))
+        return (out, out_index) if return_index else out
+
+    def knn_last_phase2(self):
+        """queries the last knn_labels / evaluate_semseg call finished by scan (include/hmsg_test.h: hmsg_test_knn_last_phase2)"""
+        return int(self.L.c.hmsg_test_knn_last_phase2())
+
+    def semseg_confusion(self, gt_label, pred_label, n_labels):
+        """confusion matrix int64 [L, L] (rows ground truth, columns prediction) of labels in [0, L) (include/hmsg.h:
+        hmsg_semseg_confusion): int32 arrays of one length, numpy or contiguous torch tensors, host or device."""
+        g = self._eval_arg(gt_label, np.int32, "semseg_confusion")
+        p = self._eval_arg(pred_label, np.int32, "semseg_confusion")
+        m = int(np.prod(tuple(g.shape)))
+        if int(np.prod(tuple(p.shape))) != m:
+            raise HmsgError("semseg_confusion: the label arrays differ in length")
+        L_ = int(n_labels)
+        conf = np.zeros((max(L_, 1), max(L_, 1)), np.int64)
+        self._ck(self.L.c.hmsg_semseg_confusion(self.h, m, _ptr(g), _ptr(p), L_, _ptr(conf)))
+        return conf
+
+    def evaluate_semseg(self, text, class_ids, gt_points, gt_labels, k=5, ignore=()):
+        """The semantic segmentation score of the pooled scene (include/hmsg.h: hmsg_evaluate_semseg): text float32 [C, D] with the
+        class id of every row, ground-truth points float64 [m, 3] with their class ids; ids are arbitrary integers, mapped to [0, L)
+        through np.unique of all of them (class_ids and gt_labels on the host).  -> dict(miou, fmiou, acc, macc, per_class_iou {id:
+        iou}, confusion int64 [L, L], classes int64 [L])"""
+        cid = np.asarray(class_ids).reshape(-1).astype(np.int64)
+        gl = np.asarray(gt_labels.detach().cpu().numpy() if hasattr(gt_labels, "detach") else gt_labels).reshape(-1).astype(np.int64)
+        classes = np.unique(np.concatenate([cid, gl, np.asarray(list(ignore), np.int64)]))
+        L_ = len(classes)
+        text = self._eval_arg(text, np.float32, "evaluate_semseg")
+        gp = self._eval_arg(gt_points, np.float64, "evaluate_semseg")
+        cl = np.ascontiguousarray(np.searchsorted(classes, cid), np.int32)
+        g32 = np.ascontiguousarray(np.searchsorted(classes, gl), np.int32)
+        ig = np.ascontiguousarray(np.searchsorted(classes, np.asarray(list(ignore), np.int64)), np.int32)
+        if len(text.shape) != 2 or int(text.shape[0]) != len(cl):
+            raise HmsgError("evaluate_semseg: text [C, D] and C class ids expected")
+        m = int(np.prod(tuple(gp.shape))) // 3
+        if m != len(g32):
+            raise HmsgError("evaluate_semseg: %d ground-truth points and %d labels" % (m, len(g32)))
+        sc = SemsegScores()
+        pc = np.zeros(L_, np.float64)
+        conf = np.zeros((L_, L_), np.int64)
+        self._ck(self.L.c.hmsg_evaluate_semseg(self.h, _ptr(text), len(cl), _ptr(cl), _ptr(gp), _ptr(g32), m, int(k), L_,
+                                               _ptr(ig) if len(ig) else None, len(ig), C.byref(sc), _ptr(pc), _ptr(conf)))
+        d = sc.as_dict()
+        d.update(per_class_iou={int(c): float(v) for c, v in zip(classes, pc)}, confusion=conf, classes=classes)
+        return d
 
     def room_clouds(self, y_lo, y_hi, T, z_levels, room_xz):
         """segment_hmsg_room's room clouds on the device (include/hmsg.h: hmsg_room_clouds): room_xz = list of [n, 2] arrays;

@@ -170,4 +170,59 @@ inline double top_k_auc(const int32_t* rank, int64_t n, int64_t C) {
     return trapz(acc.data(), x.data(), acc.size());
 }
 
+// ---- utils/metric.py from a confusion matrix conf[gt][pred] (L x L, counts): pixel_accuracy (:5-36), mean_accuracy (:39-65),
+// per_class_iou (:68-103), mean_iou (:106-140), frequency_weighted_iou (:143-179).  The reference works on float64 masks, so its
+// n_ii, t_i, n_ij are float64 counts; `cl` is np.unique of the ground truth (mean_accuracy, pixel_accuracy) or the union with the
+// prediction's (the IoUs); a skipped class leaves the 0 its list was made with, and np.sum adds the whole list pairwise.
+struct SemsegScores {
+    double miou = 0.0, fmiou = 0.0, acc = 0.0, macc = 0.0;
+};
+inline SemsegScores semseg_metrics(const int64_t* conf, int32_t L, const int32_t* ignore, int32_t n_ignore, double* per_class_iou) {
+    std::vector<double> t((size_t)L, 0.0), p((size_t)L, 0.0);      // ground-truth points, predicted points per class
+    double m = 0.0;
+    for (int32_t g = 0; g < L; ++g)
+        for (int32_t q = 0; q < L; ++q) {
+            const double v = (double)conf[(size_t)g * L + q];
+            t[(size_t)g] += v;
+            p[(size_t)q] += v;
+            m += v;
+        }
+    auto ignored = [&](int32_t c) {
+        for (int32_t k = 0; k < n_ignore; ++k)
+            if (ignore[k] == c) return true;
+        return false;
+    };
+    std::vector<double> acc_terms, iou_terms, fw_terms;
+    double sum_nii = 0.0, sum_ti = 0.0, ignored_pts = 0.0;
+    int64_t n_gt = 0, n_overlap = 0;
+    for (int32_t c = 0; c < L; ++c) {
+        const double nii = (double)conf[(size_t)c * L + c], ti = t[(size_t)c], nij = p[(size_t)c];
+        const bool in_gt = ti > 0.0, in_union = in_gt || nij > 0.0, ign = ignored(c);
+        if (per_class_iou) per_class_iou[c] = !in_union ? std::nan("") : ign ? 0.0 : nii / (ti + nij - nii);
+        if (in_gt) {
+            ++n_gt;
+            if (ign) {
+                ++n_overlap;
+                acc_terms.push_back(0.0);
+            } else {
+                sum_nii += nii;
+                sum_ti += ti;
+                acc_terms.push_back(nii / ti);
+            }
+        }
+        if (in_union) {
+            if (ign) ignored_pts += ti;
+            const bool skip = ign || ti == 0.0 || nij == 0.0;
+            iou_terms.push_back(skip ? 0.0 : nii / (ti + nij - nii));
+            fw_terms.push_back(skip ? 0.0 : (ti * nii) / (ti + nij - nii));
+        }
+    }
+    SemsegScores s;
+    s.acc = sum_ti == 0.0 ? 0.0 : sum_nii / sum_ti;
+    s.macc = np_sum(acc_terms.data(), acc_terms.size()) / (double)(n_gt - n_overlap);
+    s.miou = np_sum(iou_terms.data(), iou_terms.size()) / (double)(n_gt - n_overlap);
+    s.fmiou = np_sum(fw_terms.data(), fw_terms.size()) / (m - ignored_pts);
+    return s;
+}
+
 }  // namespace eval_metrics

@@ -621,6 +621,26 @@ class Graph:
                 self._text_cache[w] = v
         return np.stack([self._text_cache[w] for w in words]).astype(np.float32)
 
+    # ------------------------------------------------------------------ semantic segmentation score (utils/eval_utils.py, utils/metric.py)
+    def evaluate_semseg(self, gt_points, gt_labels, classes, k=5, ignore=(), class_ids=None):
+        """The open-vocabulary semantic segmentation score of the feature map against a labelled ground-truth cloud, on the device
+        (include/hmsg.h: hmsg_evaluate_semseg): every instance takes the class of its most similar text row, its points are painted
+        with it, the labels are carried onto gt_points [m, 3] by the k-NN vote of knn_interpolation and scored as metric.py scores them.
+        classes: class names (their text features come from get_text_feats_multiple_templates), a dict {class id: name}, or the text
+        features themselves, float [C, D]; class_ids: the id of every row (default 0 .. C - 1, or the dict's keys).  gt_labels and
+        ignore speak in those ids.  -> dict(miou, fmiou, acc, macc, per_class_iou {id: iou}, confusion, classes)"""
+        if self.scene is None:
+            raise RuntimeError("evaluate_semseg: this Graph holds no resident scene (create_feature_map or restore_scene first)")
+        if isinstance(classes, dict):
+            class_ids = list(classes.keys()) if class_ids is None else class_ids
+            classes = list(classes.values())
+        if len(classes) and isinstance(classes[0], str):
+            text = self.get_text_feats_multiple_templates(list(classes))
+        else:
+            text = np.ascontiguousarray(classes.detach().cpu().numpy() if hasattr(classes, "detach") else classes, np.float32)
+        ids = np.arange(len(text)) if class_ids is None else np.asarray(class_ids)
+        return self.scene.evaluate_semseg(np.ascontiguousarray(text, np.float32), ids, gt_points, gt_labels, k=k, ignore=ignore)
+
     def _scene_from_config(self, H, W, max_frames):
         """a Scene with the pipeline.* keys of the config (graph.py:262-337)"""
         p = lambda k, d=None: _get(self.cfg, "pipeline." + k, d)

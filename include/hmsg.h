@@ -507,6 +507,58 @@ int hmsg_eval_hydra_means(const double* over_pred, const double* over_gt, int32_
 /* :585-588 from the ranks: top_k_acc[i] = (pairs with rank < top_k[i]) / n; *top_k_auc = np.trapz(accuracy at k in range(0, C, 10), k / C) */
 int hmsg_eval_top_k(const int32_t* rank, int32_t n, int32_t C, const int32_t* top_k, int32_t n_top_k, double* top_k_acc, double* top_k_auc);
 
+/* ---- the open-vocabulary semantic segmentation score of a feature map (utils/eval_utils.py, utils/metric.py; csrc/hmsg_semseg.hip).
+ * text_prompt (eval_utils.py:80-95) + sim_2_label (:285-293): label_out[i] = class_label[c*], c* the smallest c with the largest
+ * cosine of emb[i] against text[c].  emb [n][D] (f32, or f64 with emb_is_f64 != 0: cast to f32 first), text [C][D] f32, class_label
+ * i32 [C], label_out i32 [n].  The cosine is torch's cosine_similarity in float32: every row is divided by max(||row||, 1e-8) and the
+ * rows are dotted, summed in the kernel's own order, which does not depend on c: rows of the same bits give the same similarity.
+ * A ZERO embedding is a real case (graph.py:479-483 pushes zeros(1, D) for an empty instance): all its similarities are 0 and it
+ * gets class_label[0].  This is NOT the rule of hmsg_eval_semantic_ranks, where a zero row gives NaN similarities (torchmetrics
+ * divides by the norm itself).  Arrays host or device memory.  D <= 8192.  n == 0: success, nothing is launched. */
+int hmsg_semseg_instance_labels(hmsg_t* h, int32_t n, const void* emb, int32_t emb_is_f64, int32_t D, int32_t C, const float* text,
+                                const int32_t* class_label, int32_t* label_out);
+/* knn_interpolation (eval_utils.py:308-339; Tree_interpolation, :296-305, is k = 1): labelled points lp f64 [n][3] with lab i32 [n],
+ * queries q f64 [m][3], 1 <= k <= 16.  Rows with lab == -1 are dropped first, the others keep their order (:318).  For every query
+ * the k labelled rows that are smallest by (d2, index) are taken: d2 = ((dx*dx) + (dy*dy)) + (dz*dz) in float64, uncontracted (the
+ * rdist sklearn's Euclidean metric accumulates), index = the row's position after the drop.  out_label[j] i32 = the most frequent
+ * label among the k, the smallest label among equally frequent ones (np.bincount(...).argmax(), :330).  out_nn_index (may be NULL)
+ * i32 [m][k]: those k positions in (d2, index) order.  This is the reference's answer wherever the k-th and (k + 1)-th distance of a
+ * query differ or the tied rows carry one label; AT EXACT TIES sklearn's BallTree takes whichever row its traversal met first, which
+ * is no rule, and this call takes the smaller index.  The search is exact (csrc/hmsg_semseg.hip): a lattice walk per query, and a
+ * scan of all rows for the queries far from every labelled row; HMSG_DEBUG_KNN_BRUTE=1 (development) scans for every query, same bits.
+ * Arrays host or device memory.  HMSG_ERR_INVALID with the outputs untouched: k outside 1 .. 16 (checked first, whatever m is);
+ * then m == 0 is success and nothing is launched or looked at; for m > 0: fewer than k labelled rows after the drop (sklearn raises),
+ * a label below -1, a coordinate that is not finite in a query or in a labelled row that is kept (rows with lab == -1 are dropped
+ * before the reference builds its tree, so what they hold does not matter here either). */
+int hmsg_knn_labels(hmsg_t* h, int64_t n, const double* lp, const int32_t* lab, int64_t m, const double* q, int32_t k, int32_t* out_label,
+                    int32_t* out_nn_index);
+/* conf i64 [L][L], rows ground truth, columns prediction: conf[g][p] = points j with gt_label[j] == g and pred_label[j] == p, labels
+ * in [0, L), L <= 4096.  Integer atomics (a histogram per workgroup in LDS while L * L counters fit, global ones otherwise): two calls
+ * give the same matrix.  Arrays host or device memory.  HMSG_ERR_INVALID with conf untouched: a label outside [0, L). */
+int hmsg_semseg_confusion(hmsg_t* h, int64_t m, const int32_t* gt_label, const int32_t* pred_label, int32_t L, int64_t* conf);
+typedef struct hmsg_semseg_scores {
+    double miou, fmiou, acc, macc;     /* mean_iou, frequency_weighted_iou, pixel_accuracy, mean_accuracy */
+} hmsg_semseg_scores;
+/* metric.py's numbers from the confusion matrix, float64 on the host (csrc/hmsg_eval_metrics_host.h; host arrays; a failed call's
+ * message goes to stderr), quirks included: the class lists are the labels PRESENT (:212-234: the ground truth's classes, and the
+ * union of ground-truth and predicted classes); mean_iou and frequency_weighted_iou skip a class absent on either side (:130, :167),
+ * per_class_iou does not (:93-94 is commented out); mean_accuracy and mean_iou divide by (ground-truth classes - ignored classes
+ * present in the ground truth) (:64, :139), which may be 0: the IEEE quotient is returned; frequency_weighted_iou divides by m - (the
+ * ground-truth points of ignored classes) (:176) and ignores nothing else; pixel_accuracy is 0 when no counted point is left (:31-32).
+ * The per-class terms are summed as np.sum sums a float64 array in ascending class order (numpy's pairwise sum), skipped classes
+ * standing in it as zeros.  per_class_iou (may be NULL) f64 [L]: NaN for a class outside the union, 0 for an ignored one. */
+int hmsg_semseg_metrics(const int64_t* conf, int32_t L, const int32_t* ignore, int32_t n_ignore, hmsg_semseg_scores* out,
+                        double* per_class_iou);
+/* The whole evaluation on a scene after hmsg_pool_instances: hmsg_semseg_instance_labels on the pooled features (cfg.feat_dim
+ * columns), every instance's pool points painted with its label on the device (instances in order, duplicates kept),
+ * hmsg_knn_labels of gt_pts f64 [m][3] in them, hmsg_semseg_confusion against gt_label i32 [m], hmsg_semseg_metrics.  class_label
+ * and gt_label are ids in [0, L).  No instance point or feature goes to the host.  per_class_iou f64 [L] and conf i64 [L][L] may be
+ * NULL; text / class_label / gt_pts / gt_label / conf host or device memory, ignore / scores / per_class_iou host.
+ * HMSG_ERR_INVALID: a scene without pooled instances, and whatever the four calls refuse. */
+int hmsg_evaluate_semseg(hmsg_t* h, const float* text, int32_t C, const int32_t* class_label, const double* gt_pts, const int32_t* gt_label,
+                         int64_t m, int32_t k, int32_t L, const int32_t* ignore, int32_t n_ignore, hmsg_semseg_scores* scores,
+                         double* per_class_iou, int64_t* conf);
+
 /* N2, load side: the object table of a saved graph straight into a retrieval index.  For every stem <dir>/<stem>.json is
  * read and its "embedding" array parsed as float64 (object.py:75-91 load; graph.py:1892-1987 load_hmsg_graph), rows in
  * the order given; room_of_node as for hmsg_index_create (declared below).  feat_dim (optional) receives the row length.

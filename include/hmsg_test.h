@@ -122,6 +122,10 @@ int hmsg_test_graph_early_objects(const hmsg_graph_t* g, const hmsg_t* h, int32_
  * launch over the logits.  Any pointer may be NULL. */
 int hmsg_test_sam_post_last(int32_t* rounds_holes, int32_t* rounds_islands, double* stats_ms);
 
+/* measurement hook: the queries that the process's last hmsg_knn_labels call (hmsg_evaluate_semseg's included) finished by scan
+ * (phase 2) -- all of them under HMSG_DEBUG_KNN_BRUTE=1. */
+int64_t hmsg_test_knn_last_phase2(void);
+
 #ifdef __cplusplus
 }
 #endif
