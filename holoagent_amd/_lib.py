@@ -85,6 +85,19 @@ class HmsgSamPostParams(C.Structure):   # include/hmsg.h: hmsg_sam_post_params
                 ("mask_threshold", C.c_float), ("box_nms_thresh", C.c_float), ("min_mask_region_area", C.c_int32)]
 
 
+class HmsgNavParams(C.Structure):       # include/hmsg.h: hmsg_nav_params
+    _fields_ = [("cell_size", C.c_double), ("obstacle_lo", C.c_double), ("obstacle_hi", C.c_double), ("region_max", C.c_double),
+                ("pose_radius", C.c_double), ("pose_eps", C.c_double), ("dilation", C.c_int32), ("blur", C.c_int32),
+                ("pose_min_samples", C.c_int32), ("region_rule", C.c_int32)]
+
+
+class HmsgNavMaps(C.Structure):         # include/hmsg.h: hmsg_nav_maps
+    _fields_ = [("obstacle_map", C.c_void_p), ("region_map", C.c_void_p), ("poses_map", C.c_void_p), ("free_map", C.c_void_p),
+                ("main_free_map", C.c_void_p), ("top_down_bgr", C.c_void_p), ("boundary_rc", C.c_void_p), ("boundary_capacity", C.c_int64),
+                ("n_boundary", C.c_int64), ("main_area", C.c_int64), ("n_regions", C.c_int32), ("main_label", C.c_int32),
+                ("grid", C.c_int32 * 2), ("pcd_min", C.c_double * 3), ("pcd_max", C.c_double * 3)]
+
+
 class HmsgError(RuntimeError):
     pass
 
@@ -118,6 +131,13 @@ _SIGS = {
     "hmsg_sam_post_default_params": (None, [_P]),
     "hmsg_sam_postprocess": (C.c_int, [C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int64, C.POINTER(C.c_int32),
                                        C.POINTER(C.c_int64), _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_double)]),
+    "hmsg_nav_default_params": (None, [_P]),
+    "hmsg_nav_grid": (C.c_int, [C.c_int32, C.c_double, C.c_int64, _P, _P, _P, _P]),
+    "hmsg_nav_floor_maps": (C.c_int, [C.c_int32, _P, C.c_int64, _P, _P, C.c_double, C.c_int32, _P, _P]),
+    "hmsg_map_nav_grid": (C.c_int, [_P, C.c_double, C.c_double, C.c_double, _P, _P, _P]),
+    "hmsg_map_nav_floor_maps": (C.c_int, [_P, C.c_double, C.c_double, C.c_double, _P, C.c_int32, _P, _P]),
+    "hmsg_graph_nav_grid": (C.c_int, [_P, C.c_int32, C.c_double, _P, _P, _P]),
+    "hmsg_graph_nav_floor_maps": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, _P]),
     "hmsg_get_frame_num_masks": (C.c_int32, [_P, C.c_int32]),
     "hmsg_fuse_frames": (C.c_int, [_P]),
     "hmsg_get_map_feats": (C.c_int, [_P, _P, _P]),
@@ -256,6 +276,7 @@ _SIGS = {
     "hmsg_test_pool_rows": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_double, C.c_int32, _P]),
     "hmsg_test_graph_early_objects": (C.c_int, [_P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "hmsg_test_sam_post_last": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "hmsg_test_nav_last": (C.c_int, [C.POINTER(C.c_int32)]),
     "hmsg_test_knn_last_phase2": (C.c_int64, []),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -1048,6 +1069,22 @@ class Scene:
                                             float(min_visible_ratio), float(max_depth), _ptr(vis), _ptr(md)))
         return vis[:len(pi)].astype(bool), md[:len(pi)]
 
+    def nav_grid(self, y_lo, y_hi, cell_size=0.03):
+        """bounds and grid of the slab y_lo <= y <= y_hi of the map (include/hmsg.h: hmsg_map_nav_grid) -> (pcd_min, pcd_max, (columns, rows))"""
+        mn, mx, grid = np.zeros(3), np.zeros(3), np.zeros(2, np.int32)
+        self._ck(self.L.c.hmsg_map_nav_grid(self.h, float(y_lo), float(y_hi), float(cell_size), _ptr(mn), _ptr(mx), _ptr(grid)))
+        return mn, mx, (int(grid[0]), int(grid[1]))
+
+    def nav_floor_maps(self, y_lo, y_hi, zero_level, poses, params=None, top_down=True, **over):
+        """The navigation maps of a slab of the map (include/hmsg.h: hmsg_map_nav_floor_maps): the slab is selected on the device, no
+        point of it goes to the host.  y_lo, y_hi, zero_level: a storey of segment_floors().  -> the dict of nav_floor_maps."""
+        prm = params if params is not None else nav_params(self.L, **over)
+        _, _, (W, H) = self.nav_grid(y_lo, y_hi, prm.cell_size)
+        P_ = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 16))
+        return _nav_call(H, W, top_down, lambda out: self._ck(
+            self.L.c.hmsg_map_nav_floor_maps(self.h, float(y_lo), float(y_hi), float(zero_level), C.byref(prm), len(P_),
+                                             _ptr(P_) if len(P_) else None, C.byref(out))))
+
     def segment_floors(self):
         """A8 behind the C ABI (include/hmsg.h: hmsg_segment_floors) -> list of dicts (y_lo, y_hi, zero_level, height,
         bbox_min, bbox_max, n_points)."""
@@ -1331,6 +1368,21 @@ class SceneGraph:
 
     def save(self, directory):
         self._ck(self.L.c.hmsg_save(self.g, str(directory).encode()))
+
+    def nav_grid(self, floor, cell_size=0.03):
+        """bounds and grid of a storey's cloud (include/hmsg.h: hmsg_graph_nav_grid) -> (pcd_min [3], pcd_max [3], (columns, rows))"""
+        mn, mx, grid = np.zeros(3), np.zeros(3), np.zeros(2, np.int32)
+        self._ck(self.L.c.hmsg_graph_nav_grid(self.g, int(floor), float(cell_size), _ptr(mn), _ptr(mx), _ptr(grid)))
+        return mn, mx, (int(grid[0]), int(grid[1]))
+
+    def nav_floor_maps(self, floor, poses, params=None, top_down=True, **over):
+        """The navigation maps of storey `floor` (include/hmsg.h: hmsg_graph_nav_floor_maps): the map's slab is selected on the
+        device, no point of it goes to the host.  poses: [n, 4, 4] camera-to-world.  -> the dict of nav_floor_maps."""
+        prm = params if params is not None else nav_params(self.L, **over)
+        _, _, (W, H) = self.nav_grid(floor, prm.cell_size)
+        P_ = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 16))
+        return _nav_call(H, W, top_down, lambda out: self._ck(
+            self.L.c.hmsg_graph_nav_floor_maps(self.g, int(floor), C.byref(prm), len(P_), _ptr(P_) if len(P_) else None, C.byref(out))))
 
     def index(self, room_name_emb=None):
         ix = _P()
@@ -1894,6 +1946,94 @@ def sam_postprocess(logits, iou_preds, params=None, max_out=None, counts_cap=Non
     k = n.value
     return dict(n=k, keep_idx=keep[:k], counts=counts[:nc.value], run_off=run_off[:k + 1], bbox=bbox[:k], area=area[:k],
                 stability_score=stab[:k], masks=masks[:k] if return_masks else None, device_ms=ms.value, size=(H, W))
+
+
+def nav_params(lib_: "HmsgLib | None" = None, **over):
+    """hmsg_nav_params with the reference's values (hmsg_nav_default_params), fields overridden by keyword"""
+    L = lib_ or lib()
+    p = HmsgNavParams()
+    L.c.hmsg_nav_default_params(C.byref(p))
+    for k, v in over.items():
+        if not hasattr(p, k):
+            raise HmsgError(f"unknown hmsg_nav_params field {k}")
+        setattr(p, k, int(v) if k in ("dilation", "blur", "pose_min_samples", "region_rule") else float(v))
+    return p
+
+
+def nav_grid(points, cell_size=0.03, device_id=0, lib_: "HmsgLib | None" = None):
+    """bounds and grid of a storey's cloud (include/hmsg.h: hmsg_nav_grid): points float64 [n, 3], numpy or a device tensor
+    -> (pcd_min [3], pcd_max [3], (columns, rows))"""
+    L = lib_ or lib()
+    if not (hasattr(points, "data_ptr") and getattr(points, "is_cuda", False)):
+        points = np.ascontiguousarray(np.asarray(points, np.float64).reshape(-1, 3))
+    mn, mx, grid = np.zeros(3), np.zeros(3), np.zeros(2, np.int32)
+    rc = L.c.hmsg_nav_grid(int(device_id), float(cell_size), int(points.shape[0]), _ptr(points), _ptr(mn), _ptr(mx), _ptr(grid))
+    if rc != 0:
+        raise HmsgError(f"hmsg_nav_grid failed ({rc}) (the message is on stderr)")
+    return mn, mx, (int(grid[0]), int(grid[1]))
+
+
+def _nav_call(H, W, top_down, call, device=None):
+    """allocates the maps (numpy, or torch tensors on `device`), runs call(out) and repeats it once when the boundary list was too
+    short"""
+    if device is not None:
+        import torch
+        buf = lambda shape, np_dtype: torch.empty(shape, dtype=getattr(torch, np.dtype(np_dtype).name), device=device)
+    else:
+        buf = lambda shape, np_dtype: np.empty(shape, np_dtype)
+    maps = dict(obstacle_map=buf((H, W), np.float32), region_map=buf((H, W), np.uint8), poses_map=buf((H, W), np.uint8),
+                free_map=buf((H, W), np.uint8), main_free_map=buf((H, W), np.uint8))
+    if top_down:
+        maps["top_down_bgr"] = buf((H, W, 3), np.uint8)
+    cap = 2 * (H + W) + 4096
+    out = HmsgNavMaps()
+    for attempt in range(2):
+        rc_buf = buf((max(cap, 1), 2), np.int32)
+        for k, v in maps.items():
+            setattr(out, k, _ptr(v))
+        out.boundary_rc, out.boundary_capacity = _ptr(rc_buf), cap
+        try:
+            call(out)
+            break
+        except HmsgError:
+            if attempt == 0 and out.n_boundary > cap:
+                cap = int(out.n_boundary)
+                continue
+            raise
+    assert (int(out.grid[0]), int(out.grid[1])) == (W, H)
+    maps.update(boundary_rc=rc_buf[: out.n_boundary], n_regions=int(out.n_regions), main_label=int(out.main_label),
+                main_area=int(out.main_area), grid=(W, H), pcd_min=np.array(out.pcd_min[:]), pcd_max=np.array(out.pcd_max[:]))
+    return maps
+
+
+def nav_floor_maps(points, colors, zero_level, poses, params=None, device_id=0, lib_: "HmsgLib | None" = None, **over):
+    """The navigation maps of a storey on the device (include/hmsg.h: hmsg_nav_floor_maps).  points float64 [n, 3]; colors float64
+    [n, 3] in [0, 1] or None (no top-down image); poses [m, 4, 4].  numpy in: numpy out; device tensors in: the maps are device
+    tensors and nothing of the storey crosses to the host.  -> dict(obstacle_map f32 [H, W] (NavigationGraph.map), region_map,
+    poses_map, free_map, main_free_map u8 [H, W], top_down_bgr u8 [H, W, 3], boundary_rc i32 [k, 2] in row-major order,
+    n_regions, main_label, main_area, grid (columns, rows), pcd_min, pcd_max).  params: an HmsgNavParams, or fields by keyword."""
+    L = lib_ or lib()
+    prm = params if params is not None else nav_params(L, **over)
+    on_dev = hasattr(points, "data_ptr") and getattr(points, "is_cuda", False)
+    if on_dev:
+        import torch
+        assert points.dtype == torch.float64 and (colors is None or (colors.dtype == torch.float64 and colors.device == points.device))
+        points, colors = points.contiguous(), None if colors is None else colors.contiguous()
+        device_id = points.device.index or 0
+    else:
+        points = np.ascontiguousarray(np.asarray(points, np.float64).reshape(-1, 3))
+        colors = None if colors is None else np.ascontiguousarray(np.asarray(colors, np.float64).reshape(-1, 3))
+    n = int(points.shape[0])
+    assert colors is None or int(colors.shape[0]) == n
+    _, _, (W, H) = nav_grid(points, prm.cell_size, device_id, L)
+    P_ = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 16))
+
+    def call(out):
+        rc = L.c.hmsg_nav_floor_maps(int(device_id), C.byref(prm), n, _ptr(points), _ptr(colors), float(zero_level), len(P_),
+                                     _ptr(P_) if len(P_) else None, C.byref(out))
+        if rc != 0:
+            raise HmsgError(f"hmsg_nav_floor_maps failed ({rc}) (the message is on stderr)")
+    return _nav_call(H, W, colors is not None, call, device=points.device if on_dev else None)
 
 
 def _clip_params(L, size, f16, mean, std):

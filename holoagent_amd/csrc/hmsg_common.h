@@ -865,3 +865,13 @@ void hmsg_graph_early_join(hmsg_ctx* h) noexcept;
 void hmsg_graph_early_abort(hmsg_ctx* h) noexcept;
 void hmsg_pool(hmsg_ctx* h);            // hmsg_pool.hip
 long long hmsg_voxel_ds(hmsg_ctx* h, const double* pts, long long n, double vs, double* out);   // hmsg_merge.hip
+// 8-connected labelling of the cells of class fg of K images u8 [K][H][W] on stream s (hmsg_sam_post.hip, k_spcc_*): lab[p] =
+// smallest cell index of p's component (SP_NONE = INT_MAX outside the class), cnt[root] = the component's cells; lab, cnt i32
+// [K][H * W].  Returns the rounds it took.
+int hmsg_cc8_components(hipStream_t s, const unsigned char* masks, int K, int H, int W, int fg, int* lab, int* cnt);
+// the navigation maps of the points of d_xyz (device memory, f64 [n][3]; d_rgb the same or null) with y_lo <= y <= y_hi
+// (hmsg_navmap.hip); fn names the entry point in the messages
+void hmsg_nav_maps_device(const char* fn, const hmsg_nav_params& prm, const double* d_xyz, const double* d_rgb, long long n, double y_lo,
+                          double y_hi, double zero_level, int n_poses, const double* poses, hmsg_nav_maps* out);
+void hmsg_nav_grid_device(const char* fn, double cell_size, const double* d_xyz, long long n, double y_lo, double y_hi, double* pcd_min,
+                          double* pcd_max, int32_t* grid);

@@ -547,3 +547,9 @@ extern "C" int hmsg_test_sam_post_last(int32_t* rounds_holes, int32_t* rounds_is
     if (stats_ms) *stats_ms = g_sp_last.stats_ms;
     return HMSG_OK;
 }
+
+// the labelling for the library's other image stages (hmsg_common.h)
+int hmsg_cc8_components(hipStream_t s, const unsigned char* masks, int K, int H, int W, int fg, int* lab, int* cnt) {
+    SpWork wk{s, H, W, H * W};
+    return wk.components(masks, K, fg, lab, cnt);
+}

@@ -1399,6 +1399,36 @@ int hmsg_graph_to_json(const hmsg_graph_t* g, char* buf, int64_t capacity, int64
     });
 }
 
+/* the navigation maps of a storey (hmsg_navmap.hip): the slab hmsg_save writes, selected on the device from the map in HBM */
+static GFloor& nav_floor(hmsg_graph_t* g, int32_t floor, const char* fn) {
+    const std::string f = fn;
+    HMSG_REQUIRE(!g->loaded, HMSG_ERR_INVALID,
+                 f + ": a graph read by hmsg_load has no cloud in HBM (give the points of hmsg_read_ply to hmsg_nav_floor_maps)");
+    HMSG_REQUIRE(g->finished && g->h, HMSG_ERR_INVALID, f + ": a graph built by hmsg_build_graph / hmsg_graph_finish (its map lives in the scene handle)");
+    HMSG_REQUIRE(g->h->map_ready, HMSG_ERR_INVALID, f + ": map not finalised");
+    HMSG_REQUIRE(floor >= 0 && (size_t)floor < g->floors.size(), HMSG_ERR_INVALID, f + ": no such floor");
+    HIP_TRY(hipSetDevice(g->h->cfg.device_id));
+    HIP_TRY(hipStreamSynchronize(g->h->stream));
+    return g->floors[(size_t)floor];
+}
+int hmsg_graph_nav_grid(hmsg_graph_t* g, int32_t floor, double cell_size, double* pcd_min, double* pcd_max, int32_t* grid) {
+    if (!g || !grid) return HMSG_ERR_INVALID;
+    return hmsg_boundary(&g->err, -1, [&] {
+        const GFloor& fl = nav_floor(g, floor, "hmsg_graph_nav_grid");
+        hmsg_nav_grid_device("hmsg_graph_nav_grid", cell_size, (const double*)g->h->pts.p, (long long)g->h->V, fl.f.y_lo, fl.f.y_hi, pcd_min, pcd_max,
+                             grid);
+    });
+}
+int hmsg_graph_nav_floor_maps(hmsg_graph_t* g, int32_t floor, const hmsg_nav_params* prm, int32_t n_poses, const double* poses,
+                              hmsg_nav_maps* out) {
+    if (!g || !prm || !out) return HMSG_ERR_INVALID;
+    return hmsg_boundary(&g->err, -1, [&] {
+        const GFloor& fl = nav_floor(g, floor, "hmsg_graph_nav_floor_maps");
+        hmsg_nav_maps_device("hmsg_graph_nav_floor_maps", *prm, (const double*)g->h->pts.p, (const double*)g->h->cols.p, (long long)g->h->V, fl.f.y_lo,
+                             fl.f.y_hi, fl.f.zero_level, n_poses, poses, out);
+    });
+}
+
 /* save_hmsg_graph (graph.py:1801-1824) in the reference layout: <dir>/floors, rooms, objects, views */
 int hmsg_save(hmsg_graph_t* g, const char* dir) {
     if (!g || !dir) return HMSG_ERR_INVALID;

@@ -1314,6 +1314,41 @@ class Graph:
         if save_path is not None:
             self.save_hmsg_graph(os.path.join(save_path, "graph"))
 
+    # ------------------------------------------------------------------ N6: graph.py:2078-2127
+    def create_nav_graph(self, nav_dir=None, poses_list=None):
+        """A navigation graph per floor, the floors joined where the lower one has stairs: <save_path>/graph/nav_graph/
+        sparse_voronoi_graph.json (each floor in turn, as the reference overwrites it) and global_nav_graph_graph.json.  A floor's maps
+        are made on the device (holoagent_amd/nav_graph.py) from the floor's slab of the resident map with the map's colours, which
+        never leaves HBM (hmsg_map_nav_floor_maps), or from floor.pcd where there is no scene.  nav_dir / poses_list: instead of cfg.main.save_path and the dataset's poses."""
+        from .nav_graph import NavigationGraph
+        if nav_dir is None:
+            nav_dir = os.path.join(_get(self.cfg, "main.save_path"), "graph", "nav_graph")
+        os.makedirs(nav_dir, exist_ok=True)
+        if poses_list is None:
+            skip = int(_get(self.cfg, "pipeline.skip_frames", 1))
+            poses_list = [np.asarray(self.dataset[i][2], np.float64) for i in range(0, len(self.dataset), skip)]
+        from .nav_graph import SceneSlab
+        last, global_voronoi = None, None
+        for floor_id, floor in enumerate(self.floors):
+            crop = getattr(floor, "_crop", None)
+            # a storey of the resident map stays in HBM: the device stage selects its slab itself
+            cloud = SceneSlab(self.scene, crop[0], crop[1]) if crop is not None and self.scene is not None else floor.pcd
+            nav = NavigationGraph(cloud, cell_size=0.03, lib_=self.L)
+            upper = self.floors[floor_id + 1].floor_zero_level if floor_id + 1 < len(self.floors) else None
+            floor_poses = nav.get_floor_poses(cloud, poses_list, upper)
+            stairs = nav.get_stairs_graph_with_poses_v2(floor, floor_id, poses_list, nav_dir)
+            graph = nav.get_floor_graph(floor, floor_poses, nav_dir)
+            if stairs is not None:
+                graph = nav.connect_stairs_and_floor_graphs(stairs, graph, nav_dir)
+            NavigationGraph.save_voronoi_graph(graph, nav_dir, "sparse_voronoi")
+            if last is not None and last.has_stairs:
+                global_voronoi = nav.connect_voronoi_graphs(last.sparse_floor_voronoi, nav.sparse_floor_voronoi)
+            last = nav
+        if global_voronoi is None:
+            global_voronoi = last.sparse_floor_voronoi
+        NavigationGraph.save_voronoi_graph(global_voronoi, nav_dir, "global_nav_graph")
+        return global_voronoi
+
     # ------------------------------------------------------------------ A11: graph.py:1752-1775
     def create_graph_new(self):
         """Building(0) - Floor - Room - Object, Room - View, View - Object.  As in the reference, `room.room_id ==

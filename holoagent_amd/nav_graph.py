@@ -1,0 +1,287 @@
+"""A floor's navigation graph (the reference's graph/navigation_graph.py NavigationGraph): the image half on the device
+(include/hmsg.h: hmsg_nav_floor_maps, or hmsg_map_nav_floor_maps for a SceneSlab of a resident map -- obstacle map, free map, its main region, the boundary cells in row-major order, the
+top-down image), the graph half on the host with the same scipy.spatial.Voronoi call the reference makes.  Given an identical,
+identically ordered boundary list Qhull numbers vertices and ridges identically, so nodes, `pos`, edges and `dist` come out in the
+reference's order.
+
+What is here: the grid (to_grid / to_world), get_floor_poses, the maps (get_main_free_map, get_poses_region, get_top_down_rgb_map,
+create_occupancy_grid's result as `map`), get_voronoi_graph, sparsify_graph, trim_graph, get_stairs_graph_with_poses_v2,
+get_floor_graph, connect_voronoi_graphs, connect_stairs_and_floor_graphs and save_voronoi_graph: what Graph.create_nav_graph
+calls.  The stairs graph and sparsify_graph are host code on a few hundred poses (numpy, scipy.signal, networkx).  The debug
+drawings and histogram plots are not reproduced; the map PNGs are written with Pillow when a directory is given.  Out of scope
+(DESIGN.md): get_height_map, compute_sdf and the older get_stairs_graph* variants.  tests/golden/navgraph.npz holds what the
+reference's own class gives on two scenes; tests/test_navgraph_golden.py compares everything exactly."""
+import json
+import os
+
+import numpy as np
+
+from . import _lib
+
+
+def _cloud(floor_pcd):
+    """(points [n, 3], colors [n, 3] or None) of an Open3D-like cloud, a (points, colors) pair or a bare array"""
+    if hasattr(floor_pcd, "points"):
+        pts, cols = floor_pcd.points, getattr(floor_pcd, "colors", None)
+    elif isinstance(floor_pcd, (tuple, list)) and len(floor_pcd) == 2:
+        pts, cols = floor_pcd
+    else:
+        pts, cols = floor_pcd, None
+    on_dev = hasattr(pts, "data_ptr") and getattr(pts, "is_cuda", False)
+    if not on_dev:
+        pts = np.ascontiguousarray(np.asarray(pts, np.float64).reshape(-1, 3))
+        cols = None if cols is None or len(cols) == 0 else np.ascontiguousarray(np.asarray(cols, np.float64).reshape(-1, 3))
+    return pts, cols
+
+
+class SceneSlab:
+    """a storey as it lies in HBM: the points of a resident scene's map with y_lo <= y <= y_hi and their colours (what
+    Scene.segment_floors returns for it).  NavigationGraph takes it in place of a cloud; nothing of it goes to the host."""
+
+    def __init__(self, scene, y_lo, y_hi):
+        self.scene, self.y_lo, self.y_hi = scene, float(y_lo), float(y_hi)
+
+
+class NavigationGraph:
+    def __init__(self, floor_pcd, cell_size, lib_=None, device_id=0):
+        self.L = lib_ or _lib.lib()
+        self.device_id = int(device_id)
+        self.cell_size = cell_size
+        self.slab = floor_pcd if isinstance(floor_pcd, SceneSlab) else None
+        if self.slab is not None:
+            self.points = self.colors = None
+            self.pcd_min, self.pcd_max, (gx, gz) = self.slab.scene.nav_grid(self.slab.y_lo, self.slab.y_hi, cell_size)
+        else:
+            self.points, self.colors = _cloud(floor_pcd)
+            self.pcd_min, self.pcd_max, (gx, gz) = _lib.nav_grid(self.points, cell_size, self.device_id, self.L)
+        self.grid_size = np.array([gx, gz], np.int32)
+        self.has_stairs = False
+        self.maps = None
+        self.map = None
+        self.top_down = None
+        self.sparse_floor_voronoi = None
+
+    # ---- the grid
+    def to_grid(self, world_coords):
+        return np.int32((world_coords - self.pcd_min) / self.cell_size)
+
+    def to_world(self, grid_coords):
+        return grid_coords * self.cell_size + self.pcd_min
+
+    def get_floor_poses(self, floor, poses_list, upper_floor_min_height=None, camera_height=0.8):
+        """the poses whose camera, lowered by camera_height, lies inside the floor's height range (or below the next floor's start).
+        The floor's cloud is this object's: its lowest and highest y are the bounds the device call returned."""
+        lo = self.pcd_min[1]
+        hi = upper_floor_min_height if upper_floor_min_height is not None else self.pcd_max[1]
+        return [p for p in poses_list if lo <= p[1, 3] - camera_height < hi]
+
+    # ---- the image half: one device call, kept for all the map getters
+    def floor_maps(self, floor_info, floor_poses_list, **params):
+        poses = np.asarray(floor_poses_list, np.float64).reshape(-1, 4, 4)
+        if self.slab is not None:
+            self.maps = self.slab.scene.nav_floor_maps(self.slab.y_lo, self.slab.y_hi, float(floor_info["floor_zero_level"]), poses,
+                                                       cell_size=self.cell_size, **params)
+            self.map = self.maps["obstacle_map"]
+            return self.maps
+        self.maps = _lib.nav_floor_maps(self.points, self.colors, float(floor_info["floor_zero_level"]), poses, lib_=self.L,
+                                        device_id=self.device_id, cell_size=self.cell_size, **params)
+        self.map = self.maps["obstacle_map"]
+        return self.maps
+
+    @staticmethod
+    def _png(floor_dir, name, img):
+        if floor_dir is None:
+            return
+        from PIL import Image
+        os.makedirs(floor_dir, exist_ok=True)
+        a = img.cpu().numpy() if hasattr(img, "cpu") else np.asarray(img)
+        Image.fromarray(a if a.ndim == 2 else np.ascontiguousarray(a[:, :, ::-1])).save(os.path.join(floor_dir, name))
+
+    def get_main_free_map(self, floor_pcd=None, floor_info=None, floor_dir=None, floor_poses_list=None, save=True, **params):
+        m = self.floor_maps(floor_info, floor_poses_list, **params)
+        if save and floor_dir is not None:
+            for name, key in (("poses_region_map.png", "poses_map"), ("floor_region.png", "region_map"), ("floor_free.png", "free_map"),
+                              ("floor_free_main.png", "main_free_map")):
+                self._png(floor_dir, name, m[key] * 255)
+            obst = m["obstacle_map"].cpu().numpy() if hasattr(m["obstacle_map"], "cpu") else m["obstacle_map"]
+            self._png(floor_dir, "floor_obstacles.png", obst.astype(np.uint8) * 255)
+        return m["main_free_map"]
+
+    def get_poses_region(self, poses_list=None, floor_dir=None, radius=0.5, save=True, cluster=True):
+        assert self.maps is not None, "get_main_free_map makes the maps"
+        return self.maps["poses_map"]
+
+    def get_top_down_rgb_map(self, floor_pcd=None, floor_info=None, floor_dir=None):
+        assert self.maps is not None and "top_down_bgr" in self.maps, "get_main_free_map makes the maps; the cloud needs colours"
+        self._png(floor_dir, "top_down_rgb.png", self.maps["top_down_bgr"])
+        return self.maps["top_down_bgr"]
+
+    # ---- the graph half
+    def get_voronoi_graph(self, main_free_map, map_rgb=None, floor_dir=None, floor_id=0, name="", height_map=None, boundary_rc=None):
+        """The Voronoi graph of the boundary cells, filtered as the reference filters it: a ridge is kept when both its vertices are
+        finite, inside the image and on a cell of main_free_map.  boundary_rc: the device's list (default: this object's, when
+        main_free_map is the map it came with; otherwise the cells are found on the host)."""
+        import networkx as nx
+        from scipy.spatial import Voronoi
+        main = main_free_map.cpu().numpy() if hasattr(main_free_map, "cpu") else np.asarray(main_free_map)
+        if boundary_rc is None and self.maps is not None and main_free_map is self.maps["main_free_map"]:
+            boundary_rc = self.maps["boundary_rc"]
+        if boundary_rc is None:
+            from scipy.ndimage import binary_erosion
+            boundary_rc = np.argwhere(main.astype(bool) & ~binary_erosion(main.astype(bool)))
+        elif hasattr(boundary_rc, "cpu"):
+            boundary_rc = boundary_rc.cpu().numpy()
+        vor = Voronoi(np.asarray(boundary_rc).astype(np.int64))
+        H, W = main.shape[:2]
+        if height_map is None:
+            height_map = np.ones((H, W), np.uint8) * self.pcd_min[1]
+        g = nx.Graph()
+
+        def node(v):
+            key = (v[0], v[1], floor_id)
+            if key not in g.nodes:
+                g.add_node(key, pos=(v[1] * self.cell_size + self.pcd_min[0], height_map[int(v[0]), int(v[1])],
+                                     v[0] * self.cell_size + self.pcd_min[2]), floor_id=floor_id)
+            return key
+        for ridge in vor.ridge_vertices:
+            ridge = np.asarray(ridge)
+            if np.any(ridge < 0):
+                continue
+            src, tar = vor.vertices[ridge]
+            if not (0 <= src[0] < H and 0 <= src[1] < W and 0 <= tar[0] < H and 0 <= tar[1] < W):
+                continue
+            if main[int(src[0]), int(src[1])] == 0 or main[int(tar[0]), int(tar[1])] == 0:
+                continue
+            a, b = node(src), node(tar)
+            if a not in g[b]:
+                g.add_edge(a, b, dist=np.linalg.norm(src - tar))
+        return g
+
+    def sparsify_graph(self, floor_graph, resampling_dist=0.4):
+        """The nodes of degree other than 2 stay; every pair of them whose shortest path runs over degree-2 nodes only is joined
+        directly, and the path between them is re-sampled every resampling_dist metres (its dist, in cells, times cell_size).
+        Edges are added in the order the reference adds them.  A graph of fewer than 10 nodes comes back as a copy."""
+        import copy
+        import networkx as nx
+        graph = copy.deepcopy(floor_graph)
+        if len(graph.nodes) < 10:
+            return graph
+        out = nx.Graph()
+        for n in graph.nodes:
+            if graph.degree(n) != 2:
+                out.add_node(n, pos=graph.nodes[n]["pos"], floor_id=graph.nodes[n]["floor_id"])
+        kept, kept_set = list(out.nodes), set(out.nodes)
+        paths = dict(nx.all_pairs_dijkstra_path(graph, weight="dist"))
+        todo = []
+        for i, a in enumerate(kept):
+            for b in kept[i + 1:]:
+                try:
+                    path = paths[a][b]
+                    if any(graph.degree(n) > 2 for n in path[1:-1]):
+                        continue
+                    todo.append((path[0], path[-1], np.linalg.norm(np.array(path[0]) - np.array(path[-1]))))
+                    steps = [graph.edges[path[k], path[k + 1]]["dist"] for k in range(len(path) - 1)]
+                    if len(path) and not set(path[1:-1]) & kept_set:
+                        run, prev = 0, path[0]
+                        for k, n in enumerate(path[1:-1]):
+                            run += steps[k]
+                            if run * self.cell_size > resampling_dist:
+                                todo.append((prev, n, np.linalg.norm(np.array(prev) - np.array(n))))
+                                prev, run = n, 0
+                        todo.append((prev, path[-1], np.linalg.norm(np.array(prev) - np.array(path[-1]))))
+                except BaseException:                         # (no path between the two, or ids that do not subtract: the pair is skipped)
+                    continue
+        for a, b, d in todo:
+            for n in (a, b):
+                if n not in out.nodes:
+                    out.add_node(n, pos=graph.nodes[n]["pos"], floor_id=graph.nodes[n]["floor_id"])
+            out.add_edge(a, b, dist=d)
+        self.floor_graph = out
+        return out
+
+    def trim_graph(self, graph, trim_deg=1):
+        """nodes of degree trim_deg removed, round after round, until none is left"""
+        import copy
+        graph = copy.deepcopy(graph)
+        while True:
+            ends = [n for n in list(graph.nodes) if graph.degree(n) == trim_deg]
+            if not ends:
+                return graph
+            graph.remove_nodes_from(ends)
+
+    def get_stairs_graph_with_poses_v2(self, floor, floor_id, poses_list, floor_dir=None):
+        """The stairs above floor `floor_id` as the chain of camera positions between two storeys: the storeys are the peaks of the
+        histogram (100 bins) of the pose heights less 1.5 m that reach 0.3 of the highest bin; the track (reversed when it comes
+        down) is cut from where it last leaves the lower peak's bin to where it first passes the upper peak, 5 poses added in
+        front and 20 behind; the chain is sparsified.  No upper peak: an empty graph and has_stairs False."""
+        import networkx as nx
+        from scipy.signal import find_peaks
+        zero = floor.floor_zero_level
+        heights = np.array([p[1, 3] - 1.5 for p in poses_list])
+        counts, edges = np.histogram(heights, bins=100)
+        padded = np.concatenate([[np.min(counts)], counts, [np.min(counts)]])
+        peaks = find_peaks(padded, height=0.3 * np.max(counts))[0] - 1
+        if floor_id >= len(peaks) - 1:
+            self.has_stairs = False
+            return nx.Graph()
+        h_lo, h_hi = edges[peaks[int(floor_id)] + 1], edges[peaks[int(floor_id) + 1]]
+        if heights[0] > heights[-1]:
+            heights, poses_list = heights[::-1], poses_list[::-1]
+        first_low = 0
+        if heights[0] > h_lo:
+            first_low = next((i for i, h in enumerate(heights) if h <= h_lo), 0)
+        st = next((i for i, h in enumerate(heights) if h > h_lo and i > first_low), None)
+        ed = next((i for i, h in enumerate(heights) if h > h_hi), None)
+        for i in range(st, ed):
+            if heights[i] < h_lo:
+                st = i
+        st, ed = np.max([st - 5, 0]), ed + 20
+        track = [p[:3, 3] for p in poses_list[st:ed]]
+        if not track:
+            self.has_stairs = False
+            return nx.Graph()
+        lowest = np.min([p[1] for p in track])
+        chain = nx.Graph()
+        last = None
+        for p in track:
+            cell = (p - self.pcd_min) / self.cell_size
+            chain.add_node((cell[2], cell[0], floor_id), pos=(p[0], p[1] - lowest + zero, p[2]), floor_id=floor_id)
+            if last is not None:
+                chain.add_edge((cell[2], cell[0], floor_id), (last[2], last[0], floor_id), dist=np.linalg.norm(cell - last))
+            last = cell
+        sparse = self.sparsify_graph(chain, resampling_dist=0.4)
+        self.has_stairs = True
+        return sparse
+
+    def get_floor_graph(self, floor, floor_poses_list, floor_dir=None, **params):
+        info = {"floor_zero_level": floor.floor_zero_level, "floor_height": getattr(floor, "floor_height", None)}
+        main = self.get_main_free_map(None, info, floor_dir, floor_poses_list, **params)
+        self.top_down = self.get_top_down_rgb_map(None, info, floor_dir) if "top_down_bgr" in self.maps else None
+        self.sparse_floor_voronoi = self.get_voronoi_graph(main, self.top_down, floor_dir, int(floor.floor_id))
+        return self.sparse_floor_voronoi
+
+    def connect_voronoi_graphs(self, src_graph, tar_graph, floor_dir=None):
+        """src_graph joined to tar_graph by one edge between the closest pair (any node of src, a node of tar of degree > 1)"""
+        import networkx as nx
+        from scipy.spatial.distance import cdist
+        tar_nodes, src_nodes = list(tar_graph.nodes), list(src_graph.nodes)
+        ids = [i for i, n in enumerate(tar_nodes) if tar_graph.degree(n) > 1]
+        d = cdist(np.array([src_graph.nodes[n]["pos"] for n in src_nodes]), np.array([tar_graph.nodes[tar_nodes[i]]["pos"] for i in ids]))
+        row, col = np.unravel_index(np.argmin(d), d.shape)
+        s, t = src_nodes[row], tar_nodes[ids[col]]
+        out = nx.compose(tar_graph, src_graph)
+        out.add_edge(s, t, dist=np.linalg.norm(np.array(s[:2]) - np.array(t[:2])))
+        return out
+
+    def connect_stairs_and_floor_graphs(self, sparse_stairs_voronoi, sparse_floor_voronoi, floor_dir=None):
+        if not self.has_stairs:
+            return sparse_floor_voronoi
+        self.sparse_floor_voronoi = self.connect_voronoi_graphs(sparse_stairs_voronoi, sparse_floor_voronoi, floor_dir)
+        return self.sparse_floor_voronoi
+
+    @staticmethod
+    def save_voronoi_graph(graph, floor_dir, name):
+        """<floor_dir>/<name>_graph.json: networkx's node-link layout with the edges under "links", indent 4"""
+        import networkx as nx
+        with open(os.path.join(floor_dir, f"{name}_graph.json"), "w") as f:
+            json.dump(nx.node_link_data(graph, edges="links"), f, indent=4)

@@ -1186,6 +1186,88 @@ int hmsg_rematch_in_views(hmsg_index_t* ix, int32_t Q, const float* T, const int
 int hmsg_points_view_depths(int32_t device_id, int64_t n_pairs, const int64_t* pts_off, const double* pts, const double* pose_inv, const int32_t* wh,
                             const double* K, double min_visible_ratio, double max_depth, double* avg_z_front, uint8_t* visible, double* mean_depth);
 
+/* ---- N6: the image half of a floor's navigation graph (graph/navigation_graph.py NavigationGraph; csrc/hmsg_navmap.hip,
+ * csrc/hmsg_nav_host.h): a storey's cloud -> the grid maps of get_main_free_map, the boundary cells get_voronoi_graph hands to
+ * scipy.spatial.Voronoi, and the top-down image of get_top_down_rgb_map.  Images are [grid[1] rows (z)][grid[0] columns (x)],
+ * row-major.  Every output is exact (integer work; the obstacle map is a whole number of sixteenths).  The rules:
+ *   1. cell of a coordinate: floor((v - pcd_min) / cell_size) in float64 (subtract, then divide); pcd_min / pcd_max are the
+ *      bounds of ALL points of the storey, grid = int32(ceil((pcd_max - pcd_min) / cell_size + 1)) for x and z (:57-65);
+ *   2. obstacle points: zero_level + obstacle_lo < y < zero_level + obstacle_hi (:163-167); region points and the points of the
+ *      top-down image: y < zero_level + region_max (:193-195, :462); the sums are formed in float64 first;
+ *   3. create_occupancy_grid (:230-240): cv2.dilate by a dilation x dilation box (the window clipped at the border), then
+ *      cv2.GaussianBlur 3 x 3 = (1, 2, 1) x (1, 2, 1) / 16 in float32, the border reflected without repeating the edge.
+ *      obstacle_map is that float32 image of the obstacle cells (NavigationGraph.map), region_map = (that of the region cells) > 0;
+ *   4. poses_map (get_poses_region :348-377): sklearn's DBSCAN(eps = pose_eps, min_samples = pose_min_samples) on the poses'
+ *      heights (pose[1][3]; neighbours at distance <= eps, clusters numbered by their first core sample, noise -1), the most
+ *      frequent label (of equally frequent ones the smallest: noise wins a tie), the mean height of that label (numpy's pairwise
+ *      sum), keep |h - mean| < pose_eps, then h < min + pose_eps; cell = int32((xz - pcd_min) / cell_size) truncated toward zero;
+ *      a filled cv2.circle of radius int(pose_radius / cell_size) round each, clipped to the image.  The circle is OpenCV's
+ *      midpoint walk restated without an OpenCV to compare with;
+ *   5. free_map = (region_map or poses_map) and obstacle_map == 0 (:414-421);
+ *   6. get_largest_region (:316-322): 8-connected components of free_map, labels in raster order of each component's first
+ *      cell, label 0 the background.  region_rule 0 (the reference): the label SECOND in descending order of area, the
+ *      background counted -- which is the background itself when the free region is the larger of the two; region_rule 1: the
+ *      largest component.  Of equal areas the larger label comes first (np.argsort leaves it open).  main_free_map = (labels ==
+ *      main_label); main_area its cells; n_regions = labels, the background included;
+ *   7. boundary_rc: the cells of main_free_map with a 4-neighbour outside it (outside the image counts), as (row, col) in
+ *      row-major order = np.argwhere(main - binary_erosion(main)) (:511-521): Qhull numbers vertices and ridges by input order;
+ *   8. top_down_bgr (:458-481; only with colours): per cell the point with the greatest height cell int32((y - pcd_min[1]) /
+ *      cell_size) wins, of equal ones the lowest index; its colour is uint8(c * 255) truncated (c in [0, 1]); empty cells are 0;
+ *      scipy.ndimage.median_filter(size = 3) over the (rows, cols, 3) array, the channel axis included, mode reflect; stored B, G, R.
+ * Any output pointer of hmsg_nav_maps may be NULL (not wanted) and may be host or device memory, as may xyz, rgb and poses.
+ * Errors (HMSG_ERR_INVALID unless said): a null prm / xyz / out; no points; a coordinate of any point of the cloud that is not
+ * finite (NaN or infinite; counted on the device, outside a graph's slab too); no pose (n_poses == 0), a pose height pose[1][3] that
+ * is not finite (a pose's x / z may be anything: its cell is clamped far outside the grid), or none left by rule 4 (the reference
+ * raises); no free cell (fewer than two labels); boundary_capacity < n_boundary (the maps
+ * are written, the list is not, n_boundary says what is needed); HMSG_ERR_UNSUPPORTED for a blur other than 3 or 0 and for a
+ * grid of 2^28 cells or more.  pcd_min, pcd_max and grid are set as soon as the cloud has been read. */
+typedef struct hmsg_nav_params {
+    double  cell_size;          /* 0.03 m */
+    double  obstacle_lo;        /* 1.4 */
+    double  obstacle_hi;        /* 2.5 */
+    double  region_max;         /* 1.5 */
+    double  pose_radius;        /* 0.5 m */
+    double  pose_eps;           /* 0.1: DBSCAN's eps and both height filters */
+    int32_t dilation;           /* 5; 0 = none */
+    int32_t blur;               /* 3; 0 = none */
+    int32_t pose_min_samples;   /* 5 */
+    int32_t region_rule;        /* 0 = the reference's second-largest label, 1 = the largest component */
+} hmsg_nav_params;
+typedef struct hmsg_nav_maps {
+    float*   obstacle_map;      /* f32 [H][W] */
+    uint8_t* region_map;        /* u8 [H][W], 0/1, like the next three */
+    uint8_t* poses_map;
+    uint8_t* free_map;
+    uint8_t* main_free_map;
+    uint8_t* top_down_bgr;      /* u8 [H][W][3] */
+    int32_t* boundary_rc;       /* i32 [boundary_capacity][2] */
+    int64_t  boundary_capacity;
+    /* out */
+    int64_t  n_boundary;
+    int64_t  main_area;
+    int32_t  n_regions;
+    int32_t  main_label;
+    int32_t  grid[2];           /* columns (x), rows (z) */
+    double   pcd_min[3], pcd_max[3];
+} hmsg_nav_maps;
+void hmsg_nav_default_params(hmsg_nav_params* p);
+/* the size call: bounds and grid of xyz f64 [n][3] (pcd_min, pcd_max: f64 [3], optional; grid: i32 [2]; host memory) */
+int hmsg_nav_grid(int32_t device_id, double cell_size, int64_t n, const double* xyz, double* pcd_min, double* pcd_max, int32_t* grid);
+/* the work call: rgb f64 [n][3] or NULL (no top-down image), poses f64 [n_poses][16] (row-major camera-to-world 4 x 4) */
+int hmsg_nav_floor_maps(int32_t device_id, const hmsg_nav_params* prm, int64_t n, const double* xyz, const double* rgb, double zero_level,
+                        int32_t n_poses, const double* poses, hmsg_nav_maps* out);
+/* The same stage on storey `floor` of a built graph: the map points with y_lo <= y <= y_hi in map order with their colours (the
+ * slab hmsg_save writes as floors/<f>.ply), selected on the device, zero_level the floor's own.  A graph read by hmsg_load has no
+ * cloud in HBM and is refused (HMSG_ERR_INVALID; its caller gives hmsg_read_ply's points to hmsg_nav_floor_maps). */
+int hmsg_graph_nav_grid(hmsg_graph_t* g, int32_t floor, double cell_size, double* pcd_min, double* pcd_max, int32_t* grid);
+int hmsg_graph_nav_floor_maps(hmsg_graph_t* g, int32_t floor, const hmsg_nav_params* prm, int32_t n_poses, const double* poses,
+                              hmsg_nav_maps* out);
+/* ... and on a slab y_lo <= y <= y_hi of a scene's finalised map (what hmsg_segment_floors returns for a storey), for callers that
+ * hold the scene and no graph handle; zero_level is theirs to give (hmsg_floor.zero_level). */
+int hmsg_map_nav_grid(hmsg_t* h, double y_lo, double y_hi, double cell_size, double* pcd_min, double* pcd_max, int32_t* grid);
+int hmsg_map_nav_floor_maps(hmsg_t* h, double y_lo, double y_hi, double zero_level, const hmsg_nav_params* prm, int32_t n_poses,
+                            const double* poses, hmsg_nav_maps* out);
+
 
 #ifdef __cplusplus
 }

@@ -121,6 +121,8 @@ int hmsg_test_graph_early_objects(const hmsg_graph_t* g, const hmsg_t* h, int32_
  * flags each) of the holes and of the islands pass (0: the pass did not run) and the HIP-event time of the statistics kernel's
  * launch over the logits.  Any pointer may be NULL. */
 int hmsg_test_sam_post_last(int32_t* rounds_holes, int32_t* rounds_islands, double* stats_ms);
+/* the labelling rounds (four scans each) of this thread's last hmsg_*nav_floor_maps call */
+int hmsg_test_nav_last(int32_t* label_rounds);
 
 /* measurement hook: the queries that the process's last hmsg_knn_labels call (hmsg_evaluate_semseg's included) finished by scan
  * (phase 2) -- all of them under HMSG_DEBUG_KNN_BRUTE=1. */
