@@ -98,6 +98,16 @@ class HmsgNavMaps(C.Structure):         # include/hmsg.h: hmsg_nav_maps
                 ("grid", C.c_int32 * 2), ("pcd_min", C.c_double * 3), ("pcd_max", C.c_double * 3)]
 
 
+class HmsgRouteParams(C.Structure):     # include/hmsg.h: hmsg_route_params
+    _fields_ = [("w_straight", C.c_int32), ("w_diag", C.c_int32), ("min_clearance", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class HmsgNavRoutes(C.Structure):       # include/hmsg.h: hmsg_nav_routes
+    _fields_ = [("goal_cell", C.c_void_p), ("goal_d2", C.c_void_p), ("goal_dist", C.c_void_p), ("path_off", C.c_void_p),
+                ("path_rc", C.c_void_p), ("path_capacity", C.c_int64), ("field", C.c_void_p), ("passable", C.c_void_p),
+                ("n_path_cells", C.c_int64), ("start_d2", C.c_int64), ("start_cell", C.c_int32 * 2)]
+
+
 class HmsgError(RuntimeError):
     pass
 
@@ -138,6 +148,12 @@ _SIGS = {
     "hmsg_map_nav_floor_maps": (C.c_int, [_P, C.c_double, C.c_double, C.c_double, _P, C.c_int32, _P, _P]),
     "hmsg_graph_nav_grid": (C.c_int, [_P, C.c_int32, C.c_double, _P, _P, _P]),
     "hmsg_graph_nav_floor_maps": (C.c_int, [_P, C.c_int32, _P, C.c_int32, _P, _P]),
+    "hmsg_route_default_params": (None, [_P]),
+    "hmsg_nav_clearance": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    "hmsg_nav_distance_fields": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, _P, _P]),
+    "hmsg_nav_snap_cells": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P, _P, _P]),
+    "hmsg_nav_paths": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int64, _P, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "hmsg_nav_route": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int64, _P, _P]),
     "hmsg_get_frame_num_masks": (C.c_int32, [_P, C.c_int32]),
     "hmsg_fuse_frames": (C.c_int, [_P]),
     "hmsg_get_map_feats": (C.c_int, [_P, _P, _P]),
@@ -277,6 +293,7 @@ _SIGS = {
     "hmsg_test_graph_early_objects": (C.c_int, [_P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "hmsg_test_sam_post_last": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "hmsg_test_nav_last": (C.c_int, [C.POINTER(C.c_int32)]),
+    "hmsg_test_nav_route_last": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "hmsg_test_knn_last_phase2": (C.c_int64, []),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -2034,6 +2051,160 @@ def nav_floor_maps(points, colors, zero_level, poses, params=None, device_id=0, 
         if rc != 0:
             raise HmsgError(f"hmsg_nav_floor_maps failed ({rc}) (the message is on stderr)")
     return _nav_call(H, W, colors is not None, call, device=points.device if on_dev else None)
+
+
+# ---- N7: routes on a floor's free map (include/hmsg.h states the rules R1 to R6)
+NAV_UNREACHED = 2147483647
+
+
+def route_params(lib_: "HmsgLib | None" = None, **over):
+    """hmsg_route_params with the defaults (w_straight 5, w_diag 7, min_clearance 0), fields overridden by keyword"""
+    L = lib_ or lib()
+    p = HmsgRouteParams()
+    L.c.hmsg_route_default_params(C.byref(p))
+    for k, v in over.items():
+        if k not in ("w_straight", "w_diag", "min_clearance"):
+            raise HmsgError(f"unknown hmsg_route_params field {k}")
+        setattr(p, k, int(v))
+    return p
+
+
+def _is_dev(a):
+    return hasattr(a, "data_ptr") and getattr(a, "is_cuda", False)
+
+
+def _nav_image(a, np_dtype):
+    """a [rows, cols] image for the C ABI: a contiguous numpy array, or the device tensor as it is -> (array, rows, cols, device)"""
+    if _is_dev(a):
+        import torch
+        assert a.dtype == getattr(torch, np.dtype(np_dtype).name) and a.dim() == 2, "a device image must have the ABI's dtype"
+        return a.contiguous(), int(a.shape[0]), int(a.shape[1]), a.device
+    a = np.ascontiguousarray(np.asarray(a, np_dtype))
+    assert a.ndim == 2
+    return a, int(a.shape[0]), int(a.shape[1]), None
+
+
+def _nav_cells(a):
+    """(row, col) pairs for the C ABI: int32 [n, 2], numpy or a device tensor"""
+    if _is_dev(a):
+        import torch
+        assert a.dtype == torch.int32
+        return a.reshape(-1, 2).contiguous()
+    a = np.asarray(a)
+    return np.ascontiguousarray(a.astype(np.int32).reshape(-1, 2)) if a.dtype != np.int32 else np.ascontiguousarray(a.reshape(-1, 2))
+
+
+def _nav_buf(device):
+    if device is not None:
+        import torch
+        return lambda shape, np_dtype: torch.empty(shape, dtype=getattr(torch, np.dtype(np_dtype).name), device=device)
+    return lambda shape, np_dtype: np.empty(shape, np_dtype)
+
+
+def _nav_dev_id(device, device_id):
+    return (device.index or 0) if device is not None else int(device_id)
+
+
+def _nav_ck(rc, fn):
+    if rc != 0:
+        raise HmsgError(f"{fn} failed ({rc}) (the message is on stderr)")
+
+
+def nav_clearance(mask, params=None, device_id=0, lib_: "HmsgLib | None" = None, **over):
+    """R3: the clearance of a mask u8 [rows, cols] (numpy in: numpy out; a device tensor in: a device tensor out) -> int32 [rows, cols]"""
+    L = lib_ or lib()
+    prm = params if params is not None else route_params(L, **over)
+    mask, H, W, dev = _nav_image(mask, np.uint8)
+    out = _nav_buf(dev)((H, W), np.int32)
+    _nav_ck(L.c.hmsg_nav_clearance(_nav_dev_id(dev, device_id), H, W, _ptr(mask), C.byref(prm), _ptr(out)), "hmsg_nav_clearance")
+    return out
+
+
+def nav_distance_fields(passable, source_sets, params=None, device_id=0, lib_: "HmsgLib | None" = None, **over):
+    """R2: one field per source set.  passable u8 [rows, cols]; source_sets: a list of (row, col) arrays [k, 2], or the pair
+    (src_off int64 [n + 1], src_rc int32 [m, 2]) -> (fields int32 [n, rows, cols], n_reached int64 [n])"""
+    L = lib_ or lib()
+    prm = params if params is not None else route_params(L, **over)
+    passable, H, W, dev = _nav_image(passable, np.uint8)
+    if isinstance(source_sets, tuple) and len(source_sets) == 2 and np.ndim(source_sets[0]) == 1:
+        off, rc = np.ascontiguousarray(np.asarray(source_sets[0], np.int64)), _nav_cells(source_sets[1])
+    else:
+        sets = [np.asarray(s_, np.int64).reshape(-1, 2) for s_ in source_sets]
+        off = np.concatenate([[0], np.cumsum([len(s_) for s_ in sets])]).astype(np.int64)
+        rc = _nav_cells(np.concatenate(sets) if sets else np.zeros((0, 2)))
+    n = len(off) - 1
+    buf = _nav_buf(dev)
+    fields, reached = buf((n, H, W), np.int32), buf((n,), np.int64)
+    _nav_ck(L.c.hmsg_nav_distance_fields(_nav_dev_id(dev, device_id), H, W, _ptr(passable), C.byref(prm), n, _ptr(off),
+                                         _ptr(rc) if len(rc) else None, _ptr(fields), _ptr(reached)), "hmsg_nav_distance_fields")
+    return fields, reached
+
+
+def nav_snap_cells(passable, targets_rc, field=None, device_id=0, lib_: "HmsgLib | None" = None):
+    """R4: the nearest candidate cell of every target -> (snapped int32 [n, 2], d2 int64 [n]); field: only reached cells are candidates"""
+    L = lib_ or lib()
+    passable, H, W, dev = _nav_image(passable, np.uint8)
+    if field is not None:
+        field, fh, fw, fdev = _nav_image(field, np.int32)
+        assert (fh, fw) == (H, W) and (fdev is None) == (dev is None)
+    t = _nav_cells(targets_rc)
+    n = int(t.shape[0])
+    buf = _nav_buf(dev)
+    snapped, d2 = buf((n, 2), np.int32), buf((n,), np.int64)
+    _nav_ck(L.c.hmsg_nav_snap_cells(_nav_dev_id(dev, device_id), H, W, _ptr(passable), _ptr(field), n, _ptr(t) if n else None,
+                                    _ptr(snapped) if n else None, _ptr(d2) if n else None), "hmsg_nav_snap_cells")
+    return snapped, d2
+
+
+def nav_paths(passable, field, goals_rc, params=None, device_id=0, lib_: "HmsgLib | None" = None, **over):
+    """R5: the cells of the way from the field's source to every goal -> (path_off int64 [n + 1], path_rc int32 [k, 2]).  The
+    first call counts, the second writes."""
+    L = lib_ or lib()
+    prm = params if params is not None else route_params(L, **over)
+    passable, H, W, dev = _nav_image(passable, np.uint8)
+    field, fh, fw, fdev = _nav_image(field, np.int32)
+    assert (fh, fw) == (H, W) and (fdev is None) == (dev is None)
+    g = _nav_cells(goals_rc)
+    n = int(g.shape[0])
+    buf = _nav_buf(dev)
+    off, need = buf((n + 1,), np.int64), C.c_int64(0)
+    args = (_nav_dev_id(dev, device_id), H, W, _ptr(passable), C.byref(prm), _ptr(field), n, _ptr(g) if n else None)
+    _nav_ck(L.c.hmsg_nav_paths(*args, _ptr(off), None, 0, C.byref(need)), "hmsg_nav_paths")
+    rc = buf((max(need.value, 1), 2), np.int32)
+    _nav_ck(L.c.hmsg_nav_paths(*args, _ptr(off), _ptr(rc), need.value, C.byref(need)), "hmsg_nav_paths")
+    return off, rc[: need.value]
+
+
+def nav_route(main_free_map, start_rc, goals_rc, params=None, device_id=0, lib_: "HmsgLib | None" = None, want_field=False, **over):
+    """hmsg_nav_route: the composition on one map -> dict(start_cell (row, col), start_d2, goal_cell int32 [n, 2], goal_d2 int64 [n],
+    goal_dist int32 [n], path_off int64 [n + 1], path_rc int32 [k, 2], passable u8 [rows, cols]; field int32 [rows, cols] with
+    want_field).  A device tensor in: device tensors out.  The path list is sized by a first guess and the call repeated once."""
+    L = lib_ or lib()
+    prm = params if params is not None else route_params(L, **over)
+    m, H, W, dev = _nav_image(main_free_map, np.uint8)
+    start = np.ascontiguousarray(np.asarray(start_rc, np.int64).reshape(2).astype(np.int32))
+    g = _nav_cells(goals_rc)
+    n = int(g.shape[0])
+    buf = _nav_buf(dev)
+    res = dict(goal_cell=buf((n, 2), np.int32), goal_d2=buf((n,), np.int64), goal_dist=buf((n,), np.int32), path_off=buf((n + 1,), np.int64),
+               passable=buf((H, W), np.uint8))
+    if want_field:
+        res["field"] = buf((H, W), np.int32)
+    out = HmsgNavRoutes()
+    cap = max(1, n) * 2 * (H + W)
+    for attempt in range(2):
+        rc = buf((max(cap, 1), 2), np.int32)
+        for k, v in res.items():
+            setattr(out, k, _ptr(v))
+        out.path_rc, out.path_capacity = _ptr(rc), cap
+        status = L.c.hmsg_nav_route(_nav_dev_id(dev, device_id), H, W, _ptr(m), C.byref(prm), _ptr(start), n, _ptr(g) if n else None, C.byref(out))
+        if status != 0 and attempt == 0 and out.n_path_cells > cap:
+            cap = int(out.n_path_cells)
+            continue
+        _nav_ck(status, "hmsg_nav_route")
+        break
+    res.update(path_rc=rc[: out.n_path_cells], start_cell=(int(out.start_cell[0]), int(out.start_cell[1])), start_d2=int(out.start_d2))
+    return res
 
 
 def _clip_params(L, size, f16, mean, std):

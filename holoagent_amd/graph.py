@@ -1349,6 +1349,87 @@ class Graph:
         NavigationGraph.save_voronoi_graph(global_voronoi, nav_dir, "global_nav_graph")
         return global_voronoi
 
+    # ------------------------------------------------------------------ N7: routes on a storey's free map (no counterpart in the reference)
+    def _nav_poses(self, poses_list):
+        if poses_list is not None:
+            return poses_list
+        skip = int(_get(self.cfg, "pipeline.skip_frames", 1))
+        return [np.asarray(self.dataset[i][2], np.float64) for i in range(0, len(self.dataset), skip)]
+
+    def _floor_nav_grid(self, floor_id):
+        """the storey's NavigationGraph, its grid known and its maps not yet made; kept per storey"""
+        from .nav_graph import NavigationGraph, SceneSlab
+        cache = self.__dict__.setdefault("_floor_navs", {})
+        if floor_id not in cache:
+            floor = self.floors[floor_id]
+            crop = getattr(floor, "_crop", None)
+            cloud = SceneSlab(self.scene, crop[0], crop[1]) if crop is not None and self.scene is not None else floor.pcd
+            cache[floor_id] = NavigationGraph(cloud, cell_size=0.03, lib_=self.L)
+        return cache[floor_id]
+
+    def floor_navigation(self, floor_id, poses_list=None):
+        """The NavigationGraph of storey `floor_id` with its maps (get_main_free_map), made once and kept: from the floor's slab of
+        the resident map where there is a scene, from floor.pcd otherwise, with the poses create_nav_graph would give it.  It
+        writes nothing and leaves create_nav_graph as it is."""
+        floor_id = int(floor_id)
+        nav = self._floor_nav_grid(floor_id)
+        if nav.maps is None:
+            floor = self.floors[floor_id]
+            upper = self.floors[floor_id + 1].floor_zero_level if floor_id + 1 < len(self.floors) else None
+            floor_poses = nav.get_floor_poses(None, self._nav_poses(poses_list), upper)
+            info = {"floor_zero_level": floor.floor_zero_level, "floor_height": getattr(floor, "floor_height", None)}
+            nav.get_main_free_map(None, info, None, floor_poses, save=False)
+        return nav
+
+    def floor_of_pose(self, pose, camera_height=0.8):
+        """the storey whose height range holds the pose's camera lowered by camera_height, as get_floor_poses chooses; None: no storey"""
+        y = float(np.asarray(pose, np.float64)[1, 3]) - camera_height
+        for f in range(len(self.floors)):
+            nav = self._floor_nav_grid(f)
+            hi = self.floors[f + 1].floor_zero_level if f + 1 < len(self.floors) else nav.pcd_max[1]
+            if nav.pcd_min[1] <= y < hi:
+                return f
+        return None
+
+    def _floor_of_object(self, obj, centre):
+        """the index in self.floors of an object's storey: its room's floor where the room is known, else by the centre's height"""
+        by_id = {str(r.room_id): r for r in self.rooms}
+        room = by_id.get(str(getattr(obj, "room_id", None)))
+        if room is not None:
+            for f, floor in enumerate(self.floors):
+                if str(floor.floor_id) == str(room.floor_id):
+                    return f
+        zeros = [fl.floor_zero_level for fl in self.floors]
+        return max(0, int(np.searchsorted(zeros, centre[1], side="right")) - 1)
+
+    def route_to_objects(self, start_pose, objects, floor_id=None, min_clearance=0.25, poses_list=None):
+        """Where to stand for each object and how to get there (include/hmsg.h: hmsg_nav_route, on the device): `objects` are indices
+        into self.objects such as query_hmsg_object returns, Object nodes, or bare centres [3].  They are routed on the storey of
+        start_pose (a camera-to-world 4 x 4; floor_id overrides the choice) from the cell under the camera, the goal being the cell
+        under the object's centre snapped to the nearest cell that has min_clearance metres of free space round it and can be
+        reached.  Per object a dict: object (as given), point (world xyz to stand on), cell, reachable, length_m, snap_m, polyline
+        [k, 3], floor_id, reason (None, "other floor", "unreachable").  Routing across stairs is not done: an object of another
+        storey comes back as not reachable with reason "other floor"."""
+        pose = np.asarray(start_pose, np.float64)
+        f = int(floor_id) if floor_id is not None else self.floor_of_pose(pose)
+        if f is None:
+            raise ValueError("the start pose lies on no storey")
+        centres, floors = [], []
+        for o in objects:
+            node = self.objects[int(o)] if isinstance(o, (int, np.integer)) else o
+            c = np.asarray(node.pcd.get_center() if hasattr(node, "pcd") else node, np.float64).reshape(3)
+            centres.append(c)
+            floors.append(self._floor_of_object(node, c))
+        here = [k for k, fo in enumerate(floors) if fo == f]
+        out = [dict(object=o, point=None, cell=(-1, -1), reachable=False, length_m=None, snap_m=None, polyline=np.zeros((0, 3)),
+                    floor_id=floors[k], reason="other floor") for k, o in enumerate(objects)]
+        if here:
+            nav = self.floor_navigation(f, poses_list)
+            routes = nav.route(pose[:3, 3], np.array([centres[k] for k in here]), min_clearance_m=min_clearance)
+            for k, r in zip(here, routes):
+                out[k].update(r, reason=None if r["reachable"] else "unreachable")
+        return out
+
     # ------------------------------------------------------------------ A11: graph.py:1752-1775
     def create_graph_new(self):
         """Building(0) - Floor - Room - Object, Room - View, View - Object.  As in the reference, `room.room_id ==

@@ -10,7 +10,10 @@ get_floor_graph, connect_voronoi_graphs, connect_stairs_and_floor_graphs and sav
 calls.  The stairs graph and sparsify_graph are host code on a few hundred poses (numpy, scipy.signal, networkx).  The debug
 drawings and histogram plots are not reproduced; the map PNGs are written with Pillow when a directory is given.  Out of scope
 (DESIGN.md): get_height_map, compute_sdf and the older get_stairs_graph* variants.  tests/golden/navgraph.npz holds what the
-reference's own class gives on two scenes; tests/test_navgraph_golden.py compares everything exactly."""
+reference's own class gives on two scenes; tests/test_navgraph_golden.py compares everything exactly.
+
+Beyond the reference (include/hmsg.h, N7): clearance_map, distance_field and route work on the maps this object already holds --
+exact integer distance fields on main_free_map, the nearest reachable free cell of a goal and the cells of the way, on the device."""
 import json
 import os
 
@@ -115,6 +118,67 @@ class NavigationGraph:
         assert self.maps is not None and "top_down_bgr" in self.maps, "get_main_free_map makes the maps; the cloud needs colours"
         self._png(floor_dir, "top_down_rgb.png", self.maps["top_down_bgr"])
         return self.maps["top_down_bgr"]
+
+    # ---- routes on the main free map (include/hmsg.h, N7: the rules R1 to R6; no counterpart in the reference)
+    def cells_of(self, xyz_or_rc):
+        """(row, col) int32 [n, 2]: of world points [n, 3] by R6, floor((v - pcd_min) / cell_size) in float64 for z (row) and x
+        (col) -- not to_grid's truncation; [n, 2] arrays are cells already"""
+        a = np.asarray(xyz_or_rc.cpu() if hasattr(xyz_or_rc, "cpu") else xyz_or_rc)
+        a = a.reshape(-1, a.shape[-1]) if a.ndim > 1 else a.reshape(1, -1)
+        if a.shape[1] == 2:
+            return np.ascontiguousarray(a.astype(np.int32))
+        assert a.shape[1] == 3, "world points [n, 3] or cells [n, 2]"
+        a = a.astype(np.float64)
+        rc = np.stack([np.floor((a[:, 2] - self.pcd_min[2]) / self.cell_size), np.floor((a[:, 0] - self.pcd_min[0]) / self.cell_size)], axis=1)
+        return np.ascontiguousarray(np.clip(rc, -2.0 ** 31, 2.0 ** 31 - 1).astype(np.int32))
+
+    def clearance_units(self, min_clearance_m, w_straight=5):
+        return int(np.ceil(float(min_clearance_m) / self.cell_size * w_straight))
+
+    def clearance_map(self, **weights):
+        """R3 of main_free_map: int32 [rows, cols] in field units (metres = value * cell_size / w_straight), where the maps are"""
+        assert self.maps is not None, "get_main_free_map makes the maps"
+        return _lib.nav_clearance(self.maps["main_free_map"], lib_=self.L, device_id=self.device_id, **weights)
+
+    def passable_map(self, min_clearance_m=0.0, **weights):
+        """main_free_map where the clearance is at least min_clearance_m (0: the map itself)"""
+        assert self.maps is not None, "get_main_free_map makes the maps"
+        main = self.maps["main_free_map"]
+        units = self.clearance_units(min_clearance_m, weights.get("w_straight", 5))
+        if units <= 0:
+            return main
+        ok = (main != 0) & (self.clearance_map(**weights) >= units)
+        return ok.to(main.dtype) if hasattr(ok, "to") else ok.astype(np.uint8)
+
+    def distance_field(self, sources_xyz_or_rc, min_clearance_m=0.0, **weights):
+        """R2 from the given sources (world points [n, 3] or cells [n, 2]) on passable_map(min_clearance_m): int32 [rows, cols]"""
+        fields, _ = _lib.nav_distance_fields(self.passable_map(min_clearance_m, **weights), [self.cells_of(sources_xyz_or_rc)], lib_=self.L,
+                                             device_id=self.device_id, **weights)
+        return fields[0]
+
+    def route(self, start_xyz, goals_xyz, min_clearance_m=0.0, **weights):
+        """hmsg_nav_route from start_xyz to every goal (world points, or cells): per goal a dict with the stand-on `point` in world
+        coordinates (the centre of the snapped cell, y = pcd_min[1]), its `cell`, `reachable`, `length_m` (None when not
+        reachable), `snap_m` (how far the goal's cell is from the cell stood on) and the `polyline` [k, 3] from the start."""
+        assert self.maps is not None, "get_main_free_map makes the maps"
+        ws = int(weights.get("w_straight", 5))
+        r = _lib.nav_route(self.maps["main_free_map"], self.cells_of(start_xyz)[0], self.cells_of(goals_xyz), lib_=self.L, device_id=self.device_id,
+                           min_clearance=self.clearance_units(min_clearance_m, ws), **weights)
+        r = {k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in r.items()}
+        self.last_route = r
+
+        def world(rc):
+            rc = np.asarray(rc, np.float64).reshape(-1, 2)
+            return np.stack([(rc[:, 1] + 0.5) * self.cell_size + self.pcd_min[0], np.full(len(rc), self.pcd_min[1]),
+                             (rc[:, 0] + 0.5) * self.cell_size + self.pcd_min[2]], axis=1)
+        out = []
+        for k, cell in enumerate(r["goal_cell"]):
+            ok = bool(cell[0] >= 0 and r["goal_dist"][k] != _lib.NAV_UNREACHED)
+            out.append(dict(point=world(cell)[0] if ok else None, cell=(int(cell[0]), int(cell[1])), reachable=ok,
+                            length_m=float(r["goal_dist"][k]) * self.cell_size / ws if ok else None,
+                            snap_m=float(np.sqrt(float(r["goal_d2"][k]))) * self.cell_size if ok else None,
+                            polyline=world(r["path_rc"][r["path_off"][k]:r["path_off"][k + 1]])))
+        return out
 
     # ---- the graph half
     def get_voronoi_graph(self, main_free_map, map_rgb=None, floor_dir=None, floor_id=0, name="", height_map=None, boundary_rc=None):

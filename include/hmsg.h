@@ -1268,6 +1268,73 @@ int hmsg_map_nav_grid(hmsg_t* h, double y_lo, double y_hi, double cell_size, dou
 int hmsg_map_nav_floor_maps(hmsg_t* h, double y_lo, double y_hi, double zero_level, const hmsg_nav_params* prm, int32_t n_poses,
                             const double* poses, hmsg_nav_maps* out);
 
+/* ---- N7: routes on a floor's free map (csrc/hmsg_navroute.hip): exact distance fields of the grid graph, the clearance of a
+ * mask, the nearest candidate cell of a target, the cells of the way.  The reference has no such stage (navigation_graph.py:23,36
+ * imports skfmm and defines compute_sdf, which nothing calls; goal_pose_publisher.py:260-271 publishes an object's centre as it
+ * is), so the rules are this library's.  Images are [rows (z)][cols (x)], row-major, as in N6; cells are (row, col) int32 pairs
+ * like boundary_rc; a cell is passable / in the mask where its byte is not 0.  Every array may be host or device memory.  All
+ * of it is integer work: every output has one right answer.  The rules:
+ *  R1. Moves: the eight neighbours in this fixed order: N (-1, 0), S (+1, 0), W (0, -1), E (0, +1), NW (-1, -1), NE (-1, +1),
+ *      SW (+1, -1), SE (+1, +1).  A straight move costs w_straight, a diagonal one w_diag (5 and 7: metres = value * cell_size
+ *      / 5).  A move is legal when both cells are passable; a diagonal move also needs both cells it squeezes between to be
+ *      passable (no corner cutting: [[1, 0], [0, 1]] is two islands).
+ *  R2. Field: field[c] = the least cost of a legal walk from any source cell of the set to c, int32.  HMSG_NAV_UNREACHED marks
+ *      every cell no walk reaches and every cell that is not passable.  A source on a cell that is not passable is no source;
+ *      an empty set gives an all-unreached field; duplicate sources are fine.  n_reached[s] counts the finite cells.
+ *  R3. Clearance: 0 outside the mask; inside, the least cost to the nearest cell not in the mask, every move allowed (no corner
+ *      rule, the walk may cross anything), cells outside the image counting as not in the mask: a full mask gives
+ *      w_straight * (1 + min(r, rows - 1 - r, c, cols - 1 - c)).
+ *  R4. Snap: for a target cell, the candidate minimising d2 = dr * dr + dc * dc (int64, the target's indices clamped to
+ *      [-2^20, 2^20] first); of equal d2 the smaller row-major index.  Candidates: the passable cells; with a field, the passable
+ *      cells whose field value is finite.  No candidate: cell (-1, -1) and d2 = -1.
+ *  R5. Path: from the field's source to a goal cell, both included.  From the goal, step to the first neighbour n in R1's order
+ *      such that the move is legal and field[n] + w == field[here]; stop at value 0; the cells are emitted reversed.  A goal
+ *      that is unreached, not passable or outside the image has an empty path -- and so has a goal from which some step finds
+ *      no such neighbour (a field that R2 did not make).
+ *  R6. The cell of a world coordinate is N6's rule 1, floor((v - pcd_min) / cell_size) in float64; the Python layer applies it.
+ * hmsg_nav_route is the composition and only that: passable = the mask where clearance >= min_clearance (min_clearance 0: the
+ * mask itself); the start is snapped with no field; one field is built from it; every goal is snapped among the reached cells;
+ * the paths are extracted to the snapped cells.  Any pointer of hmsg_nav_routes may be NULL.  A path list that is too short
+ * behaves as boundary_capacity does: everything else is written, the list is not, the count says what is needed
+ * (HMSG_ERR_INVALID).  path_off / path_rc of hmsg_nav_paths may be NULL (the count alone); d2 and n_reached may be NULL.  The
+ * structs themselves and n_needed are host memory; src_off and src_rc are read and checked by the host before anything runs.
+ * Refusals (HMSG_ERR_INVALID unless said): a null required pointer; rows or cols < 1; w_straight < 1 or w_diag < w_straight;
+ * min_clearance < 0; a decreasing src_off; a source with an index outside the image; HMSG_ERR_UNSUPPORTED when rows * cols >=
+ * 2^28 or rows * cols * w_diag >= 2^31 (below these no finite value can overflow). */
+#define HMSG_NAV_UNREACHED 2147483647
+typedef struct hmsg_route_params {
+    int32_t w_straight, w_diag;   /* 5, 7 */
+    int32_t min_clearance;        /* 0; in field units; hmsg_nav_route alone reads it */
+    int32_t reserved_;
+} hmsg_route_params;
+typedef struct hmsg_nav_routes {
+    int32_t* goal_cell;           /* i32 [n_goals][2]: the snapped cell, (-1, -1) when nothing is reached */
+    int64_t* goal_d2;             /* i64 [n_goals]: R4's d2 of the snap */
+    int32_t* goal_dist;           /* i32 [n_goals]: the field at the snapped cell */
+    int64_t* path_off;            /* i64 [n_goals + 1] */
+    int32_t* path_rc;             /* i32 [path_capacity][2] */
+    int64_t  path_capacity;
+    int32_t* field;               /* i32 [rows][cols]: the start's field (optional, like the next) */
+    uint8_t* passable;            /* u8 [rows][cols] */
+    /* out */
+    int64_t  n_path_cells;
+    int64_t  start_d2;            /* R4's d2 of the start's snap; -1: no passable cell */
+    int32_t  start_cell[2];
+} hmsg_nav_routes;
+void hmsg_route_default_params(hmsg_route_params* p);
+int hmsg_nav_clearance(int32_t device_id, int32_t rows, int32_t cols, const uint8_t* mask, const hmsg_route_params* prm, int32_t* clearance);
+/* n_fields source sets in one call: the cells src_rc[src_off[s] .. src_off[s + 1]) are the sources of fields[s] */
+int hmsg_nav_distance_fields(int32_t device_id, int32_t rows, int32_t cols, const uint8_t* passable, const hmsg_route_params* prm,
+                             int32_t n_fields, const int64_t* src_off /* [n_fields + 1] */, const int32_t* src_rc,
+                             int32_t* fields /* [n_fields][rows][cols] */, int64_t* n_reached /* [n_fields], may be NULL */);
+int hmsg_nav_snap_cells(int32_t device_id, int32_t rows, int32_t cols, const uint8_t* passable, const int32_t* field /* or NULL */, int64_t n,
+                        const int32_t* target_rc, int32_t* snapped_rc, int64_t* d2);
+int hmsg_nav_paths(int32_t device_id, int32_t rows, int32_t cols, const uint8_t* passable, const hmsg_route_params* prm, const int32_t* field,
+                   int64_t n_goals, const int32_t* goal_rc, int64_t* path_off /* [n_goals + 1] */, int32_t* path_rc, int64_t capacity,
+                   int64_t* n_needed);
+int hmsg_nav_route(int32_t device_id, int32_t rows, int32_t cols, const uint8_t* main_free_map, const hmsg_route_params* prm,
+                   const int32_t* start_rc, int64_t n_goals, const int32_t* goal_rc, hmsg_nav_routes* out);
+
 
 #ifdef __cplusplus
 }

@@ -123,6 +123,9 @@ int hmsg_test_graph_early_objects(const hmsg_graph_t* g, const hmsg_t* h, int32_
 int hmsg_test_sam_post_last(int32_t* rounds_holes, int32_t* rounds_islands, double* stats_ms);
 /* the labelling rounds (four scans each) of this thread's last hmsg_*nav_floor_maps call */
 int hmsg_test_nav_last(int32_t* label_rounds);
+/* the relaxation rounds that changed a tile and the host round trips (one read-back per batch of rounds) of this thread's last
+ * hmsg_nav_clearance / hmsg_nav_distance_fields / hmsg_nav_route call.  Either pointer may be NULL. */
+int hmsg_test_nav_route_last(int32_t* rounds, int32_t* round_trips);
 
 /* measurement hook: the queries that the process's last hmsg_knn_labels call (hmsg_evaluate_semseg's included) finished by scan
  * (phase 2) -- all of them under HMSG_DEBUG_KNN_BRUTE=1. */
