@@ -108,6 +108,10 @@ class HmsgNavRoutes(C.Structure):       # include/hmsg.h: hmsg_nav_routes
                 ("n_path_cells", C.c_int64), ("start_d2", C.c_int64), ("start_cell", C.c_int32 * 2)]
 
 
+class HmsgViewParams(C.Structure):      # include/hmsg.h: hmsg_view_params
+    _fields_ = [("r_min2", C.c_int64), ("r_max2", C.c_int64), ("prefer", C.c_int32), ("reserved_", C.c_int32)]
+
+
 class HmsgError(RuntimeError):
     pass
 
@@ -154,6 +158,9 @@ _SIGS = {
     "hmsg_nav_snap_cells": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P, _P, _P]),
     "hmsg_nav_paths": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int64, _P, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "hmsg_nav_route": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int64, _P, _P]),
+    "hmsg_view_default_params": (None, [_P]),
+    "hmsg_nav_viewpoints": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P]),
+    "hmsg_nav_view_route": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int64, _P, _P, _P]),
     "hmsg_get_frame_num_masks": (C.c_int32, [_P, C.c_int32]),
     "hmsg_fuse_frames": (C.c_int, [_P]),
     "hmsg_get_map_feats": (C.c_int, [_P, _P, _P]),
@@ -2204,6 +2211,84 @@ def nav_route(main_free_map, start_rc, goals_rc, params=None, device_id=0, lib_:
         _nav_ck(status, "hmsg_nav_route")
         break
     res.update(path_rc=rc[: out.n_path_cells], start_cell=(int(out.start_cell[0]), int(out.start_cell[1])), start_d2=int(out.start_d2))
+    return res
+
+
+# ---- N8: viewpoints on a floor's free map (include/hmsg.h states the rules V1 to V5)
+def view_params(lib_: "HmsgLib | None" = None, **over):
+    """hmsg_view_params with the defaults (r_min2 0, r_max2 100 * 100, prefer 0), fields overridden by keyword"""
+    L = lib_ or lib()
+    p = HmsgViewParams()
+    L.c.hmsg_view_default_params(C.byref(p))
+    for k, v in over.items():
+        if k not in ("r_min2", "r_max2", "prefer"):
+            raise HmsgError(f"unknown hmsg_view_params field {k}")
+        setattr(p, k, int(v))
+    return p
+
+
+def nav_viewpoints(blocking, passable, goals_rc, field=None, params=None, want_visible=False, device_id=0, lib_: "HmsgLib | None" = None,
+                   **over):
+    """V3 / V4: the viewpoint of every goal -> dict(view_rc int32 [n, 2], view_d2 int64 [n], view_dist int32 [n], n_visible int32
+    [n]; visible u8 [n, rows, cols] with want_visible).  blocking, passable u8 [rows, cols]; field int32 [rows, cols] or None.
+    numpy in: numpy out; device tensors in: device tensors out."""
+    L = lib_ or lib()
+    prm = params if params is not None else view_params(L, **over)
+    blocking, H, W, dev = _nav_image(blocking, np.uint8)
+    passable, ph, pw, pdev = _nav_image(passable, np.uint8)
+    assert (ph, pw) == (H, W) and (pdev is None) == (dev is None)
+    if field is not None:
+        field, fh, fw, fdev = _nav_image(field, np.int32)
+        assert (fh, fw) == (H, W) and (fdev is None) == (dev is None)
+    g = _nav_cells(goals_rc)
+    n = int(g.shape[0])
+    buf = _nav_buf(dev)
+    res = dict(view_rc=buf((n, 2), np.int32), view_d2=buf((n,), np.int64), view_dist=buf((n,), np.int32), n_visible=buf((n,), np.int32))
+    if want_visible:
+        res["visible"] = buf((n, H, W), np.uint8)
+    some = lambda a: _ptr(a) if n else None
+    _nav_ck(L.c.hmsg_nav_viewpoints(_nav_dev_id(dev, device_id), H, W, _ptr(blocking), _ptr(passable), _ptr(field), C.byref(prm), n, some(g),
+                                    some(res["view_rc"]), some(res["view_d2"]), some(res["view_dist"]), some(res["n_visible"]),
+                                    some(res["visible"]) if want_visible else None), "hmsg_nav_viewpoints")
+    return res
+
+
+def nav_view_route(main_free_map, blocking, start_rc, goals_rc, params=None, view=None, device_id=0, lib_: "HmsgLib | None" = None,
+                   want_field=False, **over):
+    """hmsg_nav_view_route: nav_route with the goals' cells chosen by V4 (in sight of the goal on `blocking`) in R4's place -> nav_route's
+    dict plus n_visible int32 [n].  Keywords: the fields of hmsg_route_params and of hmsg_view_params."""
+    L = lib_ or lib()
+    vkeys = ("r_min2", "r_max2", "prefer")
+    prm = params if params is not None else route_params(L, **{k: v for k, v in over.items() if k not in vkeys})
+    vprm = view if view is not None else view_params(L, **{k: v for k, v in over.items() if k in vkeys})
+    m, H, W, dev = _nav_image(main_free_map, np.uint8)
+    blocking, bh, bw, bdev = _nav_image(blocking, np.uint8)
+    assert (bh, bw) == (H, W) and (bdev is None) == (dev is None)
+    start = np.ascontiguousarray(np.asarray(start_rc, np.int64).reshape(2).astype(np.int32))
+    g = _nav_cells(goals_rc)
+    n = int(g.shape[0])
+    buf = _nav_buf(dev)
+    res = dict(goal_cell=buf((n, 2), np.int32), goal_d2=buf((n,), np.int64), goal_dist=buf((n,), np.int32), path_off=buf((n + 1,), np.int64),
+               passable=buf((H, W), np.uint8))
+    if want_field:
+        res["field"] = buf((H, W), np.int32)
+    n_visible = buf((n,), np.int32)
+    out = HmsgNavRoutes()
+    cap = max(1, n) * 2 * (H + W)
+    for attempt in range(2):
+        rc = buf((max(cap, 1), 2), np.int32)
+        for k, v in res.items():
+            setattr(out, k, _ptr(v))
+        out.path_rc, out.path_capacity = _ptr(rc), cap
+        status = L.c.hmsg_nav_view_route(_nav_dev_id(dev, device_id), H, W, _ptr(m), _ptr(blocking), C.byref(prm), C.byref(vprm), _ptr(start), n,
+                                         _ptr(g) if n else None, C.byref(out), _ptr(n_visible) if n else None)
+        if status != 0 and attempt == 0 and out.n_path_cells > cap:
+            cap = int(out.n_path_cells)
+            continue
+        _nav_ck(status, "hmsg_nav_view_route")
+        break
+    res.update(path_rc=rc[: out.n_path_cells], start_cell=(int(out.start_cell[0]), int(out.start_cell[1])), start_d2=int(out.start_d2),
+               n_visible=n_visible)
     return res
 
 

@@ -24,7 +24,7 @@
 //    2^28), so (d2, index) does not fit one 64-bit word and is compared as a pair.
 //  * Paths (k_navr_walk): a lane per goal, two passes over the same walk: count, one wave's ordered scan of the counts, write
 //    from the back.  The walk is a dependent chain of global loads; it stays here because the field does.
-#include "hmsg_boundary.h"
+#include "hmsg_navroute_dev.h"
 
 #include <climits>
 
@@ -342,6 +342,7 @@ void navr_clearance_dev(hipStream_t s, int rows, int cols, const unsigned char* 
     navr_relax(s, rows, cols, nullptr, p, false, 1, d_clr, act.p);
 }
 
+}  // namespace
 void navr_snap_dev(hipStream_t s, int rows, int cols, const unsigned char* d_pass, const int* d_field, long long n, const int* d_target,
                    int* d_snapped, long long* d_d2) {
     if (n <= 0) return;
@@ -349,6 +350,7 @@ void navr_snap_dev(hipStream_t s, int rows, int cols, const unsigned char* d_pas
                        d_snapped, d_d2);
     HMSG_CHECK_LAUNCH();
 }
+namespace {
 
 // path_off (device, [n + 1]) and the total; the list into path_rc (caller memory, host or device) when it is wanted and fits.
 // Returns the total; *too_short says that a wanted list was not written.
@@ -504,71 +506,80 @@ extern "C" int hmsg_nav_paths(int32_t device_id, int32_t rows, int32_t cols, con
     });
 }
 
-// the composition, and only that: clearance -> passable, snap the start, one field, snap the goals among the reached, paths
+// the composition, and only that: clearance -> passable, snap the start, one field, the goals' cells among the reached (R4 for
+// hmsg_nav_route, V4 for hmsg_nav_view_route: `snap` is the one step in which the two differ), paths
+void navr_route_run(const char* fn, int32_t rows, int32_t cols, const uint8_t* main_free_map, const hmsg_route_params* prm, const int32_t* start_rc,
+                    int64_t n_goals, const int32_t* goal_rc, hmsg_nav_routes* out, const navr_goal_snap& snap) {
+    navr_check(rows, cols, *prm, fn);
+    HMSG_REQUIRE(n_goals >= 0 && (!out->path_rc || out->path_capacity >= 0), HMSG_ERR_INVALID, std::string(fn) + ": n_goals < 0 or path_capacity < 0");
+    out->n_path_cells = 0, out->start_d2 = -1, out->start_cell[0] = out->start_cell[1] = -1;
+    g_navr_rounds = g_navr_trips = 0;
+    ScopedStream s(hipStreamNonBlocking);
+    const size_t HW = (size_t)rows * cols, n = (size_t)n_goals;
+    const dim3 gi(cdiv(HW, NAVR_T)), b(NAVR_T);
+    DevBuf<unsigned char> own_mask, own_pass;
+    DevBuf<int> clr, own_field, own_start, own_goal, own_cell, own_dist, start;
+    DevBuf<long long> own_d2, d_off, src_off, start_d2;
+    const unsigned char* d_mask = stage_in(own_mask, main_free_map, HW, s, Up::bounce);
+    const int* d_start = stage_in(own_start, start_rc, 2, s, Up::direct);
+    const int* d_goal = n ? stage_in(own_goal, goal_rc, n * 2, s, Up::bounce) : nullptr;
+    // 1. passable
+    unsigned char* d_pass = stage_out(own_pass, out->passable, HW);
+    if (!d_pass) own_pass.alloc(HW), d_pass = own_pass.p;
+    if (prm->min_clearance > 0) {
+        clr.alloc(HW);
+        navr_clearance_dev(s, rows, cols, d_mask, *prm, clr.p);
+        hipLaunchKernelGGL(k_navr_threshold, gi, b, 0, s, d_mask, (const int*)clr.p, prm->min_clearance, (int)HW, d_pass);
+    } else {
+        hipLaunchKernelGGL(k_navr_binary, gi, b, 0, s, d_mask, (int)HW, d_pass);
+    }
+    HMSG_CHECK_LAUNCH();
+    // 2. the start, 3. its field
+    start.alloc(2), start_d2.alloc(1), src_off.alloc(2);
+    navr_snap_dev(s, rows, cols, d_pass, nullptr, 1, d_start, start.p, start_d2.p);
+    const long long h_off[2] = {0, 1};
+    HIP_TRY(hipMemcpyAsync(src_off.p, h_off, sizeof(h_off), hipMemcpyHostToDevice, s));
+    int* d_field = stage_out(own_field, out->field, HW);
+    if (!d_field) own_field.alloc(HW), d_field = own_field.p;
+    navr_fields_dev(s, rows, cols, d_pass, *prm, 1, src_off.p, start.p, 1, d_field, nullptr);
+    // 4. the goals among the reached cells, their distances
+    int* d_cell = stage_out(own_cell, out->goal_cell, n * 2);
+    if (!d_cell) own_cell.alloc(n * 2), d_cell = own_cell.p;
+    long long* d_d2 = stage_out(own_d2, (long long*)out->goal_d2, n);
+    int* d_dist = stage_out(own_dist, out->goal_dist, n);
+    snap(s, d_pass, d_field, d_goal, d_cell, d_d2);
+    if (d_dist && n) {
+        hipLaunchKernelGGL(k_navr_gather, dim3(cdiv(n, NAVR_T)), b, 0, s, (const int*)d_field, cols, (long long)n, (const int*)d_cell, d_dist);
+        HMSG_CHECK_LAUNCH();
+    }
+    // 5. the paths
+    d_off.alloc(n + 1);
+    bool too_short = false;
+    const long long total = navr_paths_dev(s, rows, cols, d_pass, *prm, d_field, n_goals, d_cell, d_off.p, out->path_rc, out->path_capacity,
+                                           &too_short);
+    out->n_path_cells = total;
+    if (out->path_off) copy_out(out->path_off, d_off.p, (n + 1) * 8, s);
+    if (out->passable) unstage_out(out->passable, d_pass, HW, s);
+    if (out->field) unstage_out(out->field, d_field, HW, s);
+    if (out->goal_cell) unstage_out(out->goal_cell, d_cell, n * 2, s);
+    if (out->goal_d2) unstage_out((long long*)out->goal_d2, (const long long*)d_d2, n, s);
+    if (out->goal_dist) unstage_out(out->goal_dist, d_dist, n, s);
+    long long h_d2 = -1;
+    HIP_TRY(hipMemcpyAsync(out->start_cell, start.p, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&h_d2, start_d2.p, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    out->start_d2 = h_d2;
+    if (too_short) navr_throw_short(fn, total, out->path_capacity);
+}
+
 extern "C" int hmsg_nav_route(int32_t device_id, int32_t rows, int32_t cols, const uint8_t* main_free_map, const hmsg_route_params* prm,
                               const int32_t* start_rc, int64_t n_goals, const int32_t* goal_rc, hmsg_nav_routes* out) {
     if (!main_free_map || !prm || !start_rc || !out || (n_goals > 0 && !goal_rc)) return HMSG_ERR_INVALID;
     return hmsg_boundary("hmsg_nav_route", device_id, [&] {
-        navr_check(rows, cols, *prm, "hmsg_nav_route");
-        HMSG_REQUIRE(n_goals >= 0 && (!out->path_rc || out->path_capacity >= 0), HMSG_ERR_INVALID, "hmsg_nav_route: n_goals < 0 or path_capacity < 0");
-        out->n_path_cells = 0, out->start_d2 = -1, out->start_cell[0] = out->start_cell[1] = -1;
-        g_navr_rounds = g_navr_trips = 0;
-        ScopedStream s(hipStreamNonBlocking);
-        const size_t HW = (size_t)rows * cols, n = (size_t)n_goals;
-        const dim3 gi(cdiv(HW, NAVR_T)), b(NAVR_T);
-        DevBuf<unsigned char> own_mask, own_pass;
-        DevBuf<int> clr, own_field, own_start, own_goal, own_cell, own_dist, start;
-        DevBuf<long long> own_d2, d_off, src_off, start_d2;
-        const unsigned char* d_mask = stage_in(own_mask, main_free_map, HW, s, Up::bounce);
-        const int* d_start = stage_in(own_start, start_rc, 2, s, Up::direct);
-        const int* d_goal = n ? stage_in(own_goal, goal_rc, n * 2, s, Up::bounce) : nullptr;
-        // 1. passable
-        unsigned char* d_pass = stage_out(own_pass, out->passable, HW);
-        if (!d_pass) own_pass.alloc(HW), d_pass = own_pass.p;
-        if (prm->min_clearance > 0) {
-            clr.alloc(HW);
-            navr_clearance_dev(s, rows, cols, d_mask, *prm, clr.p);
-            hipLaunchKernelGGL(k_navr_threshold, gi, b, 0, s, d_mask, (const int*)clr.p, prm->min_clearance, (int)HW, d_pass);
-        } else {
-            hipLaunchKernelGGL(k_navr_binary, gi, b, 0, s, d_mask, (int)HW, d_pass);
-        }
-        HMSG_CHECK_LAUNCH();
-        // 2. the start, 3. its field
-        start.alloc(2), start_d2.alloc(1), src_off.alloc(2);
-        navr_snap_dev(s, rows, cols, d_pass, nullptr, 1, d_start, start.p, start_d2.p);
-        const long long h_off[2] = {0, 1};
-        HIP_TRY(hipMemcpyAsync(src_off.p, h_off, sizeof(h_off), hipMemcpyHostToDevice, s));
-        int* d_field = stage_out(own_field, out->field, HW);
-        if (!d_field) own_field.alloc(HW), d_field = own_field.p;
-        navr_fields_dev(s, rows, cols, d_pass, *prm, 1, src_off.p, start.p, 1, d_field, nullptr);
-        // 4. the goals among the reached cells, their distances
-        int* d_cell = stage_out(own_cell, out->goal_cell, n * 2);
-        if (!d_cell) own_cell.alloc(n * 2), d_cell = own_cell.p;
-        long long* d_d2 = stage_out(own_d2, (long long*)out->goal_d2, n);
-        int* d_dist = stage_out(own_dist, out->goal_dist, n);
-        navr_snap_dev(s, rows, cols, d_pass, d_field, n_goals, d_goal, d_cell, d_d2);
-        if (d_dist && n) {
-            hipLaunchKernelGGL(k_navr_gather, dim3(cdiv(n, NAVR_T)), b, 0, s, (const int*)d_field, cols, (long long)n, (const int*)d_cell, d_dist);
-            HMSG_CHECK_LAUNCH();
-        }
-        // 5. the paths
-        d_off.alloc(n + 1);
-        bool too_short = false;
-        const long long total = navr_paths_dev(s, rows, cols, d_pass, *prm, d_field, n_goals, d_cell, d_off.p, out->path_rc, out->path_capacity,
-                                               &too_short);
-        out->n_path_cells = total;
-        if (out->path_off) copy_out(out->path_off, d_off.p, (n + 1) * 8, s);
-        if (out->passable) unstage_out(out->passable, d_pass, HW, s);
-        if (out->field) unstage_out(out->field, d_field, HW, s);
-        if (out->goal_cell) unstage_out(out->goal_cell, d_cell, n * 2, s);
-        if (out->goal_d2) unstage_out((long long*)out->goal_d2, (const long long*)d_d2, n, s);
-        if (out->goal_dist) unstage_out(out->goal_dist, d_dist, n, s);
-        long long h_d2 = -1;
-        HIP_TRY(hipMemcpyAsync(out->start_cell, start.p, 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(&h_d2, start_d2.p, 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        out->start_d2 = h_d2;
-        if (too_short) navr_throw_short("hmsg_nav_route", total, out->path_capacity);
+        navr_route_run("hmsg_nav_route", rows, cols, main_free_map, prm, start_rc, n_goals, goal_rc, out,
+                       [&](hipStream_t s, const unsigned char* d_pass, const int* d_field, const int* d_goal, int* d_cell, long long* d_d2) {
+                           navr_snap_dev(s, rows, cols, d_pass, d_field, n_goals, d_goal, d_cell, d_d2);
+                       });
     });
 }
 

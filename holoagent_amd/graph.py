@@ -1430,6 +1430,37 @@ class Graph:
                 out[k].update(r, reason=None if r["reachable"] else "unreachable")
         return out
 
+    def view_routes_to_objects(self, start_pose, objects, floor_id=None, min_clearance=0.25, view_range=(0.5, 3.0), prefer="walk",
+                               poses_list=None):
+        """route_to_objects with the cell to stand on chosen so that the object is in sight (include/hmsg.h: hmsg_nav_view_route, on
+        the device): of the cells that have min_clearance metres of free space, can be reached and see the cell under the
+        object's centre on the storey's obstacle map from view_range metres (near, far), the one with the least walk (prefer
+        "walk") or the closest look ("look").  The nearest such cell of route_to_objects can lie behind a wall.  Per object
+        route_to_objects' dict plus n_visible, facing (unit (x, z) towards the object) and yaw; reason is None, "other floor",
+        "unreachable" (the start reaches no cell at all) or "no view" (cells are reached, none of them sees the object within the
+        range)."""
+        pose = np.asarray(start_pose, np.float64)
+        f = int(floor_id) if floor_id is not None else self.floor_of_pose(pose)
+        if f is None:
+            raise ValueError("the start pose lies on no storey")
+        centres, floors = [], []
+        for o in objects:
+            node = self.objects[int(o)] if isinstance(o, (int, np.integer)) else o
+            c = np.asarray(node.pcd.get_center() if hasattr(node, "pcd") else node, np.float64).reshape(3)
+            centres.append(c)
+            floors.append(self._floor_of_object(node, c))
+        here = [k for k, fo in enumerate(floors) if fo == f]
+        out = [dict(object=o, point=None, cell=(-1, -1), reachable=False, length_m=None, snap_m=None, polyline=np.zeros((0, 3)),
+                    n_visible=0, facing=None, yaw=None, floor_id=floors[k], reason="other floor") for k, o in enumerate(objects)]
+        if here:
+            nav = self.floor_navigation(f, poses_list)
+            routes = nav.route_to_view(pose[:3, 3], np.array([centres[k] for k in here]), min_clearance_m=min_clearance, view_range_m=view_range,
+                                       prefer=prefer)
+            nothing_reached = nav.last_route["start_cell"] == (-1, -1)
+            for k, r in zip(here, routes):
+                out[k].update(r, reason=None if r["reachable"] else ("unreachable" if nothing_reached else "no view"))
+        return out
+
     # ------------------------------------------------------------------ A11: graph.py:1752-1775
     def create_graph_new(self):
         """Building(0) - Floor - Room - Object, Room - View, View - Object.  As in the reference, `room.room_id ==

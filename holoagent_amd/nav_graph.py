@@ -13,7 +13,9 @@ drawings and histogram plots are not reproduced; the map PNGs are written with P
 reference's own class gives on two scenes; tests/test_navgraph_golden.py compares everything exactly.
 
 Beyond the reference (include/hmsg.h, N7): clearance_map, distance_field and route work on the maps this object already holds --
-exact integer distance fields on main_free_map, the nearest reachable free cell of a goal and the cells of the way, on the device."""
+exact integer distance fields on main_free_map, the nearest reachable free cell of a goal and the cells of the way, on the device.
+N8: sight_blocking_map, viewpoints and route_to_view stand the robot on a reached cell from which the goal is in sight on the
+obstacle map, not on the nearest one whatever lies between."""
 import json
 import os
 
@@ -178,6 +180,83 @@ class NavigationGraph:
                             length_m=float(r["goal_dist"][k]) * self.cell_size / ws if ok else None,
                             snap_m=float(np.sqrt(float(r["goal_d2"][k]))) * self.cell_size if ok else None,
                             polyline=world(r["path_rc"][r["path_off"][k]:r["path_off"][k + 1]])))
+        return out
+
+    # ---- viewpoints (include/hmsg.h, N8: the rules V1 to V5; no counterpart in the reference)
+    def sight_blocking_map(self):
+        """what blocks a sight line: obstacle_map > 0 as u8 [rows, cols], where the maps are"""
+        assert self.maps is not None, "get_main_free_map makes the maps"
+        ob = self.maps["obstacle_map"] > 0
+        if hasattr(ob, "to"):
+            import torch
+            return ob.to(torch.uint8)
+        return ob.astype(np.uint8)
+
+    def view_band(self, view_range_m):
+        """(r_min2, r_max2) in cells of a (near, far) range in metres: int(m / cell_size), squared; V5 bounds the far end"""
+        near, far = (int(float(m) / self.cell_size) for m in view_range_m)
+        if far > 255:
+            raise ValueError("view_range_m: the far bound is %d cells, hmsg_nav_viewpoints takes 255 at the most" % far)
+        return near * near, far * far
+
+    @staticmethod
+    def _prefer(prefer):
+        if prefer not in ("walk", "look"):
+            raise ValueError('prefer: "walk" (least walk) or "look" (closest look)')
+        return 0 if prefer == "walk" else 1
+
+    def viewpoints(self, goals, start=None, min_clearance_m=0.0, view_range_m=(0.0, 3.0), prefer="walk", want_visible=False, **weights):
+        """hmsg_nav_viewpoints for every goal (world points [n, 3] or cells [n, 2]) on passable_map(min_clearance_m) and
+        sight_blocking_map(): _lib.nav_viewpoints' dict, where the maps are.  start (a world point or a cell): only cells reached
+        from it, snapped by R4 as route snaps it, are candidates, and view_dist is the walk to them."""
+        r_min2, r_max2 = self.view_band(view_range_m)
+        pas = self.passable_map(min_clearance_m, **weights)
+        field = None
+        if start is not None:
+            cell, _ = _lib.nav_snap_cells(pas, self.cells_of(start), lib_=self.L, device_id=self.device_id)
+            cell = cell.cpu().numpy() if hasattr(cell, "cpu") else cell
+            field = self.distance_field(cell if cell[0, 0] >= 0 else np.zeros((0, 2), np.int32), min_clearance_m, **weights)
+        return _lib.nav_viewpoints(self.sight_blocking_map(), pas, self.cells_of(goals), field=field, want_visible=want_visible, lib_=self.L,
+                                   device_id=self.device_id, r_min2=r_min2, r_max2=r_max2, prefer=self._prefer(prefer))
+
+    def route_to_view(self, start_xyz, goals_xyz, min_clearance_m=0.0, view_range_m=(0.0, 3.0), prefer="walk", **weights):
+        """hmsg_nav_view_route: route's dict per goal, the cell stood on being the goal's viewpoint (V4: in sight of the goal within
+        view_range_m, the least walk or the closest look) in place of R4's nearest cell.  Added: `n_visible` (the cells the goal
+        is seen from), `facing` (a float64 unit (x, z) vector from the stand-on point to the goal's world point -- a cell's centre
+        for a goal given as a cell -- or (0, 0) when both lie in one cell; None when not reachable) and `yaw` = atan2(facing_x,
+        facing_z).  A goal that no reached cell sees is not reachable."""
+        assert self.maps is not None, "get_main_free_map makes the maps"
+        ws = int(weights.get("w_straight", 5))
+        r_min2, r_max2 = self.view_band(view_range_m)
+        goal_cells = self.cells_of(goals_xyz)
+        r = _lib.nav_view_route(self.maps["main_free_map"], self.sight_blocking_map(), self.cells_of(start_xyz)[0], goal_cells, lib_=self.L,
+                                device_id=self.device_id, min_clearance=self.clearance_units(min_clearance_m, ws), r_min2=r_min2, r_max2=r_max2,
+                                prefer=self._prefer(prefer), **weights)
+        r = {k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in r.items()}
+        self.last_route = r
+
+        def world(rc):
+            rc = np.asarray(rc, np.float64).reshape(-1, 2)
+            return np.stack([(rc[:, 1] + 0.5) * self.cell_size + self.pcd_min[0], np.full(len(rc), self.pcd_min[1]),
+                             (rc[:, 0] + 0.5) * self.cell_size + self.pcd_min[2]], axis=1)
+        g = np.asarray(goals_xyz.cpu() if hasattr(goals_xyz, "cpu") else goals_xyz, np.float64)
+        g = g.reshape(-1, g.shape[-1]) if g.ndim > 1 else g.reshape(1, -1)
+        goal_points = g if g.shape[1] == 3 else world(goal_cells)
+        out = []
+        for k, cell in enumerate(r["goal_cell"]):
+            ok = bool(cell[0] >= 0 and r["goal_dist"][k] != _lib.NAV_UNREACHED)
+            point = world(cell)[0] if ok else None
+            facing = yaw = None
+            if ok:
+                d = np.array([goal_points[k, 0] - point[0], goal_points[k, 2] - point[2]], np.float64)
+                same = tuple(int(v) for v in cell) == tuple(int(v) for v in goal_cells[k])
+                facing = np.zeros(2) if same or not d.any() else d / np.sqrt(d[0] * d[0] + d[1] * d[1])
+                yaw = float(np.arctan2(facing[0], facing[1]))
+            out.append(dict(point=point, cell=(int(cell[0]), int(cell[1])), reachable=ok,
+                            length_m=float(r["goal_dist"][k]) * self.cell_size / ws if ok else None,
+                            snap_m=float(np.sqrt(float(r["goal_d2"][k]))) * self.cell_size if ok else None,
+                            polyline=world(r["path_rc"][r["path_off"][k]:r["path_off"][k + 1]]), n_visible=int(r["n_visible"][k]),
+                            facing=facing, yaw=yaw))
         return out
 
     # ---- the graph half

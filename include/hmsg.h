@@ -1335,6 +1335,53 @@ int hmsg_nav_paths(int32_t device_id, int32_t rows, int32_t cols, const uint8_t*
 int hmsg_nav_route(int32_t device_id, int32_t rows, int32_t cols, const uint8_t* main_free_map, const hmsg_route_params* prm,
                    const int32_t* start_rc, int64_t n_goals, const int32_t* goal_rc, hmsg_nav_routes* out);
 
+/* ---- N8: viewpoints on a floor's free map (csrc/hmsg_navview.hip): the cells from which a goal is in sight, and the one to stand
+ * on.  R4 takes the nearest passable, reached cell whatever lies between it and the goal; with a clearance the passable set
+ * shrinks away from every wall, and the nearest passable cell of an object in a narrow room or on a wall can be on the wall's
+ * other side.  The reference has no such stage (goal_pose_publisher.py:260-271 publishes an object's centre; the slow path
+ * matches the object again in the camera image on arrival), so the rules are this library's.  Images, cells and memory
+ * conventions are N7's.  blocking is u8 [rows][cols], a cell is opaque where its byte is not 0 (a storey's obstacle_map);
+ * passable is u8 [rows][cols]; field (optional) is an R2 field on passable.  All of it is integer work: every output has one
+ * right answer.  The rules:
+ *  V1. Sight line of the cells a and b: start from whichever of the two has the smaller (row, col) pair, so dr >= 0.  n =
+ *      max(|dr|, |dc|).  For i = 0 .. n the major coordinate advances by one per step (towards the other cell) and the minor
+ *      coordinate is m0 + floor((2 * i * dm + n) / (2 * n)) -- the mathematical floor, not C's truncation: dm may be negative.
+ *      The major axis is the row axis when |dr| >= |dc|.  n = 0: the single cell.  The start is chosen by the cells, not by the
+ *      caller: line(a, b) == line(b, a).
+ *  V2. Clear sight: no cell of the line but its two endpoints is blocking, and no diagonal step of the line squeezes between
+ *      two blocking cells -- for consecutive cells (r0, c0) -> (r1, c1) with both coordinates changing, blocking[r0][c1] &&
+ *      blocking[r1][c0] blocks ([[1, 0], [0, 1]] is opaque, as in R1).  The endpoints never block: an object's centre may lie
+ *      inside an obstacle.
+ *  V3. Visible set of a goal g: the cells c of the image with passable[c] != 0; field[c] finite, when a field is given; r_min2
+ *      <= d2(c, g) <= r_max2, d2 = dr * dr + dc * dc in int64; and a clear sight from c to g.  A goal outside the image has an
+ *      empty set.
+ *  V4. Viewpoint: the member of the visible set with the least key -- prefer 0 (least walk): (field value, d2, row-major index);
+ *      prefer 1 (closest look): (d2, field value, row-major index).  Without a field the field value counts as 0 for every
+ *      cell (and view_dist is 0).  An empty set gives the cell (-1, -1), d2 = -1 and dist = HMSG_NAV_UNREACHED.
+ *  V5. Limits: r_max2 <= 255 * 255, so that the window round a goal is at most 511 x 511 cells and one workgroup holds its
+ *      blocking bits in LDS.
+ * hmsg_nav_viewpoints: n_visible[k] is the size of goal k's visible set and visible[k] its mask (1 / 0), every byte written;
+ * view_d2, view_dist, n_visible and visible may each be NULL.  hmsg_nav_view_route is hmsg_nav_route with its goal snap (R4)
+ * replaced by V4 on the start's field, and only that: the clearance -> passable step, the start's snap, the field, the paths,
+ * the fields of hmsg_nav_routes and the too-short path list are hmsg_nav_route's; goal_cell is the viewpoint, goal_d2 its d2,
+ * goal_dist its field value; n_visible (i32 [n_goals]) may be NULL.  Every array may be host or device memory; the structs are
+ * host memory.  Refusals (HMSG_ERR_INVALID unless said): a null required pointer; rows or cols < 1; n_goals < 0; r_min2 < 0;
+ * r_max2 < r_min2; prefer not 0 or 1; HMSG_ERR_UNSUPPORTED when r_max2 > 255 * 255 or rows * cols >= 2^28; for
+ * hmsg_nav_view_route also hmsg_nav_route's. */
+typedef struct hmsg_view_params {
+    int64_t r_min2, r_max2;       /* 0, 100 * 100: the band of squared distances to the goal, in cells */
+    int32_t prefer;               /* 0: least walk; 1: closest look */
+    int32_t reserved_;
+} hmsg_view_params;
+void hmsg_view_default_params(hmsg_view_params* p);
+int hmsg_nav_viewpoints(int32_t device_id, int32_t rows, int32_t cols, const uint8_t* blocking, const uint8_t* passable,
+                        const int32_t* field /* or NULL */, const hmsg_view_params* prm, int64_t n_goals, const int32_t* goal_rc,
+                        int32_t* view_rc /* i32 [n_goals][2] */, int64_t* view_d2 /* i64 [n_goals] */, int32_t* view_dist /* i32 [n_goals] */,
+                        int32_t* n_visible /* i32 [n_goals] */, uint8_t* visible /* u8 [n_goals][rows][cols] */);
+int hmsg_nav_view_route(int32_t device_id, int32_t rows, int32_t cols, const uint8_t* main_free_map, const uint8_t* blocking,
+                        const hmsg_route_params* route_prm, const hmsg_view_params* view_prm, const int32_t* start_rc, int64_t n_goals,
+                        const int32_t* goal_rc, hmsg_nav_routes* out, int32_t* n_visible /* i32 [n_goals], may be NULL */);
+
 
 #ifdef __cplusplus
 }
