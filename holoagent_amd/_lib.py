@@ -108,6 +108,12 @@ class HmsgNavRoutes(C.Structure):       # include/hmsg.h: hmsg_nav_routes
                 ("n_path_cells", C.c_int64), ("start_d2", C.c_int64), ("start_cell", C.c_int32 * 2)]
 
 
+class HmsgNavBuildingRoutes(C.Structure):       # include/hmsg.h: hmsg_nav_building_routes
+    _fields_ = [("goal_cell", C.c_void_p), ("goal_d2", C.c_void_p), ("goal_dist", C.c_void_p), ("path_off", C.c_void_p),
+                ("path_src", C.c_void_p), ("path_capacity", C.c_int64), ("field", C.POINTER(C.c_void_p)), ("passable", C.POINTER(C.c_void_p)),
+                ("n_path_cells", C.c_int64), ("start_d2", C.c_int64), ("start_cell", C.c_int32 * 3), ("reserved_", C.c_int32)]
+
+
 class HmsgViewParams(C.Structure):      # include/hmsg.h: hmsg_view_params
     _fields_ = [("r_min2", C.c_int64), ("r_max2", C.c_int64), ("prefer", C.c_int32), ("reserved_", C.c_int32)]
 
@@ -299,6 +305,12 @@ _SIGS = {
     "hmsg_test_pool_rows": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_double, C.c_int32, _P]),
     "hmsg_test_graph_early_objects": (C.c_int, [_P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "hmsg_test_sam_post_last": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "hmsg_nav_seeded_fields": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, _P, _P, _P]),
+    "hmsg_nav_building_fields": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P, _P, _P]),
+    "hmsg_nav_building_paths": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, C.c_int64, _P, _P, _P, C.c_int64,
+                                          C.POINTER(C.c_int64)]),
+    "hmsg_nav_building_route": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, C.c_int64, _P, _P]),
+    "hmsg_test_nav_building_last": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "hmsg_test_nav_last": (C.c_int, [C.POINTER(C.c_int32)]),
     "hmsg_test_nav_route_last": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "hmsg_test_knn_last_phase2": (C.c_int64, []),
@@ -2289,6 +2301,138 @@ def nav_view_route(main_free_map, blocking, start_rc, goals_rc, params=None, vie
         break
     res.update(path_rc=rc[: out.n_path_cells], start_cell=(int(out.start_cell[0]), int(out.start_cell[1])), start_d2=int(out.start_d2),
                n_visible=n_visible)
+    return res
+
+
+# ---- N9: routes across storeys (include/hmsg.h states the rules B1 to B6)
+def nav_seeded_fields(passable, seed_sets, params=None, device_id=0, lib_: "HmsgLib | None" = None, **over):
+    """B1: one field per seed set.  passable u8 [rows, cols]; seed_sets: a list of (cells [k, 2], costs [k]) pairs, or the triple
+    (seed_off int64 [n + 1], seed_rc int32 [m, 2], seed_cost int32 [m]) -> (fields int32 [n, rows, cols], n_reached int64 [n])"""
+    L = lib_ or lib()
+    prm = params if params is not None else route_params(L, **over)
+    passable, H, W, dev = _nav_image(passable, np.uint8)
+    if isinstance(seed_sets, tuple) and len(seed_sets) == 3 and np.ndim(seed_sets[0]) == 1:
+        off, rc = np.ascontiguousarray(np.asarray(seed_sets[0], np.int64)), _nav_cells(seed_sets[1])
+        cost = np.ascontiguousarray(np.asarray(seed_sets[2], np.int64).clip(-2 ** 31, 2 ** 31 - 1).astype(np.int32).reshape(-1))
+    else:
+        cells = [np.asarray(c_, np.int64).reshape(-1, 2) for c_, _ in seed_sets]
+        costs = [np.asarray(v_, np.int64).reshape(-1) for _, v_ in seed_sets]
+        assert all(len(c_) == len(v_) for c_, v_ in zip(cells, costs)), "a cost per seed"
+        off = np.concatenate([[0], np.cumsum([len(c_) for c_ in cells])]).astype(np.int64)
+        rc = _nav_cells(np.concatenate(cells) if cells else np.zeros((0, 2)))
+        cost = np.ascontiguousarray((np.concatenate(costs) if costs else np.zeros(0)).clip(-2 ** 31, 2 ** 31 - 1).astype(np.int32))
+    n = len(off) - 1
+    buf = _nav_buf(dev)
+    fields, reached = buf((n, H, W), np.int32), buf((n,), np.int64)
+    _nav_ck(L.c.hmsg_nav_seeded_fields(_nav_dev_id(dev, device_id), H, W, _ptr(passable), C.byref(prm), n, _ptr(off),
+                                       _ptr(rc) if len(rc) else None, _ptr(cost) if len(cost) else None, _ptr(fields), _ptr(reached)),
+            "hmsg_nav_seeded_fields")
+    return fields, reached
+
+
+class _NavBuilding:
+    """a building for the C ABI: the storeys' images (all numpy or all device tensors), shapes, the array of pointers, the links"""
+
+    def __init__(self, images, links, np_dtype=np.uint8):
+        assert len(images) >= 1, "a building has a storey"
+        got = [_nav_image(m, np_dtype) for m in images]
+        self.images = [g[0] for g in got]
+        self.shapes = [(g[1], g[2]) for g in got]
+        self.dev = got[0][3]
+        assert all((g[3] is None) == (self.dev is None) for g in got), "the storeys' images: all host or all device memory"
+        self.n = len(got)
+        self.rows = np.array([h for h, _ in self.shapes], np.int32)
+        self.cols = np.array([w for _, w in self.shapes], np.int32)
+        self.ptrs = self.pointers(self.images)
+        ln = np.asarray(links if links is not None and len(links) else np.zeros((0, 7)), np.int64).reshape(-1, 7)
+        self.links = np.ascontiguousarray(ln.clip(-2 ** 31, 2 ** 31 - 1).astype(np.int32))
+
+    @staticmethod
+    def pointers(arrays):
+        return (C.c_void_p * len(arrays))(*[_ptr(a) for a in arrays])
+
+    def head(self, device_id):
+        return (_nav_dev_id(self.dev, device_id), self.n, _ptr(self.rows), _ptr(self.cols), self.ptrs, len(self.links),
+                _ptr(self.links) if len(self.links) else None)
+
+
+def _nav_triples(a):
+    """(storey, row, col) triples for the C ABI: int32 [n, 3] on the host (the library reads them there)"""
+    a = np.asarray(a.cpu() if hasattr(a, "cpu") else a)
+    return np.ascontiguousarray(np.asarray(a, np.int64).reshape(-1, 3).clip(-2 ** 31, 2 ** 31 - 1).astype(np.int32))
+
+
+def nav_building_fields(passables, links, starts, params=None, device_id=0, lib_: "HmsgLib | None" = None, **over):
+    """B3: the building fields of every start.  passables: a list of u8 [rows_l, cols_l] (numpy, or device tensors: then the fields
+    are device tensors); links int [k, 7] (sa, ra, ca, sb, rb, cb, cost); starts int [n, 3] (storey, row, col) -> (fields: a list
+    with one int32 [n, rows_l, cols_l] per storey, n_reached int64 [n, storeys])"""
+    L = lib_ or lib()
+    prm = params if params is not None else route_params(L, **over)
+    b = _NavBuilding(passables, links)
+    st = _nav_triples(starts)
+    n = len(st)
+    buf = _nav_buf(b.dev)
+    fields = [buf((n, h, w), np.int32) for h, w in b.shapes]
+    reached = buf((n, b.n), np.int64)
+    _nav_ck(L.c.hmsg_nav_building_fields(*b.head(device_id), C.byref(prm), n, _ptr(st) if n else None, b.pointers(fields), _ptr(reached)),
+            "hmsg_nav_building_fields")
+    return fields, reached
+
+
+def nav_building_paths(passables, links, fields, goals, params=None, device_id=0, lib_: "HmsgLib | None" = None, **over):
+    """B5 on the building field of one start (fields: one int32 [rows_l, cols_l] per storey) -> (path_off int64 [n + 1], path_src
+    int32 [k, 3]: storey, row, col).  The first call counts, the second writes."""
+    L = lib_ or lib()
+    prm = params if params is not None else route_params(L, **over)
+    b = _NavBuilding(passables, links)
+    f = _NavBuilding(fields, None, np.int32)
+    assert f.shapes == b.shapes and (f.dev is None) == (b.dev is None)
+    g = _nav_triples(goals)
+    n = len(g)
+    buf = _nav_buf(b.dev)
+    off, need = buf((n + 1,), np.int64), C.c_int64(0)
+    args = b.head(device_id) + (C.byref(prm), f.ptrs, n, _ptr(g) if n else None)
+    _nav_ck(L.c.hmsg_nav_building_paths(*args, _ptr(off), None, 0, C.byref(need)), "hmsg_nav_building_paths")
+    src = buf((max(need.value, 1), 3), np.int32)
+    _nav_ck(L.c.hmsg_nav_building_paths(*args, _ptr(off), _ptr(src), need.value, C.byref(need)), "hmsg_nav_building_paths")
+    return off, src[: need.value]
+
+
+def nav_building_route(main_free_maps, links, start, goals, params=None, device_id=0, lib_: "HmsgLib | None" = None, want_fields=False, **over):
+    """hmsg_nav_building_route: the composition over a building -> dict(start_cell (storey, row, col), start_d2, goal_cell int32
+    [n, 3], goal_d2 int64 [n], goal_dist int32 [n], path_off int64 [n + 1], path_src int32 [k, 3], passable: a list of u8 [rows_l,
+    cols_l]; fields: a list of int32 [rows_l, cols_l] with want_fields).  Device tensors in: device tensors out.  The path list is
+    sized by a first guess and the call repeated once."""
+    L = lib_ or lib()
+    prm = params if params is not None else route_params(L, **over)
+    b = _NavBuilding(main_free_maps, links)
+    st = _nav_triples(start).reshape(3)
+    g = _nav_triples(goals)
+    n = len(g)
+    buf = _nav_buf(b.dev)
+    res = dict(goal_cell=buf((n, 3), np.int32), goal_d2=buf((n,), np.int64), goal_dist=buf((n,), np.int32), path_off=buf((n + 1,), np.int64))
+    passable = [buf((h, w), np.uint8) for h, w in b.shapes]
+    fields = [buf((h, w), np.int32) for h, w in b.shapes] if want_fields else None
+    keep = (b.pointers(passable), b.pointers(fields) if want_fields else None)
+    out = HmsgNavBuildingRoutes()
+    cap = max(1, n) * 2 * int(b.rows.sum() + b.cols.sum())
+    for attempt in range(2):
+        src = buf((max(cap, 1), 3), np.int32)
+        for k, v in res.items():
+            setattr(out, k, _ptr(v))
+        out.path_src, out.path_capacity = _ptr(src), cap
+        out.passable = C.cast(keep[0], C.POINTER(C.c_void_p))
+        if want_fields:
+            out.field = C.cast(keep[1], C.POINTER(C.c_void_p))
+        status = L.c.hmsg_nav_building_route(*b.head(device_id), C.byref(prm), _ptr(st), n, _ptr(g) if n else None, C.byref(out))
+        if status != 0 and attempt == 0 and out.n_path_cells > cap:
+            cap = int(out.n_path_cells)
+            continue
+        _nav_ck(status, "hmsg_nav_building_route")
+        break
+    res.update(path_src=src[: out.n_path_cells], start_cell=tuple(int(v) for v in out.start_cell), start_d2=int(out.start_d2), passable=passable)
+    if want_fields:
+        res["fields"] = fields
     return res
 
 

@@ -28,8 +28,6 @@
 
 #include <climits>
 
-#define NAVR_T 256
-#define NAVR_TILE 64
 #define NAVR_SIDE (NAVR_TILE + 2)
 #define NAVR_LD 67                       // LDS row stride of the field tile in words (odd: see above)
 #define NAVR_PLD 68                      // ... and of the passable bytes
@@ -260,7 +258,9 @@ __global__ __launch_bounds__(64) void k_navr_scan(long long n, const long long* 
 // ------------------------------------------------------------------------------------------ the calls
 namespace {
 thread_local int g_navr_rounds = 0, g_navr_trips = 0;       // what hmsg_test_nav_route_last reports
+}  // namespace
 
+void navr_last_reset() { g_navr_rounds = g_navr_trips = 0; }
 void navr_check(int32_t rows, int32_t cols, const hmsg_route_params& p, const char* fn) {
     const std::string f = fn;
     HMSG_REQUIRE(rows >= 1 && cols >= 1, HMSG_ERR_INVALID, f + ": rows and cols must be at least 1");
@@ -270,6 +270,7 @@ void navr_check(int32_t rows, int32_t cols, const hmsg_route_params& p, const ch
     HMSG_REQUIRE(HW < NAVR_MAX_CELLS, HMSG_ERR_UNSUPPORTED, f + ": the image has 2^28 cells or more");
     HMSG_REQUIRE(HW * p.w_diag < (1ll << 31), HMSG_ERR_UNSUPPORTED, f + ": rows * cols * w_diag reaches 2^31");
 }
+namespace {
 void navr_check_shape(int32_t rows, int32_t cols, const char* fn) {
     hmsg_route_params p;
     hmsg_route_default_params(&p);
@@ -277,10 +278,19 @@ void navr_check_shape(int32_t rows, int32_t cols, const char* fn) {
     navr_check(rows, cols, p, fn);
 }
 
+}  // namespace
+// one round over all tiles of nf fields (hmsg_navroute_dev.h)
+void navr_relax_round(hipStream_t s, int rows, int cols, const unsigned char* d_pass, const hmsg_route_params& p, bool corner, int nf, int* d_field,
+                      int* d_act, int round, unsigned* d_changed) {
+    const dim3 grid(cdiv((size_t)cols, NAVR_TILE), cdiv((size_t)rows, NAVR_TILE), (unsigned)nf);
+    if (corner)
+        hipLaunchKernelGGL(k_navr_relax<true>, grid, dim3(NAVR_T), 0, s, rows, cols, d_pass, p.w_straight, p.w_diag, d_field, d_act, round, d_changed);
+    else
+        hipLaunchKernelGGL(k_navr_relax<false>, grid, dim3(NAVR_T), 0, s, rows, cols, d_pass, p.w_straight, p.w_diag, d_field, d_act, round, d_changed);
+}
 // rounds until no tile is stamped; act: i32 [nf][tiles], stamped 1 where a tile starts
 void navr_relax(hipStream_t s, int rows, int cols, const unsigned char* d_pass, const hmsg_route_params& p, bool corner, int nf, int* d_field,
                 int* d_act) {
-    const dim3 grid(cdiv((size_t)cols, NAVR_TILE), cdiv((size_t)rows, NAVR_TILE), (unsigned)nf);
     constexpr int MAXB = 32;
     DevBuf<unsigned> chg;
     chg.alloc(MAXB);
@@ -288,14 +298,7 @@ void navr_relax(hipStream_t s, int rows, int cols, const unsigned char* d_pass, 
     int round = 1, batch = 4;
     for (;;) {
         HIP_TRY(hipMemsetAsync(chg.p, 0, sizeof(unsigned) * (size_t)batch, s));
-        for (int b = 0; b < batch; ++b) {
-            if (corner)
-                hipLaunchKernelGGL(k_navr_relax<true>, grid, dim3(NAVR_T), 0, s, rows, cols, d_pass, p.w_straight, p.w_diag, d_field, d_act, round + b,
-                                   chg.p + b);
-            else
-                hipLaunchKernelGGL(k_navr_relax<false>, grid, dim3(NAVR_T), 0, s, rows, cols, d_pass, p.w_straight, p.w_diag, d_field, d_act, round + b,
-                                   chg.p + b);
-        }
+        for (int b = 0; b < batch; ++b) navr_relax_round(s, rows, cols, d_pass, p, corner, nf, d_field, d_act, round + b, chg.p + b);
         HMSG_CHECK_LAUNCH();
         HIP_TRY(hipMemcpyAsync(h, chg.p, sizeof(unsigned) * (size_t)batch, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
@@ -307,6 +310,14 @@ void navr_relax(hipStream_t s, int rows, int cols, const unsigned char* d_pass, 
     }
 }
 
+void navr_fill_dev(hipStream_t s, int* d_p, long long n, int v) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_navr_fill, dim3(cdiv((size_t)n, NAVR_T)), dim3(NAVR_T), 0, s, d_p, n, v);
+}
+void navr_scan_dev(hipStream_t s, long long n, const long long* d_cnt, long long* d_off) {
+    hipLaunchKernelGGL(k_navr_scan, dim3(1), dim3(64), 0, s, n, d_cnt, d_off);
+}
+namespace {
 // d_fields i32 [nf][rows][cols] from the sources src_rc[src_off[f] .. src_off[f + 1]) (device memory, cells outside the image skipped)
 void navr_fields_dev(hipStream_t s, int rows, int cols, const unsigned char* d_pass, const hmsg_route_params& p, long long nf_all,
                      const long long* d_src_off, const int* d_src_rc, long long max_sources, int* d_fields, unsigned long long* d_n_reached) {
@@ -343,6 +354,20 @@ void navr_clearance_dev(hipStream_t s, int rows, int cols, const unsigned char* 
 }
 
 }  // namespace
+// hmsg_nav_route's first step: d_pass = the mask where its clearance reaches min_clearance (0: the mask's cells as 1 / 0)
+void navr_passable_dev(hipStream_t s, int rows, int cols, const unsigned char* d_mask, const hmsg_route_params& p, unsigned char* d_pass) {
+    const size_t HW = (size_t)rows * cols;
+    const dim3 gi(cdiv(HW, NAVR_T)), b(NAVR_T);
+    if (p.min_clearance > 0) {
+        DevBuf<int> clr;
+        clr.alloc(HW);
+        navr_clearance_dev(s, rows, cols, d_mask, p, clr.p);
+        hipLaunchKernelGGL(k_navr_threshold, gi, b, 0, s, d_mask, (const int*)clr.p, p.min_clearance, (int)HW, d_pass);
+    } else {
+        hipLaunchKernelGGL(k_navr_binary, gi, b, 0, s, d_mask, (int)HW, d_pass);
+    }
+    HMSG_CHECK_LAUNCH();
+}
 void navr_snap_dev(hipStream_t s, int rows, int cols, const unsigned char* d_pass, const int* d_field, long long n, const int* d_target,
                    int* d_snapped, long long* d_d2) {
     if (n <= 0) return;
@@ -380,11 +405,11 @@ long long navr_paths_dev(hipStream_t s, int rows, int cols, const unsigned char*
     return total;
 }
 
+}  // namespace
 [[noreturn]] void navr_throw_short(const char* fn, long long total, long long capacity) {
     throw hmsg_error{HMSG_ERR_INVALID, std::string(fn) + ": " + std::to_string(total) + " path cells, path_rc holds " + std::to_string(capacity) +
                                            " (the count says what is needed)"};
 }
-}  // namespace
 
 extern "C" void hmsg_route_default_params(hmsg_route_params* p) {
     if (!p) return;
@@ -516,9 +541,9 @@ void navr_route_run(const char* fn, int32_t rows, int32_t cols, const uint8_t* m
     g_navr_rounds = g_navr_trips = 0;
     ScopedStream s(hipStreamNonBlocking);
     const size_t HW = (size_t)rows * cols, n = (size_t)n_goals;
-    const dim3 gi(cdiv(HW, NAVR_T)), b(NAVR_T);
+    const dim3 b(NAVR_T);
     DevBuf<unsigned char> own_mask, own_pass;
-    DevBuf<int> clr, own_field, own_start, own_goal, own_cell, own_dist, start;
+    DevBuf<int> own_field, own_start, own_goal, own_cell, own_dist, start;
     DevBuf<long long> own_d2, d_off, src_off, start_d2;
     const unsigned char* d_mask = stage_in(own_mask, main_free_map, HW, s, Up::bounce);
     const int* d_start = stage_in(own_start, start_rc, 2, s, Up::direct);
@@ -526,14 +551,7 @@ void navr_route_run(const char* fn, int32_t rows, int32_t cols, const uint8_t* m
     // 1. passable
     unsigned char* d_pass = stage_out(own_pass, out->passable, HW);
     if (!d_pass) own_pass.alloc(HW), d_pass = own_pass.p;
-    if (prm->min_clearance > 0) {
-        clr.alloc(HW);
-        navr_clearance_dev(s, rows, cols, d_mask, *prm, clr.p);
-        hipLaunchKernelGGL(k_navr_threshold, gi, b, 0, s, d_mask, (const int*)clr.p, prm->min_clearance, (int)HW, d_pass);
-    } else {
-        hipLaunchKernelGGL(k_navr_binary, gi, b, 0, s, d_mask, (int)HW, d_pass);
-    }
-    HMSG_CHECK_LAUNCH();
+    navr_passable_dev(s, rows, cols, d_mask, *prm, d_pass);
     // 2. the start, 3. its field
     start.alloc(2), start_d2.alloc(1), src_off.alloc(2);
     navr_snap_dev(s, rows, cols, d_pass, nullptr, 1, d_start, start.p, start_d2.p);

@@ -1461,6 +1461,94 @@ class Graph:
                 out[k].update(r, reason=None if r["reachable"] else ("unreachable" if nothing_reached else "no view"))
         return out
 
+    # ------------------------------------------------------------------ N9: routes across storeys (no counterpart in the reference)
+    def stair_links(self, poses_list=None, min_clearance=0.25):
+        """The links (include/hmsg.h, B2) between consecutive storeys, one per stairs that the camera track shows
+        (NavigationGraph.stairs_pose_track, the track create_nav_graph's stairs graph is made of): nav_graph.stair_link of the
+        track on the two storeys' maps, its ends snapped to cells with min_clearance metres of free space."""
+        from .nav_graph import NavigationGraph, stair_link
+        poses = self._nav_poses(poses_list)
+        links = []
+        for f in range(len(self.floors) - 1):
+            track = NavigationGraph.stairs_pose_track(f, poses)
+            if track is None or len(track) == 0:
+                continue
+            link, _ = stair_link(self.floor_navigation(f, poses), self.floor_navigation(f + 1, poses), track, f, f + 1, min_clearance)
+            if link is not None:
+                links.append(link)
+        return links
+
+    def building_navigation(self, poses_list=None, min_clearance=0.25, links=None):
+        """The BuildingNavigation of all storeys (floor_navigation of each) joined by stair_links, made once and kept.  links: a
+        link list of the caller's in place of the stairs found in the track; such a building is made anew and not kept."""
+        from .nav_graph import BuildingNavigation
+        if links is not None:
+            return BuildingNavigation([self.floor_navigation(f, poses_list) for f in range(len(self.floors))], links, lib_=self.L)
+        if self.__dict__.get("_building_nav") is None:
+            storeys = [self.floor_navigation(f, poses_list) for f in range(len(self.floors))]
+            self._building_nav = BuildingNavigation(storeys, self.stair_links(poses_list, min_clearance), lib_=self.L)
+        return self._building_nav
+
+    def _across_floors(self, start_pose, objects, floor_id):
+        pose = np.asarray(start_pose, np.float64)
+        f = int(floor_id) if floor_id is not None else self.floor_of_pose(pose)
+        if f is None:
+            raise ValueError("the start pose lies on no storey")
+        centres, floors = [], []
+        for o in objects:
+            node = self.objects[int(o)] if isinstance(o, (int, np.integer)) else o
+            c = np.asarray(node.pcd.get_center() if hasattr(node, "pcd") else node, np.float64).reshape(3)
+            centres.append(c)
+            floors.append(self._floor_of_object(node, c))
+        return pose, f, np.array(centres, np.float64).reshape(-1, 3), floors
+
+    @staticmethod
+    def _across_reason(r, nothing_reached, storey_reached):
+        if r["reachable"]:
+            return None
+        if nothing_reached:
+            return "unreachable"
+        return "no view" if storey_reached else "no stairs"
+
+    def route_across_floors(self, start_pose, objects, floor_id=None, min_clearance=0.25, poses_list=None, links=None):
+        """route_to_objects over the whole building (include/hmsg.h: hmsg_nav_building_route, on the device): an object of another
+        storey is routed through the stairs' links (building_navigation; links: the caller's own list).  Per object
+        route_to_objects' dict plus `floors` (the storey of every polyline point) and `cells`; floor_id is the object's storey.
+        reason: None, "unreachable" (the start reaches no cell at all) or "no stairs" (no cell of the object's storey is
+        reached from the start)."""
+        pose, f, centres, floors = self._across_floors(start_pose, objects, floor_id)
+        if not len(objects):
+            return []
+        nav = self.building_navigation(poses_list, min_clearance, links)
+        routes = nav.route(f, pose[:3, 3], centres, floors, min_clearance_m=min_clearance)
+        nothing = nav.last_route["start_cell"][1] < 0
+        out = []
+        for k, (o, r) in enumerate(zip(objects, routes)):
+            r.pop("floor")
+            out.append(dict(r, object=o, floor_id=floors[k], reason=self._across_reason(r, nothing, False)))
+        return out
+
+    def view_routes_across_floors(self, start_pose, objects, floor_id=None, min_clearance=0.25, view_range=(0.5, 3.0), prefer="walk",
+                                  poses_list=None, links=None):
+        """view_routes_to_objects over the whole building (BuildingNavigation.route_to_view): the cell stood on sees the object on the
+        object's own storey.  reason: None, "unreachable", "no stairs" or "no view" (cells of the object's storey are reached,
+        none of them sees it within the range)."""
+        from ._lib import NAV_UNREACHED
+        pose, f, centres, floors = self._across_floors(start_pose, objects, floor_id)
+        if not len(objects):
+            return []
+        nav = self.building_navigation(poses_list, min_clearance, links)
+        routes = nav.route_to_view(f, pose[:3, 3], centres, floors, min_clearance_m=min_clearance, view_range_m=view_range, prefer=prefer)
+        last = nav.last_route
+        nothing = last["start_cell"][1] < 0
+        out = []
+        for k, (o, r) in enumerate(zip(objects, routes)):
+            fld = None if nothing else last["fields"][floors[k]]
+            reached = fld is not None and bool((fld != NAV_UNREACHED).any())
+            r.pop("floor")
+            out.append(dict(r, object=o, floor_id=floors[k], reason=self._across_reason(r, nothing, reached)))
+        return out
+
     # ------------------------------------------------------------------ A11: graph.py:1752-1775
     def create_graph_new(self):
         """Building(0) - Floor - Room - Object, Room - View, View - Object.  As in the reference, `room.room_id ==

@@ -65,6 +65,7 @@ class NavigationGraph:
         self.map = None
         self.top_down = None
         self.sparse_floor_voronoi = None
+        self.zero_level = None
 
     # ---- the grid
     def to_grid(self, world_coords):
@@ -83,6 +84,7 @@ class NavigationGraph:
     # ---- the image half: one device call, kept for all the map getters
     def floor_maps(self, floor_info, floor_poses_list, **params):
         poses = np.asarray(floor_poses_list, np.float64).reshape(-1, 4, 4)
+        self.zero_level = float(floor_info["floor_zero_level"])
         if self.slab is not None:
             self.maps = self.slab.scene.nav_floor_maps(self.slab.y_lo, self.slab.y_hi, float(floor_info["floor_zero_level"]), poses,
                                                        cell_size=self.cell_size, **params)
@@ -358,28 +360,12 @@ class NavigationGraph:
         down) is cut from where it last leaves the lower peak's bin to where it first passes the upper peak, 5 poses added in
         front and 20 behind; the chain is sparsified.  No upper peak: an empty graph and has_stairs False."""
         import networkx as nx
-        from scipy.signal import find_peaks
         zero = floor.floor_zero_level
-        heights = np.array([p[1, 3] - 1.5 for p in poses_list])
-        counts, edges = np.histogram(heights, bins=100)
-        padded = np.concatenate([[np.min(counts)], counts, [np.min(counts)]])
-        peaks = find_peaks(padded, height=0.3 * np.max(counts))[0] - 1
-        if floor_id >= len(peaks) - 1:
+        poses = self.stairs_pose_track(floor_id, poses_list)
+        if poses is None:
             self.has_stairs = False
             return nx.Graph()
-        h_lo, h_hi = edges[peaks[int(floor_id)] + 1], edges[peaks[int(floor_id) + 1]]
-        if heights[0] > heights[-1]:
-            heights, poses_list = heights[::-1], poses_list[::-1]
-        first_low = 0
-        if heights[0] > h_lo:
-            first_low = next((i for i, h in enumerate(heights) if h <= h_lo), 0)
-        st = next((i for i, h in enumerate(heights) if h > h_lo and i > first_low), None)
-        ed = next((i for i, h in enumerate(heights) if h > h_hi), None)
-        for i in range(st, ed):
-            if heights[i] < h_lo:
-                st = i
-        st, ed = np.max([st - 5, 0]), ed + 20
-        track = [p[:3, 3] for p in poses_list[st:ed]]
+        track = [p[:3, 3] for p in poses]
         if not track:
             self.has_stairs = False
             return nx.Graph()
@@ -395,6 +381,31 @@ class NavigationGraph:
         sparse = self.sparsify_graph(chain, resampling_dist=0.4)
         self.has_stairs = True
         return sparse
+
+    @staticmethod
+    def stairs_pose_track(floor_id, poses_list):
+        """The poses of the stairs above floor `floor_id`, as get_stairs_graph_with_poses_v2 cuts them from the camera track (see
+        there): poses_list[st:ed] of the track in climbing order, or None when the pose heights show no storey above."""
+        from scipy.signal import find_peaks
+        heights = np.array([p[1, 3] - 1.5 for p in poses_list])
+        counts, edges = np.histogram(heights, bins=100)
+        padded = np.concatenate([[np.min(counts)], counts, [np.min(counts)]])
+        peaks = find_peaks(padded, height=0.3 * np.max(counts))[0] - 1
+        if floor_id >= len(peaks) - 1:
+            return None
+        h_lo, h_hi = edges[peaks[int(floor_id)] + 1], edges[peaks[int(floor_id) + 1]]
+        if heights[0] > heights[-1]:
+            heights, poses_list = heights[::-1], poses_list[::-1]
+        first_low = 0
+        if heights[0] > h_lo:
+            first_low = next((i for i, h in enumerate(heights) if h <= h_lo), 0)
+        st = next((i for i, h in enumerate(heights) if h > h_lo and i > first_low), None)
+        ed = next((i for i, h in enumerate(heights) if h > h_hi), None)
+        for i in range(st, ed):
+            if heights[i] < h_lo:
+                st = i
+        st, ed = np.max([st - 5, 0]), ed + 20
+        return poses_list[st:ed]
 
     def get_floor_graph(self, floor, floor_poses_list, floor_dir=None, **params):
         info = {"floor_zero_level": floor.floor_zero_level, "floor_height": getattr(floor, "floor_height", None)}
@@ -428,3 +439,156 @@ class NavigationGraph:
         import networkx as nx
         with open(os.path.join(floor_dir, f"{name}_graph.json"), "w") as f:
             json.dump(nx.node_link_data(graph, edges="links"), f, indent=4)
+
+
+# ---- routes across storeys (include/hmsg.h, N9: the rules B1 to B6; no counterpart in the reference)
+def _host(v):
+    return v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)
+
+
+def stair_link(lower_nav, upper_nav, track, lower_id=0, upper_id=1, min_clearance_m=0.0, w_straight=5):
+    """The link (B2) that a stairs' pose track (NavigationGraph.stairs_pose_track: camera-to-world poses in climbing order, or
+    positions [n, 3]) makes between two storeys: the first position's cell by R6 on the lower storey's grid and the last one's on
+    the upper storey's, each snapped by R4 to its storey's passable_map(min_clearance_m); cost = max(1, ceil(track length in metres
+    * w_straight / cell_size)).  -> (link (sa, ra, ca, sb, rb, cb, cost) or None when a storey has no passable cell, (d2 of the
+    lower snap, d2 of the upper snap))"""
+    pos = np.array([np.asarray(p, np.float64)[:3, 3] if np.ndim(p) == 2 else np.asarray(p, np.float64).reshape(3) for p in track], np.float64)
+    assert len(pos) >= 1, "an empty track makes no link"
+    length = float(np.sqrt(((pos[1:] - pos[:-1]) ** 2).sum(axis=1)).sum())
+    cost = max(1, int(np.ceil(length * w_straight / lower_nav.cell_size)))
+    ends = []
+    for nav, p in ((lower_nav, pos[0]), (upper_nav, pos[-1])):
+        cell, d2 = _lib.nav_snap_cells(nav.passable_map(min_clearance_m, w_straight=w_straight), nav.cells_of(p), lib_=nav.L,
+                                       device_id=nav.device_id)
+        ends.append((tuple(int(v) for v in _host(cell)[0]), int(_host(d2)[0])))
+    (a, da), (b, db) = ends
+    if a[0] < 0 or b[0] < 0:
+        return None, (da, db)
+    return (int(lower_id),) + a + (int(upper_id),) + b + (cost,), (da, db)
+
+
+class BuildingNavigation:
+    """Several storeys' NavigationGraph objects (their maps made) and the links between them (B2: (storey_a, row_a, col_a,
+    storey_b, row_b, col_b, cost) in field units, stair_link makes one): fields, routes and routes to a viewpoint over the whole
+    building, on the device (hmsg_nav_building_fields / _route / _paths).  The storeys share one cell size; their grids are their
+    own.  A link's endpoints are meant for the clearance the routes are asked with: a link whose endpoint is not passable at a
+    larger clearance does not exist there."""
+
+    def __init__(self, storeys, links, lib_=None):
+        assert len(storeys) >= 1 and all(n.maps is not None for n in storeys), "get_main_free_map makes a storey's maps"
+        assert all(n.cell_size == storeys[0].cell_size for n in storeys), "one cell size for the building"
+        self.storeys = list(storeys)
+        self.links = [tuple(int(v) for v in l) for l in links]
+        self.L = lib_ or storeys[0].L
+        self.device_id = storeys[0].device_id
+        self.cell_size = storeys[0].cell_size
+        self.last_route = None
+
+    def _level(self, l):
+        nav = self.storeys[l]
+        return nav.zero_level if nav.zero_level is not None else float(nav.pcd_min[1])
+
+    def world(self, triples):
+        """cell centres of (storey, row, col) triples in world coordinates, y = the storey's zero level -> float64 [n, 3]"""
+        t = np.asarray(triples, np.int64).reshape(-1, 3)
+        out = np.zeros((len(t), 3), np.float64)
+        for k, (l, r, c) in enumerate(t):
+            nav = self.storeys[l]
+            out[k] = ((c + 0.5) * nav.cell_size + nav.pcd_min[0], self._level(l), (r + 0.5) * nav.cell_size + nav.pcd_min[2])
+        return out
+
+    def triples_of(self, floors, xyz_or_rc):
+        """(storey, row, col) int32 [n, 3] of world points (or cells) on the given storeys, by R6 on each storey's own grid"""
+        a = _host(xyz_or_rc)
+        a = a.reshape(-1, a.shape[-1]) if a.ndim > 1 else a.reshape(1, -1)
+        floors = np.broadcast_to(np.asarray(floors, np.int64).reshape(-1), (len(a),))
+        out = np.zeros((len(a), 3), np.int32)
+        for k, l in enumerate(floors):
+            out[k] = (l,) + tuple(self.storeys[int(l)].cells_of(a[k])[0])
+        return out
+
+    def passables(self, min_clearance_m=0.0, **weights):
+        return [n.passable_map(min_clearance_m, **weights) for n in self.storeys]
+
+    def fields(self, start_floor, start_xyz_or_rc, min_clearance_m=0.0, **weights):
+        """B3 from the start as it is (a world point or a cell of storey start_floor; no snap): one int32 [rows_l, cols_l] per
+        storey, where the maps are"""
+        f, _ = _lib.nav_building_fields(self.passables(min_clearance_m, **weights), self.links, self.triples_of(start_floor, start_xyz_or_rc),
+                                        lib_=self.L, device_id=self.device_id, **weights)
+        return [x[0] for x in f]
+
+    def _dicts(self, r, ws):
+        out = []
+        for k, cell in enumerate(r["goal_cell"]):
+            ok = bool(cell[1] >= 0 and r["goal_dist"][k] != _lib.NAV_UNREACHED)
+            src = r["path_src"][r["path_off"][k]:r["path_off"][k + 1]]
+            out.append(dict(point=self.world(cell)[0] if ok else None, cell=(int(cell[1]), int(cell[2])), floor=int(cell[0]), reachable=ok,
+                            length_m=float(r["goal_dist"][k]) * self.cell_size / ws if ok else None,
+                            snap_m=float(np.sqrt(float(r["goal_d2"][k]))) * self.cell_size if ok else None,
+                            polyline=self.world(src), floors=np.ascontiguousarray(src[:, 0].astype(np.int32)),
+                            cells=np.ascontiguousarray(src[:, 1:].astype(np.int32))))
+        return out
+
+    def route(self, start_floor, start_xyz, goals_xyz, goal_floors, min_clearance_m=0.0, **weights):
+        """hmsg_nav_building_route from start_xyz on storey start_floor to every goal (world points or cells, goal_floors: their
+        storeys): NavigationGraph.route's dict per goal -- point, cell, reachable, length_m, snap_m, polyline [k, 3] (world
+        coordinates at each storey's zero level) -- plus `floor` (the cell's storey), and `floors` int32 [k] and `cells` int32
+        [k, 2] beside the polyline"""
+        ws = int(weights.get("w_straight", 5))
+        maps = [n.maps["main_free_map"] for n in self.storeys]
+        r = _lib.nav_building_route(maps, self.links, self.triples_of(start_floor, start_xyz)[0], self.triples_of(goal_floors, goals_xyz),
+                                    lib_=self.L, device_id=self.device_id, min_clearance=self.storeys[0].clearance_units(min_clearance_m, ws),
+                                    **weights)
+        r = {k: ([_host(x) for x in v] if isinstance(v, list) else (_host(v) if hasattr(v, "cpu") else v)) for k, v in r.items()}
+        self.last_route = r
+        return self._dicts(r, ws)
+
+    def route_to_view(self, start_floor, start_xyz, goals_xyz, goal_floors, min_clearance_m=0.0, view_range_m=(0.0, 3.0), prefer="walk",
+                      **weights):
+        """route with the cell stood on chosen so that the goal is in sight on its own storey (composed, no device code of its own):
+        the start is snapped by R4, its building field made (B3), and each storey's part of it handed to hmsg_nav_viewpoints as
+        the `field` with that storey's sight_blocking_map (V4: least walk from the START, or closest look); then B5 to the
+        viewpoints.  route's dict plus n_visible, facing and yaw as NavigationGraph.route_to_view gives them."""
+        ws = int(weights.get("w_straight", 5))
+        pas = self.passables(min_clearance_m, **weights)
+        st = self.triples_of(start_floor, start_xyz)[0]
+        goals = self.triples_of(goal_floors, goals_xyz)
+        cell, d2 = _lib.nav_snap_cells(pas[int(st[0])], st[1:], lib_=self.L, device_id=self.device_id)
+        cell, d2 = _host(cell), _host(d2)
+        n = len(goals)
+        r = dict(start_cell=(int(st[0]), int(cell[0, 0]), int(cell[0, 1])), start_d2=int(d2[0]), goal_cell=np.full((n, 3), -1, np.int32),
+                 goal_d2=np.full(n, -1, np.int64), goal_dist=np.full(n, _lib.NAV_UNREACHED, np.int32), n_visible=np.zeros(n, np.int32))
+        r["goal_cell"][:, 0] = goals[:, 0]
+        if cell[0, 0] >= 0:
+            fields = self.fields(int(st[0]), cell[0], min_clearance_m, **weights)
+        else:
+            fields = None
+        if fields is not None:
+            for l in sorted(set(int(v) for v in goals[:, 0])):
+                nav = self.storeys[l]
+                sel = np.flatnonzero(goals[:, 0] == l)
+                r_min2, r_max2 = nav.view_band(view_range_m)
+                v = _lib.nav_viewpoints(nav.sight_blocking_map(), pas[l], goals[sel, 1:], field=fields[l], lib_=self.L, device_id=self.device_id,
+                                        r_min2=r_min2, r_max2=r_max2, prefer=nav._prefer(prefer))
+                r["goal_cell"][sel, 1:] = _host(v["view_rc"])
+                r["goal_d2"][sel], r["goal_dist"][sel], r["n_visible"][sel] = _host(v["view_d2"]), _host(v["view_dist"]), _host(v["n_visible"])
+            off, src = _lib.nav_building_paths(pas, self.links, fields, r["goal_cell"], lib_=self.L, device_id=self.device_id, **weights)
+            r["path_off"], r["path_src"] = _host(off), _host(src)
+            r["fields"] = fields
+        else:
+            r["path_off"], r["path_src"] = np.zeros(n + 1, np.int64), np.zeros((0, 3), np.int32)
+        r["passable"] = pas
+        self.last_route = r
+        out = self._dicts(r, ws)
+        g = _host(goals_xyz).astype(np.float64)
+        g = g.reshape(-1, g.shape[-1]) if g.ndim > 1 else g.reshape(1, -1)
+        goal_points = g if g.shape[1] == 3 else self.world(goals)
+        for k, d in enumerate(out):
+            d["n_visible"] = int(r["n_visible"][k])
+            d["facing"] = d["yaw"] = None
+            if d["reachable"]:
+                v = np.array([goal_points[k, 0] - d["point"][0], goal_points[k, 2] - d["point"][2]], np.float64)
+                same = d["cell"] == (int(goals[k, 1]), int(goals[k, 2]))
+                d["facing"] = np.zeros(2) if same or not v.any() else v / np.sqrt(v[0] * v[0] + v[1] * v[1])
+                d["yaw"] = float(np.arctan2(d["facing"][0], d["facing"][1]))
+        return out

@@ -1382,6 +1382,80 @@ int hmsg_nav_view_route(int32_t device_id, int32_t rows, int32_t cols, const uin
                         const hmsg_route_params* route_prm, const hmsg_view_params* view_prm, const int32_t* start_rc, int64_t n_goals,
                         const int32_t* goal_rc, hmsg_nav_routes* out, int32_t* n_visible /* i32 [n_goals], may be NULL */);
 
+/* ---- N9: routes across storeys (csrc/hmsg_navbuilding.hip): exact fields over several maps that are joined at a few cells (stairs,
+ * a lift), the goals' cells and the cells of the way through such joins.  The reference has no such stage (its global navigation
+ * graph joins two floors by one Voronoi edge; goal_pose_publisher.py:260-271 publishes an object's centre), so the rules are this
+ * library's.  Images, cells, weights and memory conventions are N7's; R1 to R6 hold on every storey.  All of it is integer work:
+ * every output has one right answer.  The rules:
+ *  B1. Seeded field: seeds are cells with an int32 cost >= 0.  field[c] = the minimum over the seeds s of cost_s + the least cost
+ *      of a legal R1 walk from s to c.  A seed on a cell that is not passable is no seed; duplicate seeds on one cell count with
+ *      their least cost; with no seed every cell is HMSG_NAV_UNREACHED.  hmsg_nav_distance_fields is the case of every cost 0.
+ *  B2. Building: n_storeys maps, each with its own rows_l, cols_l and passable_l, and n_links links (storey_a, cell_a, storey_b,
+ *      cell_b, cost), cost >= 1, written as seven int32: sa, ra, ca, sb, rb, cb, cost.  A link is walked in both directions at
+ *      that cost.  A link with an endpoint on a cell that is not passable does not exist.  storey_a == storey_b is allowed (a
+ *      lift, a door the map does not show).  The building's graph is the disjoint union of the storeys' R1 grid graphs plus the
+ *      links.
+ *  B3. Building field: for a start (storey, cell), field_l[c] = the least cost in that graph from the start to cell c of storey
+ *      l, for every storey l.  A storey that no chain of links reaches is all unreached; a start on a cell that is not passable
+ *      gives all-unreached fields everywhere.  n_reached counts the finite cells per start and per storey.
+ *  B4. Goal: a goal is (storey, cell); its snap is R4 on its own storey among the cells whose building field is finite.  No
+ *      candidate on that storey: cell (-1, -1), d2 = -1, dist = HMSG_NAV_UNREACHED.
+ *  B5. Path: (storey, row, col) triples from the start to the goal, both included, emitted reversed as in R5.  From the goal, first
+ *      R5's step on the same storey: the first neighbour in R1's order whose move is legal and whose field + w equals the value
+ *      here.  If there is none, step through the first link in index order that exists (B2), has an endpoint here and whose other
+ *      endpoint o has field[o] + cost == the value here; for one link the walk a -> b (here is b, o is a) is tried before b -> a.
+ *      Stop at value 0.  If neither step exists the path is empty, as it is for a goal that is unreached, not passable or outside
+ *      its image.  Every step lowers the value by at least 1, so the walk ends.
+ *  B6. Limits: 1 <= n_storeys <= 256, 0 <= n_links < 2^20, every storey within N7's shape limits.  HMSG_ERR_UNSUPPORTED when
+ *      w_diag * (the sum of rows_l * cols_l) + (the sum of the links' costs) reaches 2^31; for B1 when max seed cost + rows * cols *
+ *      w_diag does.  Below these bounds no finite value overflows.  Refused with HMSG_ERR_INVALID: a link, start or goal with a
+ *      storey index out of range; a link endpoint, seed or start with a cell index outside its image (the starts of
+ *      hmsg_nav_building_fields: hmsg_nav_building_route snaps its start, whose cell may lie anywhere, as a goal's may); a cost
+ *      < 1 of a link or < 0 of a seed; a null required pointer; N7's refusals of the weights.
+ * Every array may be host or device memory; the structs and the arrays of pointers (rows, cols, passable, fields) are host
+ * memory; links, seeds, starts and goals are read and checked by the host before anything runs.  n_reached, path_off, path_src
+ * and every pointer of hmsg_nav_building_routes may be NULL as N7's may; a path list that is too short behaves as in
+ * hmsg_nav_route.  hmsg_nav_building_route is the composition and only that: per storey passable = main_free_map where its
+ * clearance reaches min_clearance, exactly as hmsg_nav_route does it; the start (storey, cell) is snapped by R4 on its storey
+ * with no field; B3 for that one start; B4 per goal; B5 to the snapped cells.  With one storey and no link every output equals
+ * hmsg_nav_route's, the triples carrying storey 0. */
+typedef struct hmsg_nav_building_routes {
+    int32_t* goal_cell;           /* i32 [n_goals][3]: the goal's storey and its snapped cell, (-1, -1) when nothing is reached there */
+    int64_t* goal_d2;             /* i64 [n_goals] */
+    int32_t* goal_dist;           /* i32 [n_goals]: the building field at the snapped cell */
+    int64_t* path_off;            /* i64 [n_goals + 1] */
+    int32_t* path_src;            /* i32 [path_capacity][3]: storey, row, col */
+    int64_t  path_capacity;
+    int32_t** field;              /* NULL, or n_storeys pointers (each NULL or i32 [rows_l][cols_l]): the start's building field */
+    uint8_t** passable;           /* NULL, or n_storeys pointers (each NULL or u8 [rows_l][cols_l]) */
+    /* out */
+    int64_t  n_path_cells;
+    int64_t  start_d2;            /* R4's d2 of the start's snap; -1: no passable cell on its storey */
+    int32_t  start_cell[3];       /* storey, row, col */
+    int32_t  reserved_;
+} hmsg_nav_building_routes;
+/* B1, batched like hmsg_nav_distance_fields: the seeds seed_rc / seed_cost [seed_off[s] .. seed_off[s + 1]) make fields[s] */
+int hmsg_nav_seeded_fields(int32_t device_id, int32_t rows, int32_t cols, const uint8_t* passable, const hmsg_route_params* prm,
+                           int32_t n_fields, const int64_t* seed_off /* [n_fields + 1] */, const int32_t* seed_rc /* [m][2] */,
+                           const int32_t* seed_cost /* [m] */, int32_t* fields /* [n_fields][rows][cols] */,
+                           int64_t* n_reached /* [n_fields], may be NULL */);
+/* B3 for n_starts starts in one call */
+int hmsg_nav_building_fields(int32_t device_id, int32_t n_storeys, const int32_t* rows, const int32_t* cols,
+                             const uint8_t* const* passable /* n_storeys pointers */, int32_t n_links,
+                             const int32_t* links /* i32 [n_links][7]: sa, ra, ca, sb, rb, cb, cost */, const hmsg_route_params* prm,
+                             int32_t n_starts, const int32_t* start /* i32 [n_starts][3]: storey, row, col */,
+                             int32_t* const* fields /* one pointer per storey: i32 [n_starts][rows_l][cols_l] */,
+                             int64_t* n_reached /* i64 [n_starts][n_storeys], may be NULL */);
+/* B5 on the building field of one start (fields: one pointer per storey, i32 [rows_l][cols_l]) */
+int hmsg_nav_building_paths(int32_t device_id, int32_t n_storeys, const int32_t* rows, const int32_t* cols, const uint8_t* const* passable,
+                            int32_t n_links, const int32_t* links, const hmsg_route_params* prm, const int32_t* const* fields,
+                            int64_t n_goals, const int32_t* goals /* i32 [n_goals][3] */, int64_t* path_off /* [n_goals + 1] */,
+                            int32_t* path_src /* i32 [capacity][3] */, int64_t capacity, int64_t* n_needed);
+int hmsg_nav_building_route(int32_t device_id, int32_t n_storeys, const int32_t* rows, const int32_t* cols,
+                            const uint8_t* const* main_free_map /* n_storeys pointers */, int32_t n_links, const int32_t* links,
+                            const hmsg_route_params* prm, const int32_t* start /* i32 [3] */, int64_t n_goals,
+                            const int32_t* goals /* i32 [n_goals][3] */, hmsg_nav_building_routes* out);
+
 
 #ifdef __cplusplus
 }

@@ -126,6 +126,10 @@ int hmsg_test_nav_last(int32_t* label_rounds);
 /* the relaxation rounds that changed a tile and the host round trips (one read-back per batch of rounds) of this thread's last
  * hmsg_nav_clearance / hmsg_nav_distance_fields / hmsg_nav_route call.  Either pointer may be NULL. */
 int hmsg_test_nav_route_last(int32_t* rounds, int32_t* round_trips);
+/* the rounds (one relaxation launch per storey plus one link launch) in which a tile or a link changed, and the host round trips
+ * (one read-back per batch of rounds), of this thread's last hmsg_nav_building_fields / hmsg_nav_building_route call.  Either
+ * pointer may be NULL. */
+int hmsg_test_nav_building_last(int32_t* rounds, int32_t* round_trips);
 
 /* measurement hook: the queries that the process's last hmsg_knn_labels call (hmsg_evaluate_semseg's included) finished by scan
  * (phase 2) -- all of them under HMSG_DEBUG_KNN_BRUTE=1. */
