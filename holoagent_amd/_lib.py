@@ -118,6 +118,10 @@ class HmsgViewParams(C.Structure):      # include/hmsg.h: hmsg_view_params
     _fields_ = [("r_min2", C.c_int64), ("r_max2", C.c_int64), ("prefer", C.c_int32), ("reserved_", C.c_int32)]
 
 
+class HmsgHeightParams(C.Structure):    # include/hmsg.h: hmsg_height_params
+    _fields_ = [("cell_size", C.c_double), ("height_unit", C.c_double), ("top_max", C.c_double), ("dilation", C.c_int32), ("reserved_", C.c_int32)]
+
+
 class HmsgError(RuntimeError):
     pass
 
@@ -167,6 +171,13 @@ _SIGS = {
     "hmsg_view_default_params": (None, [_P]),
     "hmsg_nav_viewpoints": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P]),
     "hmsg_nav_view_route": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int64, _P, _P, _P]),
+    "hmsg_height_default_params": (None, [_P]),
+    "hmsg_nav_height_map": (C.c_int, [C.c_int32, _P, C.c_int64, _P, C.c_double, _P, _P, _P, _P, _P]),
+    "hmsg_graph_nav_height_map": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    "hmsg_map_nav_height_map": (C.c_int, [_P, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P]),
+    "hmsg_nav_viewpoints_h": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "hmsg_nav_view_route_h": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, _P, C.c_int64, _P, _P, _P, _P, _P]),
+    "hmsg_test_nav_sight_layout": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "hmsg_get_frame_num_masks": (C.c_int32, [_P, C.c_int32]),
     "hmsg_fuse_frames": (C.c_int, [_P]),
     "hmsg_get_map_feats": (C.c_int, [_P, _P, _P]),
@@ -1121,6 +1132,14 @@ class Scene:
             self.L.c.hmsg_map_nav_floor_maps(self.h, float(y_lo), float(y_hi), float(zero_level), C.byref(prm), len(P_),
                                              _ptr(P_) if len(P_) else None, C.byref(out))))
 
+    def nav_height_map(self, y_lo, y_hi, zero_level, params=None, **over):
+        """The height map of a slab of the map (include/hmsg.h, N10: hmsg_map_nav_height_map), selected on the device -> the dict
+        of nav_height_map."""
+        prm = params if params is not None else height_params(self.L, **over)
+        _, _, (W, H) = self.nav_grid(y_lo, y_hi, prm.cell_size)
+        return _height_call(H, W, None, lambda top, known, mn, mx, grid: self._ck(
+            self.L.c.hmsg_map_nav_height_map(self.h, float(y_lo), float(y_hi), float(zero_level), C.byref(prm), top, known, mn, mx, grid)))
+
     def segment_floors(self):
         """A8 behind the C ABI (include/hmsg.h: hmsg_segment_floors) -> list of dicts (y_lo, y_hi, zero_level, height,
         bbox_min, bbox_max, n_points)."""
@@ -1419,6 +1438,14 @@ class SceneGraph:
         P_ = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 16))
         return _nav_call(H, W, top_down, lambda out: self._ck(
             self.L.c.hmsg_graph_nav_floor_maps(self.g, int(floor), C.byref(prm), len(P_), _ptr(P_) if len(P_) else None, C.byref(out))))
+
+    def nav_height_map(self, floor, params=None, **over):
+        """The height map of storey `floor` (include/hmsg.h, N10: hmsg_graph_nav_height_map), zero_level the floor's own -> the dict
+        of nav_height_map."""
+        prm = params if params is not None else height_params(self.L, **over)
+        _, _, (W, H) = self.nav_grid(floor, prm.cell_size)
+        return _height_call(H, W, None, lambda top, known, mn, mx, grid: self._ck(
+            self.L.c.hmsg_graph_nav_height_map(self.g, int(floor), C.byref(prm), top, known, mn, mx, grid)))
 
     def index(self, room_name_emb=None):
         ix = _P()
@@ -2298,6 +2325,131 @@ def nav_view_route(main_free_map, blocking, start_rc, goals_rc, params=None, vie
             cap = int(out.n_path_cells)
             continue
         _nav_ck(status, "hmsg_nav_view_route")
+        break
+    res.update(path_rc=rc[: out.n_path_cells], start_cell=(int(out.start_cell[0]), int(out.start_cell[1])), start_d2=int(out.start_d2),
+               n_visible=n_visible)
+    return res
+
+
+# ---- N10: a storey's height map and sight with heights (include/hmsg.h states the rules H1 to H3 and S1 to S5)
+def height_params(lib_: "HmsgLib | None" = None, **over):
+    """hmsg_height_params with the defaults (cell_size 0.03, height_unit 0.01, top_max 2.5, dilation 5), fields overridden by keyword"""
+    L = lib_ or lib()
+    p = HmsgHeightParams()
+    L.c.hmsg_height_default_params(C.byref(p))
+    for k, v in over.items():
+        if k not in ("cell_size", "height_unit", "top_max", "dilation"):
+            raise HmsgError(f"unknown hmsg_height_params field {k}")
+        setattr(p, k, int(v) if k == "dilation" else float(v))
+    return p
+
+
+def _height_call(H, W, device, call):
+    """allocates top and known (numpy, or torch tensors on `device`) and runs call(top, known, pcd_min, pcd_max, grid) on their pointers"""
+    buf = _nav_buf(device)
+    top, known = buf((H, W), np.uint16), buf((H, W), np.uint8)
+    mn, mx, grid = np.zeros(3), np.zeros(3), np.zeros(2, np.int32)
+    call(_ptr(top), _ptr(known), _ptr(mn), _ptr(mx), _ptr(grid))
+    assert (int(grid[0]), int(grid[1])) == (W, H)
+    return dict(top=top, known=known, grid=(W, H), pcd_min=mn, pcd_max=mx)
+
+
+def nav_height_map(points, zero_level, params=None, device_id=0, lib_: "HmsgLib | None" = None, **over):
+    """H1 to H3: the height map of a storey's cloud (hmsg_nav_height_map).  points float64 [n, 3], numpy or a device tensor (then
+    the maps are device tensors) -> dict(top u16 [rows, cols] in height units above zero_level, known u8 [rows, cols], grid
+    (columns, rows), pcd_min, pcd_max).  params: an HmsgHeightParams, or fields by keyword."""
+    L = lib_ or lib()
+    prm = params if params is not None else height_params(L, **over)
+    on_dev = _is_dev(points)
+    if on_dev:
+        import torch
+        assert points.dtype == torch.float64
+        points = points.contiguous()
+        device_id = points.device.index or 0
+    else:
+        points = np.ascontiguousarray(np.asarray(points, np.float64).reshape(-1, 3))
+    n = int(points.shape[0])
+    _, _, (W, H) = nav_grid(points, prm.cell_size, device_id, L)
+    return _height_call(H, W, points.device if on_dev else None, lambda top, known, mn, mx, grid: _nav_ck(
+        L.c.hmsg_nav_height_map(int(device_id), C.byref(prm), n, _ptr(points), float(zero_level), top, known, mn, mx, grid), "hmsg_nav_height_map"))
+
+
+def _nav_goal_heights(goal_h, goal_r2, n, dev):
+    """goal_h int32 [n] and goal_r2 int64 [n] or None for the C ABI, where the images are (a scalar counts for every goal)"""
+    def one(a, np_dtype):
+        if _is_dev(a):
+            import torch
+            assert a.dtype == getattr(torch, np.dtype(np_dtype).name) and a.numel() == n
+            return a.reshape(-1).contiguous()
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.int64).clip(np.iinfo(np_dtype).min, np.iinfo(np_dtype).max), (n,)).astype(np_dtype))
+        if dev is not None:
+            import torch
+            return torch.from_numpy(a).to(dev)
+        return a
+    return one(goal_h, np.int32), None if goal_r2 is None else one(goal_r2, np.int64)
+
+
+def nav_viewpoints_h(top, passable, goals_rc, eye, goal_h, goal_r2=None, field=None, params=None, want_visible=False, device_id=0,
+                     lib_: "HmsgLib | None" = None, **over):
+    """S3 / S4: nav_viewpoints with sight judged on the height map `top` u16 [rows, cols] (hmsg_nav_viewpoints_h).  eye: the
+    camera's height in height units; goal_h [n] (or one value): the goals' heights; goal_r2 [n], one value or None: their
+    footprints (squared radius in cells).  -> nav_viewpoints' dict; numpy in: numpy out, device tensors in: device tensors out."""
+    L = lib_ or lib()
+    prm = params if params is not None else view_params(L, **over)
+    top, H, W, dev = _nav_image(top, np.uint16)
+    passable, ph, pw, pdev = _nav_image(passable, np.uint8)
+    assert (ph, pw) == (H, W) and (pdev is None) == (dev is None)
+    if field is not None:
+        field, fh, fw, fdev = _nav_image(field, np.int32)
+        assert (fh, fw) == (H, W) and (fdev is None) == (dev is None)
+    g = _nav_cells(goals_rc)
+    n = int(g.shape[0])
+    gh, gr2 = _nav_goal_heights(goal_h, goal_r2, n, dev)
+    buf = _nav_buf(dev)
+    res = dict(view_rc=buf((n, 2), np.int32), view_d2=buf((n,), np.int64), view_dist=buf((n,), np.int32), n_visible=buf((n,), np.int32))
+    if want_visible:
+        res["visible"] = buf((n, H, W), np.uint8)
+    some = lambda a: _ptr(a) if n and a is not None else None
+    _nav_ck(L.c.hmsg_nav_viewpoints_h(_nav_dev_id(dev, device_id), H, W, _ptr(top), _ptr(passable), _ptr(field), C.byref(prm), int(eye), n, some(g),
+                                      some(gh), some(gr2), some(res["view_rc"]), some(res["view_d2"]), some(res["view_dist"]),
+                                      some(res["n_visible"]), some(res["visible"]) if want_visible else None), "hmsg_nav_viewpoints_h")
+    return res
+
+
+def nav_view_route_h(main_free_map, top, start_rc, goals_rc, eye, goal_h, goal_r2=None, params=None, view=None, device_id=0,
+                     lib_: "HmsgLib | None" = None, want_field=False, **over):
+    """hmsg_nav_view_route_h: nav_view_route with sight judged on the height map `top` (S3 in V3's place) -> nav_view_route's dict"""
+    L = lib_ or lib()
+    vkeys = ("r_min2", "r_max2", "prefer")
+    prm = params if params is not None else route_params(L, **{k: v for k, v in over.items() if k not in vkeys})
+    vprm = view if view is not None else view_params(L, **{k: v for k, v in over.items() if k in vkeys})
+    m, H, W, dev = _nav_image(main_free_map, np.uint8)
+    top, th, tw, tdev = _nav_image(top, np.uint16)
+    assert (th, tw) == (H, W) and (tdev is None) == (dev is None)
+    start = np.ascontiguousarray(np.asarray(start_rc, np.int64).reshape(2).astype(np.int32))
+    g = _nav_cells(goals_rc)
+    n = int(g.shape[0])
+    gh, gr2 = _nav_goal_heights(goal_h, goal_r2, n, dev)
+    buf = _nav_buf(dev)
+    res = dict(goal_cell=buf((n, 2), np.int32), goal_d2=buf((n,), np.int64), goal_dist=buf((n,), np.int32), path_off=buf((n + 1,), np.int64),
+               passable=buf((H, W), np.uint8))
+    if want_field:
+        res["field"] = buf((H, W), np.int32)
+    n_visible = buf((n,), np.int32)
+    out = HmsgNavRoutes()
+    cap = max(1, n) * 2 * (H + W)
+    some = lambda a: _ptr(a) if n and a is not None else None
+    for attempt in range(2):
+        rc = buf((max(cap, 1), 2), np.int32)
+        for k, v in res.items():
+            setattr(out, k, _ptr(v))
+        out.path_rc, out.path_capacity = _ptr(rc), cap
+        status = L.c.hmsg_nav_view_route_h(_nav_dev_id(dev, device_id), H, W, _ptr(m), _ptr(top), C.byref(prm), C.byref(vprm), int(eye), _ptr(start),
+                                           n, some(g), some(gh), some(gr2), C.byref(out), some(n_visible))
+        if status != 0 and attempt == 0 and out.n_path_cells > cap:
+            cap = int(out.n_path_cells)
+            continue
+        _nav_ck(status, "hmsg_nav_view_route_h")
         break
     res.update(path_rc=rc[: out.n_path_cells], start_cell=(int(out.start_cell[0]), int(out.start_cell[1])), start_d2=int(out.start_d2),
                n_visible=n_visible)

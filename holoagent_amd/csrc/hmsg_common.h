@@ -875,3 +875,6 @@ void hmsg_nav_maps_device(const char* fn, const hmsg_nav_params& prm, const doub
                           double y_hi, double zero_level, int n_poses, const double* poses, hmsg_nav_maps* out);
 void hmsg_nav_grid_device(const char* fn, double cell_size, const double* d_xyz, long long n, double y_lo, double y_hi, double* pcd_min,
                           double* pcd_max, int32_t* grid);
+// the height map (N10, H1 to H3) of the same points; top (u16) and known (u8, may be null) in host or device memory
+void hmsg_nav_height_device(const char* fn, const hmsg_height_params& prm, const double* d_xyz, long long n, double y_lo, double y_hi,
+                            double zero_level, uint16_t* top, uint8_t* known, double* pcd_min, double* pcd_max, int32_t* grid);

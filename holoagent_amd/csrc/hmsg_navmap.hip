@@ -175,6 +175,39 @@ __global__ __launch_bounds__(NAV_T) void k_nav_free(const unsigned char* __restr
     free_map[i] = ((reg[i] | poses[i]) && !obst[i]) ? 1 : 0;
 }
 
+// ------------------------------------------------------------------------------------------ the height map (N10, H1 to H3)
+// one pass: a point below top_hi takes part; its cell is k_nav_points', its height q = floor((y - zero) / unit) clamped to
+// [0, 65535]; raw[cell] = the greatest q (an integer maximum: any order gives it), known[cell] = 1 (every point stores the same)
+__global__ __launch_bounds__(NAV_T) void k_nav_height_points(const double* __restrict__ xyz, long long n, double y_lo, double y_hi, double min_x,
+                                                             double min_z, double cell, double zero, double unit, double top_hi, int H, int W,
+                                                             int* __restrict__ raw, unsigned char* __restrict__ known) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double y = xyz[i * 3 + 1];
+    if (!(y >= y_lo && y <= y_hi) || !(y < top_hi)) return;
+    const double fx = floor((xyz[i * 3] - min_x) / cell), fz = floor((xyz[i * 3 + 2] - min_z) / cell);
+    if (!(fx >= 0.0 && fx < (double)W && fz >= 0.0 && fz < (double)H)) return;          // (never for a cloud inside its own bounds)
+    const size_t c = (size_t)(int)fz * W + (int)fx;
+    const double fq = floor((y - zero) / unit);
+    const int q = fq >= 65535.0 ? 65535 : (fq > 0.0 ? (int)fq : 0);
+    known[c] = 1;
+    if (raw[c] < q) atomicMax(&raw[c], q);                      // (a cell only grows: one already at this height needs no atomic)
+}
+// the maximum over a d x d box (d odd), one axis at a time, the window clipped at the border; out16: the last pass narrows
+__global__ __launch_bounds__(NAV_T) void k_nav_height_max(const int* __restrict__ in, int H, int W, int d, int along_rows, int* __restrict__ out,
+                                                          unsigned short* __restrict__ out16) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= H * W) return;
+    const int r = i / W, c = i - r * W;
+    int v = 0;
+    for (int k = -(d / 2); k <= d / 2; ++k) {
+        const int rr = along_rows ? r + k : r, cc = along_rows ? c : c + k;
+        if (rr >= 0 && rr < H && cc >= 0 && cc < W) v = max(v, in[(size_t)rr * W + cc]);
+    }
+    if (out16) out16[i] = (unsigned short)v;
+    else out[i] = v;
+}
+
 // ------------------------------------------------------------------------------------------ the main region
 // st[0] = components, st[1] = free cells, st[2] = the greatest key (area << 32 | root + 1)
 __global__ __launch_bounds__(NAV_T) void k_nav_roots(int HW, const int* __restrict__ lab, const int* __restrict__ cnt,
@@ -534,6 +567,67 @@ void hmsg_nav_grid_device(const char* fn, double cell_size, const double* d_xyz,
     nav_put_grid(nav_grid(s, d_xyz, n, y_lo, y_hi, cell_size, fn), pcd_min, pcd_max, grid);
 }
 
+// N10, H1 to H3: the bounds come from nav_grid (k_nav_bounds), so the map lies cell for cell on hmsg_nav_maps_device's
+void hmsg_nav_height_device(const char* fn, const hmsg_height_params& prm, const double* d_xyz, long long n, double y_lo, double y_hi,
+                            double zero_level, uint16_t* top, uint8_t* known, double* pcd_min, double* pcd_max, int32_t* grid) {
+    const std::string f = fn;
+    HMSG_REQUIRE(std::isfinite(prm.cell_size) && prm.cell_size > 0.0, HMSG_ERR_INVALID, f + ": cell_size must be positive");
+    HMSG_REQUIRE(std::isfinite(prm.height_unit) && prm.height_unit > 0.0, HMSG_ERR_INVALID, f + ": height_unit must be positive");
+    HMSG_REQUIRE(std::isfinite(prm.top_max) && prm.top_max > 0.0, HMSG_ERR_INVALID, f + ": top_max must be positive");
+    HMSG_REQUIRE(prm.dilation >= 0 && prm.dilation <= 63, HMSG_ERR_INVALID, f + ": dilation must be in [0, 63]");
+    HMSG_REQUIRE(prm.dilation == 0 || (prm.dilation & 1), HMSG_ERR_UNSUPPORTED, f + ": an even dilation has no centre cell");
+    HMSG_REQUIRE(n >= 0 && n < (1ll << 32) && std::isfinite(zero_level), HMSG_ERR_INVALID, f + ": 0 <= n < 2^32 and a finite zero_level");
+    ScopedStream s(hipStreamNonBlocking);
+    const NavGrid g = nav_grid(s, d_xyz, n, y_lo, y_hi, prm.cell_size, fn);
+    nav_put_grid(g, pcd_min, pcd_max, grid);
+    const int H = g.H, W = g.W, HW = H * W;
+    const dim3 gi(cdiv((size_t)HW, NAV_T)), b(NAV_T);
+    DevBuf<int> raw, tmp;
+    DevBuf<unsigned short> own_top;
+    DevBuf<unsigned char> own_known;
+    raw.alloc((size_t)HW), raw.zero(s);
+    unsigned short* p_top = stage_out(own_top, (unsigned short*)top, (size_t)HW);
+    unsigned char* p_known = stage_out(own_known, known, (size_t)HW);
+    if (!p_known) own_known.alloc((size_t)HW), p_known = own_known.p;
+    HIP_TRY(hipMemsetAsync(p_known, 0, (size_t)HW, s));
+    hipLaunchKernelGGL(k_nav_height_points, dim3(cdiv((size_t)n, NAV_T)), b, 0, s, d_xyz, n, y_lo, y_hi, g.mn[0], g.mn[2], prm.cell_size, zero_level,
+                       prm.height_unit, zero_level + prm.top_max, H, W, raw.p, p_known);
+    const int d = prm.dilation > 1 ? prm.dilation : 1;
+    if (d > 1) {
+        tmp.alloc((size_t)HW);
+        hipLaunchKernelGGL(k_nav_height_max, gi, b, 0, s, (const int*)raw.p, H, W, d, 0, tmp.p, (unsigned short*)nullptr);
+        hipLaunchKernelGGL(k_nav_height_max, gi, b, 0, s, (const int*)tmp.p, H, W, d, 1, (int*)nullptr, p_top);
+    } else {
+        hipLaunchKernelGGL(k_nav_height_max, gi, b, 0, s, (const int*)raw.p, H, W, 1, 0, (int*)nullptr, p_top);
+    }
+    HMSG_CHECK_LAUNCH();
+    unstage_out((unsigned short*)top, (const unsigned short*)p_top, (size_t)HW, s);
+    if (known) unstage_out(known, (const unsigned char*)p_known, (size_t)HW, s);
+    HIP_TRY(hipStreamSynchronize(s));
+}
+
+extern "C" void hmsg_height_default_params(hmsg_height_params* p) {
+    if (!p) return;
+    p->cell_size = 0.03;
+    p->height_unit = 0.01;
+    p->top_max = 2.5;
+    p->dilation = 5;
+    p->reserved_ = 0;
+}
+
+extern "C" int hmsg_nav_height_map(int32_t device_id, const hmsg_height_params* prm, int64_t n, const double* xyz, double zero_level,
+                                   uint16_t* top, uint8_t* known, double* pcd_min, double* pcd_max, int32_t* grid) {
+    if (!prm || !xyz || !top) return HMSG_ERR_INVALID;
+    return hmsg_boundary("hmsg_nav_height_map", device_id, [&] {
+        HMSG_REQUIRE(n >= 0, HMSG_ERR_INVALID, "hmsg_nav_height_map: n < 0");
+        ScopedStream s(hipStreamNonBlocking);
+        DevBuf<double> own_xyz;
+        const double* d_xyz = stage_in(own_xyz, xyz, (size_t)n * 3, s, Up::bounce);
+        HIP_TRY(hipStreamSynchronize(s));
+        hmsg_nav_height_device("hmsg_nav_height_map", *prm, d_xyz, n, -INFINITY, INFINITY, zero_level, top, known, pcd_min, pcd_max, grid);
+    });
+}
+
 extern "C" void hmsg_nav_default_params(hmsg_nav_params* p) {
     if (!p) return;
     p->cell_size = 0.03;
@@ -595,6 +689,17 @@ extern "C" int hmsg_map_nav_floor_maps(hmsg_t* hc, double y_lo, double y_hi, dou
         nav_scene_ready(h, y_lo, y_hi, "hmsg_map_nav_floor_maps");
         hmsg_nav_maps_device("hmsg_map_nav_floor_maps", *prm, (const double*)h->pts.p, (const double*)h->cols.p, (long long)h->V, y_lo, y_hi,
                              zero_level, n_poses, poses, out);
+    });
+}
+
+extern "C" int hmsg_map_nav_height_map(hmsg_t* hc, double y_lo, double y_hi, double zero_level, const hmsg_height_params* prm, uint16_t* top,
+                                       uint8_t* known, double* pcd_min, double* pcd_max, int32_t* grid) {
+    hmsg_ctx* h = hc;
+    if (!h || !prm || !top) return HMSG_ERR_INVALID;
+    return hmsg_boundary(h, [&] {
+        nav_scene_ready(h, y_lo, y_hi, "hmsg_map_nav_height_map");
+        hmsg_nav_height_device("hmsg_map_nav_height_map", *prm, (const double*)h->pts.p, (long long)h->V, y_lo, y_hi, zero_level, top, known,
+                               pcd_min, pcd_max, grid);
     });
 }
 

@@ -1428,6 +1428,15 @@ int hmsg_graph_nav_floor_maps(hmsg_graph_t* g, int32_t floor, const hmsg_nav_par
                              fl.f.y_hi, fl.f.zero_level, n_poses, poses, out);
     });
 }
+int hmsg_graph_nav_height_map(hmsg_graph_t* g, int32_t floor, const hmsg_height_params* prm, uint16_t* top, uint8_t* known, double* pcd_min,
+                              double* pcd_max, int32_t* grid) {
+    if (!g || !prm || !top) return HMSG_ERR_INVALID;
+    return hmsg_boundary(&g->err, -1, [&] {
+        const GFloor& fl = nav_floor(g, floor, "hmsg_graph_nav_height_map");
+        hmsg_nav_height_device("hmsg_graph_nav_height_map", *prm, (const double*)g->h->pts.p, (long long)g->h->V, fl.f.y_lo, fl.f.y_hi,
+                               fl.f.zero_level, top, known, pcd_min, pcd_max, grid);
+    });
+}
 
 /* save_hmsg_graph (graph.py:1801-1824) in the reference layout: <dir>/floors, rooms, objects, views */
 int hmsg_save(hmsg_graph_t* g, const char* dir) {

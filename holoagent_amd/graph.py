@@ -1402,6 +1402,19 @@ class Graph:
         zeros = [fl.floor_zero_level for fl in self.floors]
         return max(0, int(np.searchsorted(zeros, centre[1], side="right")) - 1)
 
+    def _sight_of_objects(self, objects, centres, floors):
+        """for sight "heights" (include/hmsg.h, N10): per object its centre's height in metres above its storey's zero level and its
+        footprint radius in metres -- half the diagonal of the axis-aligned x-z extent of its points, 0 for a bare centre (the
+        navigation graph rounds it up to cells and squares it)"""
+        heights, radii = [], []
+        for o, c, f in zip(objects, centres, floors):
+            node = self.objects[int(o)] if isinstance(o, (int, np.integer)) else o
+            heights.append(float(c[1]) - float(self.floors[f].floor_zero_level))
+            pts = np.asarray(node.pcd.points, np.float64).reshape(-1, 3) if hasattr(node, "pcd") else np.zeros((0, 3))
+            ext = pts[:, [0, 2]].max(axis=0) - pts[:, [0, 2]].min(axis=0) if len(pts) else np.zeros(2)
+            radii.append(0.5 * float(np.sqrt(ext[0] * ext[0] + ext[1] * ext[1])))
+        return np.array(heights, np.float64), np.array(radii, np.float64)
+
     def route_to_objects(self, start_pose, objects, floor_id=None, min_clearance=0.25, poses_list=None):
         """Where to stand for each object and how to get there (include/hmsg.h: hmsg_nav_route, on the device): `objects` are indices
         into self.objects such as query_hmsg_object returns, Object nodes, or bare centres [3].  They are routed on the storey of
@@ -1431,14 +1444,17 @@ class Graph:
         return out
 
     def view_routes_to_objects(self, start_pose, objects, floor_id=None, min_clearance=0.25, view_range=(0.5, 3.0), prefer="walk",
-                               poses_list=None):
+                               poses_list=None, sight="map", camera_height=1.5, max_step=None):
         """route_to_objects with the cell to stand on chosen so that the object is in sight (include/hmsg.h: hmsg_nav_view_route, on
         the device): of the cells that have min_clearance metres of free space, can be reached and see the cell under the
         object's centre on the storey's obstacle map from view_range metres (near, far), the one with the least walk (prefer
         "walk") or the closest look ("look").  The nearest such cell of route_to_objects can lie behind a wall.  Per object
         route_to_objects' dict plus n_visible, facing (unit (x, z) towards the object) and yaw; reason is None, "other floor",
         "unreachable" (the start reaches no cell at all) or "no view" (cells are reached, none of them sees the object within the
-        range)."""
+        range).  sight "heights" (hmsg_nav_view_route_h): sight is judged on the storey's height map from camera_height metres
+        above its zero level, towards the object's centre at its own height, the object's footprint (_sight_of_objects) not
+        hiding it: a table no longer hides a lamp, a counter hides the mug behind it.  max_step (metres): cells whose top is
+        higher are not walked on."""
         pose = np.asarray(start_pose, np.float64)
         f = int(floor_id) if floor_id is not None else self.floor_of_pose(pose)
         if f is None:
@@ -1454,8 +1470,14 @@ class Graph:
                     n_visible=0, facing=None, yaw=None, floor_id=floors[k], reason="other floor") for k, o in enumerate(objects)]
         if here:
             nav = self.floor_navigation(f, poses_list)
+            extra = {}
+            if sight != "map":
+                h, rad = self._sight_of_objects([objects[k] for k in here], [centres[k] for k in here], [f] * len(here))
+                extra = dict(sight=sight, camera_height_m=camera_height, goal_heights_m=h, goal_radius_m=rad)
+            if max_step is not None:
+                extra["max_step_m"] = max_step
             routes = nav.route_to_view(pose[:3, 3], np.array([centres[k] for k in here]), min_clearance_m=min_clearance, view_range_m=view_range,
-                                       prefer=prefer)
+                                       prefer=prefer, **extra)
             nothing_reached = nav.last_route["start_cell"] == (-1, -1)
             for k, r in zip(here, routes):
                 out[k].update(r, reason=None if r["reachable"] else ("unreachable" if nothing_reached else "no view"))
@@ -1529,16 +1551,23 @@ class Graph:
         return out
 
     def view_routes_across_floors(self, start_pose, objects, floor_id=None, min_clearance=0.25, view_range=(0.5, 3.0), prefer="walk",
-                                  poses_list=None, links=None):
+                                  poses_list=None, links=None, sight="map", camera_height=1.5, max_step=None):
         """view_routes_to_objects over the whole building (BuildingNavigation.route_to_view): the cell stood on sees the object on the
         object's own storey.  reason: None, "unreachable", "no stairs" or "no view" (cells of the object's storey are reached,
-        none of them sees it within the range)."""
+        none of them sees it within the range).  sight, camera_height and max_step: as view_routes_to_objects has them, each
+        object's height taken above its own storey's zero level."""
         from ._lib import NAV_UNREACHED
         pose, f, centres, floors = self._across_floors(start_pose, objects, floor_id)
         if not len(objects):
             return []
         nav = self.building_navigation(poses_list, min_clearance, links)
-        routes = nav.route_to_view(f, pose[:3, 3], centres, floors, min_clearance_m=min_clearance, view_range_m=view_range, prefer=prefer)
+        extra = {}
+        if sight != "map":
+            h, rad = self._sight_of_objects(objects, centres, floors)
+            extra = dict(sight=sight, camera_height_m=camera_height, goal_heights_m=h, goal_radius_m=rad)
+        if max_step is not None:
+            extra["max_step_m"] = max_step
+        routes = nav.route_to_view(f, pose[:3, 3], centres, floors, min_clearance_m=min_clearance, view_range_m=view_range, prefer=prefer, **extra)
         last = nav.last_route
         nothing = last["start_cell"][1] < 0
         out = []

@@ -15,7 +15,9 @@ reference's own class gives on two scenes; tests/test_navgraph_golden.py compare
 Beyond the reference (include/hmsg.h, N7): clearance_map, distance_field and route work on the maps this object already holds --
 exact integer distance fields on main_free_map, the nearest reachable free cell of a goal and the cells of the way, on the device.
 N8: sight_blocking_map, viewpoints and route_to_view stand the robot on a reached cell from which the goal is in sight on the
-obstacle map, not on the nearest one whatever lies between."""
+obstacle map, not on the nearest one whatever lies between.  N10: height_map is the storey's exact integer height map;
+viewpoints and route_to_view with sight="heights" judge sight on it from the camera's height, and max_step_m keeps routes off
+cells that the flat maps leave free under furniture (walkable_map)."""
 import json
 import os
 
@@ -144,29 +146,47 @@ class NavigationGraph:
         assert self.maps is not None, "get_main_free_map makes the maps"
         return _lib.nav_clearance(self.maps["main_free_map"], lib_=self.L, device_id=self.device_id, **weights)
 
-    def passable_map(self, min_clearance_m=0.0, **weights):
-        """main_free_map where the clearance is at least min_clearance_m (0: the map itself)"""
+    def walkable_map(self, max_step_m=None):
+        """main_free_map (max_step_m None), or its cells whose height-map top is at most max_step_m above the zero level: what the
+        robot can roll over.  main_free_map alone only loses what the obstacle band (1.4 to 2.5 m by default) holds, so a low box
+        in a room stays in it."""
         assert self.maps is not None, "get_main_free_map makes the maps"
         main = self.maps["main_free_map"]
+        if max_step_m is None:
+            return main
+        top = self.height_map()["top_map"]
+        step = int(np.floor(float(max_step_m) / self.height_unit))
+        if hasattr(top, "to"):
+            import torch
+            return ((main != 0) & (top.to(torch.int32) <= step)).to(main.dtype)
+        return ((main != 0) & (top <= step)).astype(np.uint8)
+
+    def passable_map(self, min_clearance_m=0.0, max_step_m=None, **weights):
+        """main_free_map where the clearance is at least min_clearance_m (0: the map itself).  max_step_m: walkable_map(max_step_m)
+        in main_free_map's place, the clearance being that mask's own."""
+        assert self.maps is not None, "get_main_free_map makes the maps"
+        main = self.walkable_map(max_step_m)
         units = self.clearance_units(min_clearance_m, weights.get("w_straight", 5))
         if units <= 0:
             return main
-        ok = (main != 0) & (self.clearance_map(**weights) >= units)
+        clearance = self.clearance_map(**weights) if max_step_m is None else _lib.nav_clearance(main, lib_=self.L, device_id=self.device_id, **weights)
+        ok = (main != 0) & (clearance >= units)
         return ok.to(main.dtype) if hasattr(ok, "to") else ok.astype(np.uint8)
 
-    def distance_field(self, sources_xyz_or_rc, min_clearance_m=0.0, **weights):
-        """R2 from the given sources (world points [n, 3] or cells [n, 2]) on passable_map(min_clearance_m): int32 [rows, cols]"""
-        fields, _ = _lib.nav_distance_fields(self.passable_map(min_clearance_m, **weights), [self.cells_of(sources_xyz_or_rc)], lib_=self.L,
-                                             device_id=self.device_id, **weights)
+    def distance_field(self, sources_xyz_or_rc, min_clearance_m=0.0, max_step_m=None, **weights):
+        """R2 from the given sources (world points [n, 3] or cells [n, 2]) on passable_map(min_clearance_m, max_step_m): int32 [rows, cols]"""
+        fields, _ = _lib.nav_distance_fields(self.passable_map(min_clearance_m, max_step_m, **weights), [self.cells_of(sources_xyz_or_rc)],
+                                             lib_=self.L, device_id=self.device_id, **weights)
         return fields[0]
 
-    def route(self, start_xyz, goals_xyz, min_clearance_m=0.0, **weights):
+    def route(self, start_xyz, goals_xyz, min_clearance_m=0.0, max_step_m=None, **weights):
         """hmsg_nav_route from start_xyz to every goal (world points, or cells): per goal a dict with the stand-on `point` in world
         coordinates (the centre of the snapped cell, y = pcd_min[1]), its `cell`, `reachable`, `length_m` (None when not
-        reachable), `snap_m` (how far the goal's cell is from the cell stood on) and the `polyline` [k, 3] from the start."""
+        reachable), `snap_m` (how far the goal's cell is from the cell stood on) and the `polyline` [k, 3] from the start.
+        max_step_m: routed on walkable_map(max_step_m)."""
         assert self.maps is not None, "get_main_free_map makes the maps"
         ws = int(weights.get("w_straight", 5))
-        r = _lib.nav_route(self.maps["main_free_map"], self.cells_of(start_xyz)[0], self.cells_of(goals_xyz), lib_=self.L, device_id=self.device_id,
+        r = _lib.nav_route(self.walkable_map(max_step_m), self.cells_of(start_xyz)[0], self.cells_of(goals_xyz), lib_=self.L, device_id=self.device_id,
                            min_clearance=self.clearance_units(min_clearance_m, ws), **weights)
         r = {k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in r.items()}
         self.last_route = r
@@ -207,33 +227,96 @@ class NavigationGraph:
             raise ValueError('prefer: "walk" (least walk) or "look" (closest look)')
         return 0 if prefer == "walk" else 1
 
-    def viewpoints(self, goals, start=None, min_clearance_m=0.0, view_range_m=(0.0, 3.0), prefer="walk", want_visible=False, **weights):
+    # ---- the height map and sight with heights (include/hmsg.h, N10: the rules H1 to H3 and S1 to S5)
+    height_unit = 0.01                        # metres per height unit of the kept height map (height_map sets it)
+
+    def height_map(self, floor_pcd=None, **params):
+        """hmsg_nav_height_map of the storey (this object's cloud or SceneSlab; floor_pcd: another cloud or slab of the same grid),
+        zero_level the one the maps were made with: made once and kept as self.maps["top_map"] (u16 [rows, cols], height units
+        above the zero level) and self.maps["known_map"] (u8), where the other maps are.  params: height_unit, top_max, dilation;
+        asked again with other values it is made again."""
+        assert self.maps is not None and self.zero_level is not None, "get_main_free_map makes the maps and sets the zero level"
+        key = tuple(sorted(params.items()))
+        if "top_map" in self.maps and getattr(self, "_height_key", None) == key and floor_pcd is None:
+            return self.maps
+        src = floor_pcd if floor_pcd is not None else (self.slab if self.slab is not None else self.points)
+        if isinstance(src, SceneSlab):
+            m = src.scene.nav_height_map(src.y_lo, src.y_hi, self.zero_level, cell_size=self.cell_size, **params)
+        else:
+            m = _lib.nav_height_map(_cloud(src)[0], self.zero_level, lib_=self.L, device_id=self.device_id, cell_size=self.cell_size, **params)
+        assert tuple(m["grid"]) == (int(self.grid_size[0]), int(self.grid_size[1])), "the height map's cloud has another grid"
+        self.maps.update(top_map=m["top"], known_map=m["known"])
+        self._height_key = key
+        self.height_unit = float(params.get("height_unit", 0.01))
+        return self.maps
+
+    def eye_units(self, camera_height_m):
+        """a camera height above the zero level in the height map's units, as S1 takes it"""
+        return int(min(max(np.floor(float(camera_height_m) / self.height_unit), 0), 65535))
+
+    def _sight(self, sight, goals_xyz, n, camera_height_m, goal_heights_m, goal_radius_m):
+        """None for sight "map"; for "heights" (top_map, eye, goal_h int32 [n], goal_r2 int64 [n] or None).  goal_heights_m:
+        metres above the zero level, one or [n]; default: the goals' own y (world points only).  goal_radius_m: the goals'
+        footprints in metres, one or [n]: ceil(radius / cell_size), squared."""
+        if sight == "map":
+            return None
+        if sight != "heights":
+            raise ValueError('sight: "map" (the obstacle map) or "heights" (the height map)')
+        top = self.height_map()["top_map"]
+        if goal_heights_m is None:
+            g = np.asarray(goals_xyz.cpu() if hasattr(goals_xyz, "cpu") else goals_xyz, np.float64)
+            g = g.reshape(-1, g.shape[-1]) if g.ndim > 1 else g.reshape(1, -1)
+            if g.shape[1] != 3:
+                raise ValueError('sight "heights": goals given as cells need goal_heights_m')
+            goal_heights_m = g[:, 1] - self.zero_level
+        gh = np.floor(np.broadcast_to(np.asarray(goal_heights_m, np.float64), (n,)) / self.height_unit).clip(0, 65535).astype(np.int32)
+        gr2 = None
+        if goal_radius_m is not None:
+            cells = np.ceil(np.broadcast_to(np.asarray(goal_radius_m, np.float64), (n,)) / self.cell_size).clip(0, 2 ** 20).astype(np.int64)
+            gr2 = cells * cells
+        return top, self.eye_units(camera_height_m), gh, gr2
+
+    def viewpoints(self, goals, start=None, min_clearance_m=0.0, view_range_m=(0.0, 3.0), prefer="walk", want_visible=False, sight="map",
+                   camera_height_m=1.5, goal_heights_m=None, goal_radius_m=None, max_step_m=None, **weights):
         """hmsg_nav_viewpoints for every goal (world points [n, 3] or cells [n, 2]) on passable_map(min_clearance_m) and
         sight_blocking_map(): _lib.nav_viewpoints' dict, where the maps are.  start (a world point or a cell): only cells reached
-        from it, snapped by R4 as route snaps it, are candidates, and view_dist is the walk to them."""
+        from it, snapped by R4 as route snaps it, are candidates, and view_dist is the walk to them.  sight "heights":
+        hmsg_nav_viewpoints_h on height_map() from camera_height_m above the zero level (_sight says how the goals' heights and
+        footprints are given)."""
         r_min2, r_max2 = self.view_band(view_range_m)
-        pas = self.passable_map(min_clearance_m, **weights)
+        pas = self.passable_map(min_clearance_m, max_step_m, **weights)
+        goal_cells = self.cells_of(goals)
+        hs = self._sight(sight, goals, len(goal_cells), camera_height_m, goal_heights_m, goal_radius_m)
         field = None
         if start is not None:
             cell, _ = _lib.nav_snap_cells(pas, self.cells_of(start), lib_=self.L, device_id=self.device_id)
             cell = cell.cpu().numpy() if hasattr(cell, "cpu") else cell
-            field = self.distance_field(cell if cell[0, 0] >= 0 else np.zeros((0, 2), np.int32), min_clearance_m, **weights)
-        return _lib.nav_viewpoints(self.sight_blocking_map(), pas, self.cells_of(goals), field=field, want_visible=want_visible, lib_=self.L,
+            field = self.distance_field(cell if cell[0, 0] >= 0 else np.zeros((0, 2), np.int32), min_clearance_m, max_step_m, **weights)
+        if hs is not None:
+            return _lib.nav_viewpoints_h(hs[0], pas, goal_cells, hs[1], hs[2], hs[3], field=field, want_visible=want_visible, lib_=self.L,
+                                         device_id=self.device_id, r_min2=r_min2, r_max2=r_max2, prefer=self._prefer(prefer))
+        return _lib.nav_viewpoints(self.sight_blocking_map(), pas, goal_cells, field=field, want_visible=want_visible, lib_=self.L,
                                    device_id=self.device_id, r_min2=r_min2, r_max2=r_max2, prefer=self._prefer(prefer))
 
-    def route_to_view(self, start_xyz, goals_xyz, min_clearance_m=0.0, view_range_m=(0.0, 3.0), prefer="walk", **weights):
+    def route_to_view(self, start_xyz, goals_xyz, min_clearance_m=0.0, view_range_m=(0.0, 3.0), prefer="walk", sight="map", camera_height_m=1.5,
+                      goal_heights_m=None, goal_radius_m=None, max_step_m=None, **weights):
         """hmsg_nav_view_route: route's dict per goal, the cell stood on being the goal's viewpoint (V4: in sight of the goal within
         view_range_m, the least walk or the closest look) in place of R4's nearest cell.  Added: `n_visible` (the cells the goal
         is seen from), `facing` (a float64 unit (x, z) vector from the stand-on point to the goal's world point -- a cell's centre
         for a goal given as a cell -- or (0, 0) when both lie in one cell; None when not reachable) and `yaw` = atan2(facing_x,
-        facing_z).  A goal that no reached cell sees is not reachable."""
+        facing_z).  A goal that no reached cell sees is not reachable.  sight "heights": hmsg_nav_view_route_h, as viewpoints
+        has it; max_step_m: routed on walkable_map(max_step_m)."""
         assert self.maps is not None, "get_main_free_map makes the maps"
         ws = int(weights.get("w_straight", 5))
         r_min2, r_max2 = self.view_band(view_range_m)
         goal_cells = self.cells_of(goals_xyz)
-        r = _lib.nav_view_route(self.maps["main_free_map"], self.sight_blocking_map(), self.cells_of(start_xyz)[0], goal_cells, lib_=self.L,
-                                device_id=self.device_id, min_clearance=self.clearance_units(min_clearance_m, ws), r_min2=r_min2, r_max2=r_max2,
-                                prefer=self._prefer(prefer), **weights)
+        hs = self._sight(sight, goals_xyz, len(goal_cells), camera_height_m, goal_heights_m, goal_radius_m)
+        common = dict(lib_=self.L, device_id=self.device_id, min_clearance=self.clearance_units(min_clearance_m, ws), r_min2=r_min2, r_max2=r_max2,
+                      prefer=self._prefer(prefer), **weights)
+        if hs is not None:
+            r = _lib.nav_view_route_h(self.walkable_map(max_step_m), hs[0], self.cells_of(start_xyz)[0], goal_cells, hs[1], hs[2], hs[3], **common)
+        else:
+            r = _lib.nav_view_route(self.walkable_map(max_step_m), self.sight_blocking_map(), self.cells_of(start_xyz)[0], goal_cells, **common)
         r = {k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in r.items()}
         self.last_route = r
 
@@ -544,13 +627,15 @@ class BuildingNavigation:
         return self._dicts(r, ws)
 
     def route_to_view(self, start_floor, start_xyz, goals_xyz, goal_floors, min_clearance_m=0.0, view_range_m=(0.0, 3.0), prefer="walk",
-                      **weights):
+                      sight="map", camera_height_m=1.5, goal_heights_m=None, goal_radius_m=None, max_step_m=None, **weights):
         """route with the cell stood on chosen so that the goal is in sight on its own storey (composed, no device code of its own):
         the start is snapped by R4, its building field made (B3), and each storey's part of it handed to hmsg_nav_viewpoints as
         the `field` with that storey's sight_blocking_map (V4: least walk from the START, or closest look); then B5 to the
-        viewpoints.  route's dict plus n_visible, facing and yaw as NavigationGraph.route_to_view gives them."""
+        viewpoints.  route's dict plus n_visible, facing and yaw as NavigationGraph.route_to_view gives them.  sight "heights":
+        hmsg_nav_viewpoints_h per storey on its height_map(), the goals' heights above their own storey's zero level (goal_heights_m
+        and goal_radius_m: one value or one per goal); max_step_m: every storey's walkable_map(max_step_m) in main_free_map's place."""
         ws = int(weights.get("w_straight", 5))
-        pas = self.passables(min_clearance_m, **weights)
+        pas = [n_.passable_map(min_clearance_m, max_step_m, **weights) for n_ in self.storeys]
         st = self.triples_of(start_floor, start_xyz)[0]
         goals = self.triples_of(goal_floors, goals_xyz)
         cell, d2 = _lib.nav_snap_cells(pas[int(st[0])], st[1:], lib_=self.L, device_id=self.device_id)
@@ -560,7 +645,8 @@ class BuildingNavigation:
                  goal_d2=np.full(n, -1, np.int64), goal_dist=np.full(n, _lib.NAV_UNREACHED, np.int32), n_visible=np.zeros(n, np.int32))
         r["goal_cell"][:, 0] = goals[:, 0]
         if cell[0, 0] >= 0:
-            fields = self.fields(int(st[0]), cell[0], min_clearance_m, **weights)
+            f, _ = _lib.nav_building_fields(pas, self.links, self.triples_of(int(st[0]), cell[0]), lib_=self.L, device_id=self.device_id, **weights)
+            fields = [x[0] for x in f]
         else:
             fields = None
         if fields is not None:
@@ -568,8 +654,14 @@ class BuildingNavigation:
                 nav = self.storeys[l]
                 sel = np.flatnonzero(goals[:, 0] == l)
                 r_min2, r_max2 = nav.view_band(view_range_m)
-                v = _lib.nav_viewpoints(nav.sight_blocking_map(), pas[l], goals[sel, 1:], field=fields[l], lib_=self.L, device_id=self.device_id,
-                                        r_min2=r_min2, r_max2=r_max2, prefer=nav._prefer(prefer))
+                per = lambda a: None if a is None else (np.asarray(a, np.float64)[sel] if np.ndim(a) else a)
+                hs = nav._sight(sight, _host(goals_xyz)[sel] if np.ndim(_host(goals_xyz)) > 1 else goals_xyz, len(sel), camera_height_m,
+                                per(goal_heights_m), per(goal_radius_m))
+                common = dict(field=fields[l], lib_=self.L, device_id=self.device_id, r_min2=r_min2, r_max2=r_max2, prefer=nav._prefer(prefer))
+                if hs is not None:
+                    v = _lib.nav_viewpoints_h(hs[0], pas[l], goals[sel, 1:], hs[1], hs[2], hs[3], **common)
+                else:
+                    v = _lib.nav_viewpoints(nav.sight_blocking_map(), pas[l], goals[sel, 1:], **common)
                 r["goal_cell"][sel, 1:] = _host(v["view_rc"])
                 r["goal_d2"][sel], r["goal_dist"][sel], r["n_visible"][sel] = _host(v["view_d2"]), _host(v["view_dist"]), _host(v["n_visible"])
             off, src = _lib.nav_building_paths(pas, self.links, fields, r["goal_cell"], lib_=self.L, device_id=self.device_id, **weights)

@@ -1456,6 +1456,62 @@ int hmsg_nav_building_route(int32_t device_id, int32_t n_storeys, const int32_t*
                             const hmsg_route_params* prm, const int32_t* start /* i32 [3] */, int64_t n_goals,
                             const int32_t* goals /* i32 [n_goals][3] */, hmsg_nav_building_routes* out);
 
+/* ---- N10: sight over furniture (csrc/hmsg_navmap.hip, csrc/hmsg_navview.hip): an exact integer height map of a storey and N8's
+ * sight rule in 2.5-D on top of it.  N8 judges sight on obstacle_map > 0, a flat image of the points between obstacle_lo and
+ * obstacle_hi: nothing below that band hides anything, and with the band lowered a table hides a lamp as a wall does.  The
+ * reference's get_height_map is last-writer-wins in float and feeds an older stairs variant only; it is not restated, and the
+ * rules are this library's.  Images, cells and memory conventions are N6's and N7's.  All of it is integer work: every output has
+ * one right answer.
+ * The height map:
+ *  H1. The grid (pcd_min, pcd_max, grid) is N6's rule 1 over ALL points of the storey, so the map lies cell for cell on the maps
+ *      hmsg_nav_floor_maps makes of the same cloud.  A point takes part when y < zero_level + top_max (the sum formed in float64
+ *      first, as in N6's rule 2; top_max keeps ceilings out).  Its cell is N6's rule 1 for x and z; its height is q = floor((y -
+ *      zero_level) / height_unit) in float64 (subtract, then divide), clamped to [0, 65535].
+ *  H2. raw[cell] = the maximum q of the cell's points, 0 for a cell with none; known[cell] (u8) = 1 where a point took part.
+ *  H3. top[cell] (u16) = the maximum of raw over the dilation x dilation box centred on the cell, clipped at the image border.
+ *      dilation is odd (5, as the obstacle map's: the map's voxels are coarser than the cells, and without it a wall is a
+ *      sieve); 0 or 1: top = raw.
+ * Refusals: N6's (a null prm / xyz / top, no points, a coordinate that is not finite, counted on the device; HMSG_ERR_UNSUPPORTED
+ * for a grid of 2^28 cells or more); height_unit <= 0, top_max <= 0, cell_size <= 0, a dilation outside [0, 63];
+ * HMSG_ERR_UNSUPPORTED for an even dilation other than 0.  known may be NULL; pcd_min, pcd_max and grid may be NULL.  The graph
+ * and scene forms take the slabs of their _floor_maps siblings and refuse what those refuse.
+ * Sight with heights: eye is the camera's height above the storey's zero level in height units, one value per call; goal_h[k]
+ * (i32, read clamped to [0, 65535]) is goal k's height, goal_r2[k] (i64; the array may be NULL: -1 everywhere) its footprint.
+ *  S1. The line of two cells is V1, unchanged: it starts at the smaller (row, col) pair, indices i = 0 .. n.  Each end keeps its
+ *      height: the viewpoint's end eye, the goal's end goal_h.  h0 is the height at i = 0, hn the one at i = n.
+ *  S2. T(c) = 0 when d2(c, goal) <= goal_r2, else top[c]: the object's own body does not hide its centre.  The sight is clear
+ *      when no cell 0 < i < n has T(c_i) * n >= h0 * (n - i) + hn * i, and no diagonal step i - 1 -> i has BOTH cells s it
+ *      squeezes between at T(s) * 2 n >= h0 * (2 n - 2 i + 1) + hn * (2 i - 1).  The endpoints never block.  Every product fits
+ *      int32 (65535 * 510).  A column is solid from the floor to its top: there is no seeing under a table.
+ *  S3. The visible set is V3 with S2 in V2's place.
+ *  S4. The viewpoint is V4, unchanged.
+ *  S5. Limits are V5's.  Refusals are N8's, plus eye outside [0, 65535], a goal_r2[k] < -1, a null top or goal_h.
+ * With top = 65535 where a cell blocks and 0 elsewhere, no footprint and eye and goal_h anywhere in [1, 65535], S3 is V3 bit for
+ * bit.  hmsg_nav_view_route_h is hmsg_nav_view_route with S3 in V3's place, and only that. */
+typedef struct hmsg_height_params {
+    double  cell_size;            /* 0.03 m */
+    double  height_unit;          /* 0.01 m */
+    double  top_max;              /* 2.5: points at zero_level + top_max and above take no part */
+    int32_t dilation;             /* 5; odd; 0 or 1 = none */
+    int32_t reserved_;
+} hmsg_height_params;
+void hmsg_height_default_params(hmsg_height_params* p);
+/* xyz f64 [n][3]; top u16 [grid[1]][grid[0]], known u8 of the same shape or NULL (hmsg_nav_grid says the size beforehand) */
+int hmsg_nav_height_map(int32_t device_id, const hmsg_height_params* prm, int64_t n, const double* xyz, double zero_level, uint16_t* top,
+                        uint8_t* known, double* pcd_min /* f64 [3] */, double* pcd_max, int32_t* grid /* i32 [2] */);
+int hmsg_graph_nav_height_map(hmsg_graph_t* g, int32_t floor, const hmsg_height_params* prm, uint16_t* top, uint8_t* known, double* pcd_min,
+                              double* pcd_max, int32_t* grid);
+int hmsg_map_nav_height_map(hmsg_t* h, double y_lo, double y_hi, double zero_level, const hmsg_height_params* prm, uint16_t* top,
+                            uint8_t* known, double* pcd_min, double* pcd_max, int32_t* grid);
+int hmsg_nav_viewpoints_h(int32_t device_id, int32_t rows, int32_t cols, const uint16_t* top, const uint8_t* passable,
+                          const int32_t* field /* or NULL */, const hmsg_view_params* prm, int32_t eye, int64_t n_goals, const int32_t* goal_rc,
+                          const int32_t* goal_h /* i32 [n_goals] */, const int64_t* goal_r2 /* i64 [n_goals] or NULL */, int32_t* view_rc,
+                          int64_t* view_d2, int32_t* view_dist, int32_t* n_visible, uint8_t* visible);
+int hmsg_nav_view_route_h(int32_t device_id, int32_t rows, int32_t cols, const uint8_t* main_free_map, const uint16_t* top,
+                          const hmsg_route_params* route_prm, const hmsg_view_params* view_prm, int32_t eye, const int32_t* start_rc,
+                          int64_t n_goals, const int32_t* goal_rc, const int32_t* goal_h, const int64_t* goal_r2 /* or NULL */,
+                          hmsg_nav_routes* out, int32_t* n_visible /* i32 [n_goals], may be NULL */);
+
 
 #ifdef __cplusplus
 }
