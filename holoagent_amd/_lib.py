@@ -114,6 +114,11 @@ class HmsgNavBuildingRoutes(C.Structure):       # include/hmsg.h: hmsg_nav_build
                 ("n_path_cells", C.c_int64), ("start_d2", C.c_int64), ("start_cell", C.c_int32 * 3), ("reserved_", C.c_int32)]
 
 
+class HmsgNavDoorTable(C.Structure):    # include/hmsg.h: hmsg_nav_door_table
+    _fields_ = [("door_pair", C.c_void_p), ("door_off", C.c_void_p), ("door_rc", C.c_void_p), ("other", C.c_void_p), ("adjacency", C.c_void_p),
+                ("door_capacity", C.c_int64), ("cell_capacity", C.c_int64), ("n_doors", C.c_int64), ("n_door_cells", C.c_int64)]
+
+
 class HmsgViewParams(C.Structure):      # include/hmsg.h: hmsg_view_params
     _fields_ = [("r_min2", C.c_int64), ("r_max2", C.c_int64), ("prefer", C.c_int32), ("reserved_", C.c_int32)]
 
@@ -322,6 +327,11 @@ _SIGS = {
                                           C.POINTER(C.c_int64)]),
     "hmsg_nav_building_route": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P, C.c_int64, _P, _P]),
     "hmsg_test_nav_building_last": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "hmsg_nav_room_labels": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, _P, _P, _P]),
+    "hmsg_nav_doors": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P]),
+    "hmsg_nav_path_rooms": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64, _P, _P, _P, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "hmsg_nav_room_doors": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, _P, _P, _P]),
+    "hmsg_test_nav_rooms_last": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "hmsg_test_nav_last": (C.c_int, [C.POINTER(C.c_int32)]),
     "hmsg_test_nav_route_last": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "hmsg_test_knn_last_phase2": (C.c_int64, []),
@@ -2585,6 +2595,101 @@ def nav_building_route(main_free_maps, links, start, goals, params=None, device_
     res.update(path_src=src[: out.n_path_cells], start_cell=tuple(int(v) for v in out.start_cell), start_d2=int(out.start_d2), passable=passable)
     if want_fields:
         res["fields"] = fields
+    return res
+
+
+# ---- N11: rooms on a floor's free map (include/hmsg.h states the rules G1, G2, D1 to D4, L1)
+def _nav_seed_sets(seed_sets):
+    """a list of (row, col) arrays, one per room, or the pair (seed_off int64 [n + 1], seed_rc int32 [m, 2]) -> (off, rc)"""
+    if isinstance(seed_sets, tuple) and len(seed_sets) == 2 and np.ndim(seed_sets[0]) == 1:
+        return np.ascontiguousarray(np.asarray(seed_sets[0], np.int64)), _nav_cells(seed_sets[1])
+    sets = [np.asarray(s_, np.int64).reshape(-1, 2) for s_ in seed_sets]
+    off = np.concatenate([[0], np.cumsum([len(s_) for s_ in sets])]).astype(np.int64)
+    return off, _nav_cells(np.concatenate(sets) if sets else np.zeros((0, 2)))
+
+
+def nav_room_labels(passable, seed_sets, params=None, want_dist=False, device_id=0, lib_: "HmsgLib | None" = None, **over):
+    """G1, G2: the room of every reached cell (hmsg_nav_room_labels).  passable u8 [rows, cols]; seed_sets as _nav_seed_sets takes
+    them -> (label int32 [rows, cols], n_cells int64 [n_rooms]) and, with want_dist, dist int32 [rows, cols] as the third.  A
+    device tensor in: device tensors out."""
+    L = lib_ or lib()
+    prm = params if params is not None else route_params(L, **over)
+    passable, H, W, dev = _nav_image(passable, np.uint8)
+    off, rc = _nav_seed_sets(seed_sets)
+    n = len(off) - 1
+    buf = _nav_buf(dev)
+    label, cells = buf((H, W), np.int32), buf((max(n, 0),), np.int64)
+    dist = buf((H, W), np.int32) if want_dist else None
+    _nav_ck(L.c.hmsg_nav_room_labels(_nav_dev_id(dev, device_id), H, W, _ptr(passable), C.byref(prm), n, _ptr(off), _ptr(rc) if len(rc) else None,
+                                     _ptr(label), _ptr(dist), _ptr(cells) if n > 0 else None), "hmsg_nav_room_labels")
+    return (label, cells, dist) if want_dist else (label, cells)
+
+
+def _nav_door_call(call, fn, buf, H, W, n_rooms, want_other, want_adjacency):
+    """the door table of `call(out)`, with lists as long as the image has cells (only what the counts say is written and kept)"""
+    res = {}
+    if want_other:
+        res["other"] = buf((H, W), np.int32)
+    if want_adjacency:
+        res["adjacency"] = buf((n_rooms, n_rooms), np.int32)
+    out = HmsgNavDoorTable()
+    cap = H * W                                                           # no more doors or door cells than cells: never too short
+    pair, off, rc = buf((cap, 2), np.int32), buf((cap + 1,), np.int64), buf((cap, 2), np.int32)
+    for k, v in res.items():
+        setattr(out, k, _ptr(v))
+    out.door_pair, out.door_off, out.door_rc, out.door_capacity, out.cell_capacity = _ptr(pair), _ptr(off), _ptr(rc), cap, cap
+    _nav_ck(call(out), fn)
+    nd, nc = int(out.n_doors), int(out.n_door_cells)
+    res.update(door_pair=pair[:nd], door_off=off[: nd + 1], door_rc=rc[:nc], n_doors=nd, n_door_cells=nc)
+    return res
+
+
+def nav_doors(passable, label, n_rooms, want_other=True, want_adjacency=True, device_id=0, lib_: "HmsgLib | None" = None):
+    """D1 to D4: the doors between the rooms of a label image (hmsg_nav_doors) -> dict(door_pair int32 [n_doors, 2], door_off int64
+    [n_doors + 1], door_rc int32 [n_door_cells, 2], n_doors, n_door_cells; other int32 [rows, cols]; adjacency int32 [n_rooms,
+    n_rooms])"""
+    L = lib_ or lib()
+    passable, H, W, dev = _nav_image(passable, np.uint8)
+    label, lh, lw, ldev = _nav_image(label, np.int32)
+    assert (lh, lw) == (H, W) and (ldev is None) == (dev is None)
+    n_rooms = int(n_rooms)
+    call = lambda out: L.c.hmsg_nav_doors(_nav_dev_id(dev, device_id), H, W, _ptr(passable), _ptr(label), n_rooms, C.byref(out))
+    return _nav_door_call(call, "hmsg_nav_doors", _nav_buf(dev), H, W, max(n_rooms, 0), want_other, want_adjacency and 0 <= n_rooms <= 4096)
+
+
+def nav_path_rooms(label, path_off, path_rc, device_id=0, lib_: "HmsgLib | None" = None):
+    """L1: the legs of every path by room (hmsg_nav_path_rooms) -> (leg_off int64 [n_paths + 1], leg_room int32 [k], leg_first int64
+    [k]).  The first call counts, the second writes."""
+    L = lib_ or lib()
+    label, H, W, dev = _nav_image(label, np.int32)
+    if not _is_dev(path_off):
+        path_off = np.ascontiguousarray(np.asarray(path_off, np.int64))
+    rc = _nav_cells(path_rc)
+    n = int(path_off.shape[0]) - 1
+    buf = _nav_buf(dev)
+    off, need = buf((n + 1,), np.int64), C.c_int64(0)
+    args = (_nav_dev_id(dev, device_id), H, W, _ptr(label), n, _ptr(path_off), _ptr(rc) if len(rc) else None)
+    _nav_ck(L.c.hmsg_nav_path_rooms(*args, _ptr(off), None, None, 0, C.byref(need)), "hmsg_nav_path_rooms")
+    room, first = buf((max(need.value, 1),), np.int32), buf((max(need.value, 1),), np.int64)
+    _nav_ck(L.c.hmsg_nav_path_rooms(*args, _ptr(off), _ptr(room), _ptr(first), need.value, C.byref(need)), "hmsg_nav_path_rooms")
+    return off, room[: need.value], first[: need.value]
+
+
+def nav_room_doors(main_free_map, seed_sets, params=None, want_other=True, want_adjacency=True, device_id=0, lib_: "HmsgLib | None" = None,
+                   **over):
+    """hmsg_nav_room_doors: passable as nav_route makes it, the labels, the doors, in one call -> nav_doors' dict plus label int32
+    [rows, cols] and passable u8 [rows, cols]"""
+    L = lib_ or lib()
+    prm = params if params is not None else route_params(L, **over)
+    m, H, W, dev = _nav_image(main_free_map, np.uint8)
+    off, rc = _nav_seed_sets(seed_sets)
+    n = len(off) - 1
+    buf = _nav_buf(dev)
+    label, passable = buf((H, W), np.int32), buf((H, W), np.uint8)
+    call = lambda out: L.c.hmsg_nav_room_doors(_nav_dev_id(dev, device_id), H, W, _ptr(m), C.byref(prm), n, _ptr(off), _ptr(rc) if len(rc) else None,
+                                               _ptr(label), _ptr(passable), C.byref(out))
+    res = _nav_door_call(call, "hmsg_nav_room_doors", buf, H, W, max(n, 0), want_other, want_adjacency and 0 <= n <= 4096)
+    res.update(label=label, passable=passable)
     return res
 
 

@@ -28,9 +28,6 @@
 
 #include <climits>
 
-#define NAVR_SIDE (NAVR_TILE + 2)
-#define NAVR_LD 67                       // LDS row stride of the field tile in words (odd: see above)
-#define NAVR_PLD 68                      // ... and of the passable bytes
 #define NAVR_MAX_CELLS (1ll << 28)
 #define NAVR_CLAMP (1ll << 20)
 #define NAVR_NONE HMSG_NAV_UNREACHED
@@ -261,6 +258,7 @@ thread_local int g_navr_rounds = 0, g_navr_trips = 0;       // what hmsg_test_na
 }  // namespace
 
 void navr_last_reset() { g_navr_rounds = g_navr_trips = 0; }
+void navr_last_get(int* rounds, int* trips) { *rounds = g_navr_rounds, *trips = g_navr_trips; }
 void navr_check(int32_t rows, int32_t cols, const hmsg_route_params& p, const char* fn) {
     const std::string f = fn;
     HMSG_REQUIRE(rows >= 1 && cols >= 1, HMSG_ERR_INVALID, f + ": rows and cols must be at least 1");
@@ -288,9 +286,8 @@ void navr_relax_round(hipStream_t s, int rows, int cols, const unsigned char* d_
     else
         hipLaunchKernelGGL(k_navr_relax<false>, grid, dim3(NAVR_T), 0, s, rows, cols, d_pass, p.w_straight, p.w_diag, d_field, d_act, round, d_changed);
 }
-// rounds until no tile is stamped; act: i32 [nf][tiles], stamped 1 where a tile starts
-void navr_relax(hipStream_t s, int rows, int cols, const unsigned char* d_pass, const hmsg_route_params& p, bool corner, int nf, int* d_field,
-                int* d_act) {
+// rounds in growing batches until the last round of a batch changed nothing (hmsg_navroute_dev.h)
+void navr_rounds(hipStream_t s, const navr_round_fn& enqueue) {
     constexpr int MAXB = 32;
     DevBuf<unsigned> chg;
     chg.alloc(MAXB);
@@ -298,7 +295,7 @@ void navr_relax(hipStream_t s, int rows, int cols, const unsigned char* d_pass, 
     int round = 1, batch = 4;
     for (;;) {
         HIP_TRY(hipMemsetAsync(chg.p, 0, sizeof(unsigned) * (size_t)batch, s));
-        for (int b = 0; b < batch; ++b) navr_relax_round(s, rows, cols, d_pass, p, corner, nf, d_field, d_act, round + b, chg.p + b);
+        for (int b = 0; b < batch; ++b) enqueue(round + b, chg.p + b);
         HMSG_CHECK_LAUNCH();
         HIP_TRY(hipMemcpyAsync(h, chg.p, sizeof(unsigned) * (size_t)batch, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
@@ -309,6 +306,11 @@ void navr_relax(hipStream_t s, int rows, int cols, const unsigned char* d_pass, 
         batch = std::min(batch * 2, MAXB);
     }
 }
+// rounds until no tile is stamped; act: i32 [nf][tiles], stamped 1 where a tile starts
+void navr_relax(hipStream_t s, int rows, int cols, const unsigned char* d_pass, const hmsg_route_params& p, bool corner, int nf, int* d_field,
+                int* d_act) {
+    navr_rounds(s, [&](int round, unsigned* d_changed) { navr_relax_round(s, rows, cols, d_pass, p, corner, nf, d_field, d_act, round, d_changed); });
+}
 
 void navr_fill_dev(hipStream_t s, int* d_p, long long n, int v) {
     if (n <= 0) return;
@@ -317,7 +319,6 @@ void navr_fill_dev(hipStream_t s, int* d_p, long long n, int v) {
 void navr_scan_dev(hipStream_t s, long long n, const long long* d_cnt, long long* d_off) {
     hipLaunchKernelGGL(k_navr_scan, dim3(1), dim3(64), 0, s, n, d_cnt, d_off);
 }
-namespace {
 // d_fields i32 [nf][rows][cols] from the sources src_rc[src_off[f] .. src_off[f + 1]) (device memory, cells outside the image skipped)
 void navr_fields_dev(hipStream_t s, int rows, int cols, const unsigned char* d_pass, const hmsg_route_params& p, long long nf_all,
                      const long long* d_src_off, const int* d_src_rc, long long max_sources, int* d_fields, unsigned long long* d_n_reached) {
@@ -342,6 +343,7 @@ void navr_fields_dev(hipStream_t s, int rows, int cols, const unsigned char* d_p
         }
     }
 }
+namespace {
 
 void navr_clearance_dev(hipStream_t s, int rows, int cols, const unsigned char* d_mask, const hmsg_route_params& p, int* d_clr) {
     const int HW = rows * cols, ntiles = (int)(cdiv((size_t)cols, NAVR_TILE) * cdiv((size_t)rows, NAVR_TILE));

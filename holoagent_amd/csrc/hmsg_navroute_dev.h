@@ -7,6 +7,9 @@
 
 #define NAVR_T 256                       // threads of a workgroup of the routing kernels
 #define NAVR_TILE 64                     // the side of a tile of the relaxation: a stamp in `act` speaks of one tile
+#define NAVR_SIDE (NAVR_TILE + 2)        // ... with its one-cell halo
+#define NAVR_LD 67                       // LDS row stride of a tile of int32 in words (odd: 64 lanes of a sweep hit 64 banks)
+#define NAVR_PLD 68                      // ... and of the passable bytes
 
 // the cells of the goals (d_goal, i32 [n][2]) among the reached cells of d_field on d_pass: d_cell i32 [n][2], (-1, -1) for none;
 // d_d2 i64 [n] or nullptr.  All device memory, all work on s.
@@ -36,3 +39,14 @@ void navr_fill_dev(hipStream_t s, int* d_p, long long n, int v);
 // one wave: d_off [n + 1] = the exclusive scan of d_cnt [n] and the sum
 void navr_scan_dev(hipStream_t s, long long n, const long long* d_cnt, long long* d_off);
 [[noreturn]] void navr_throw_short(const char* fn, long long total, long long capacity);
+
+// What hmsg_navrooms.hip (N11) shares with hmsg_navroute.hip: the fields themselves and the loop of rounds.  navr_fields_dev makes
+// d_fields i32 [nf][rows][cols] from the sources d_src_rc[d_src_off[f] .. d_src_off[f + 1]) (device memory; max_sources: the most
+// of one field; d_n_reached u64 [nf] or nullptr).  navr_rounds calls enqueue(round, d_changed) for round 1, 2, ... in batches of 4,
+// 8, 16, then 32 rounds, reads the batch's counters back once and ends when the last round of a batch left its counter 0; it counts
+// rounds and round trips as navr_relax does (which is navr_rounds over navr_relax_round).  navr_last_get reads the two counts.
+using navr_round_fn = std::function<void(int round, unsigned* d_changed)>;
+void navr_rounds(hipStream_t s, const navr_round_fn& enqueue);
+void navr_last_get(int* rounds, int* trips);
+void navr_fields_dev(hipStream_t s, int rows, int cols, const unsigned char* d_pass, const hmsg_route_params& p, long long nf_all,
+                     const long long* d_src_off, const int* d_src_rc, long long max_sources, int* d_fields, unsigned long long* d_n_reached);

@@ -30,6 +30,7 @@ from scipy.ndimage import gaussian_filter1d
 from scipy.signal import find_peaks
 from scipy.spatial import cKDTree
 
+from . import _lib
 from . import rle as _rle
 from ._lib import HmsgLib, NodeIndex, Scene, lib as _default_lib
 
@@ -1481,6 +1482,87 @@ class Graph:
             nothing_reached = nav.last_route["start_cell"] == (-1, -1)
             for k, r in zip(here, routes):
                 out[k].update(r, reason=None if r["reachable"] else ("unreachable" if nothing_reached else "no view"))
+        return out
+
+    # ------------------------------------------------------------------ N11: rooms on the free map (no counterpart in the reference)
+    def _floor_rooms(self, floor_id):
+        fid = str(self.floors[int(floor_id)].floor_id)
+        return [r for r in self.rooms if str(getattr(r, "floor_id", None)) == fid]
+
+    def room_map(self, floor_id, min_clearance=0.25, poses_list=None):
+        """The rooms of storey `floor_id` laid over its free map (include/hmsg.h: hmsg_nav_room_doors, G1 and G2): int32 [rows,
+        cols], for every cell that has min_clearance metres of free space the index, in the storey's rooms in self.rooms' order,
+        of the room whose vertices are nearest by the walk; -1 where no room reaches.  Where the storey's maps are."""
+        return self.floor_navigation(floor_id, poses_list).room_map(self._floor_rooms(floor_id), min_clearance_m=min_clearance)
+
+    def room_doors(self, floor_id, min_clearance=0.25, min_cells=1, poses_list=None):
+        """The doors between the rooms of a storey (D1 to D4): NavigationGraph.doors' dicts in the table's order with `rooms` as
+        the pair of room ids and `room_indices` as the pair of indices room_map uses; doors of fewer than min_cells cells are left
+        out."""
+        rooms = self._floor_rooms(floor_id)
+        out = []
+        for d in self.floor_navigation(floor_id, poses_list).doors(rooms, min_clearance_m=min_clearance):
+            if d["n_cells"] >= min_cells:
+                p, q = d["rooms"]
+                out.append(dict(d, rooms=(rooms[p].room_id, rooms[q].room_id), room_indices=(p, q)))
+        return out
+
+    def room_graph(self, floor_id, min_clearance=0.25, min_cells=1, walks=False, poses_list=None):
+        """The rooms of a storey as a networkx graph: a node per room id (with `name` and `index`), an edge per pair of rooms that
+        share a door, carrying `doors` (room_doors' dicts, each with its `index` among the storey's doors) and `n_doors`.  walks:
+        the walk in metres between the middles of all doors of the storey (hmsg_nav_distance_fields, one field per door) as
+        G.graph["walk_m"] [n][n] (None: no way), and per edge `walk_m`, the rows and columns of its own doors."""
+        import networkx as nx
+        rooms = self._floor_rooms(floor_id)
+        doors = self.room_doors(floor_id, min_clearance, min_cells, poses_list)
+        G = nx.Graph()
+        for k, r in enumerate(rooms):
+            G.add_node(r.room_id, name=getattr(r, "name", None), index=k)
+        for k, d in enumerate(doors):
+            d["index"] = k
+            a, b = d["rooms"]
+            if not G.has_edge(a, b):
+                G.add_edge(a, b, doors=[], n_doors=0)
+            G.edges[a, b]["doors"].append(d)
+            G.edges[a, b]["n_doors"] += 1
+        G.graph["doors"] = doors
+        if walks:
+            nav = self.floor_navigation(floor_id, poses_list)
+            mids = np.array([d["middle_cell"] for d in doors], np.int32).reshape(-1, 2)
+            walk = []
+            if len(doors):
+                fields, _ = _lib.nav_distance_fields(nav.passable_map(min_clearance), [m.reshape(1, 2) for m in mids], lib_=self.L)
+                if hasattr(fields, "cpu"):
+                    import torch
+                    ix = torch.as_tensor(mids, dtype=torch.long, device=fields.device)
+                    at = fields[:, ix[:, 0], ix[:, 1]].cpu().numpy()
+                else:
+                    at = fields[:, mids[:, 0], mids[:, 1]]
+                walk = [[None if v == _lib.NAV_UNREACHED else float(v) * nav.cell_size / 5 for v in row] for row in at]
+            G.graph["walk_m"] = walk
+            for a, b in G.edges:
+                ix = [d["index"] for d in G.edges[a, b]["doors"]]
+                G.edges[a, b]["walk_m"] = [[walk[i][j] for j in ix] for i in ix]
+        return G
+
+    def rooms_on_route(self, route, min_clearance=0.25, poses_list=None):
+        """The rooms a route passes through (L1): `route` is one dict of route_to_objects or view_routes_to_objects, made with the
+        same min_clearance.  Per leg a dict with `room_id` (None off every room), the room's `name` when it has one, `first` (the
+        index in route["polyline"] of the leg's first point), `n_points` and `length_m`, the walk of the moves that end in the
+        leg's cells (the legs' lengths sum to the route's)."""
+        f = int(route["floor_id"])
+        nav, rooms = self.floor_navigation(f, poses_list), self._floor_rooms(f)
+        if len(route["polyline"]) == 0:
+            return []
+        cells = nav.cells_of(route["polyline"])
+        step = np.where((np.diff(cells, axis=0) != 0).all(axis=1), 7.0, 5.0) * nav.cell_size / 5
+        upto = np.concatenate([[0.0], np.cumsum(step)])                    # the walk up to each point
+        out = []
+        for leg in nav.rooms_along(cells, rooms, min_clearance_m=min_clearance):
+            a, b = leg["first"], leg["first"] + leg["n_cells"]
+            room = rooms[leg["room"]] if leg["room"] >= 0 else None
+            out.append(dict(room_id=room.room_id if room is not None else None, name=getattr(room, "name", None), first=a, n_points=b - a,
+                            length_m=float(upto[b - 1] - (upto[a - 1] if a else 0.0))))
         return out
 
     # ------------------------------------------------------------------ N9: routes across storeys (no counterpart in the reference)

@@ -17,7 +17,8 @@ exact integer distance fields on main_free_map, the nearest reachable free cell 
 N8: sight_blocking_map, viewpoints and route_to_view stand the robot on a reached cell from which the goal is in sight on the
 obstacle map, not on the nearest one whatever lies between.  N10: height_map is the storey's exact integer height map;
 viewpoints and route_to_view with sight="heights" judge sight on it from the camera's height, and max_step_m keeps routes off
-cells that the flat maps leave free under furniture (walkable_map)."""
+cells that the flat maps leave free under furniture (walkable_map).  N11: room_seeds, room_map, doors and rooms_along lay a list
+of rooms over the free map -- the room of every reached cell, the doors between rooms with their cells, the rooms along a way."""
 import json
 import os
 
@@ -203,6 +204,63 @@ class NavigationGraph:
                             snap_m=float(np.sqrt(float(r["goal_d2"][k]))) * self.cell_size if ok else None,
                             polyline=world(r["path_rc"][r["path_off"][k]:r["path_off"][k + 1]])))
         return out
+
+    # ---- rooms on the main free map (include/hmsg.h, N11: the rules G1, G2, D1 to D4, L1; no counterpart in the reference)
+    def room_seeds(self, rooms):
+        """per room (anything with `vertices`, the (x, z) pairs of Room.vertices) the cells of its vertices by R6, int32 [k, 2];
+        vertices outside the grid are left out, a room without vertices has no seed"""
+        rows, cols = int(self.grid_size[1]), int(self.grid_size[0])
+        out = []
+        for room in rooms:
+            v = np.asarray(getattr(room, "vertices", room), np.float64).reshape(-1, 2)
+            rc = self.cells_of(np.stack([v[:, 0], np.zeros(len(v)), v[:, 1]], axis=1)) if len(v) else np.zeros((0, 2), np.int32)
+            ok = (rc[:, 0] >= 0) & (rc[:, 0] < rows) & (rc[:, 1] >= 0) & (rc[:, 1] < cols)
+            out.append(np.ascontiguousarray(rc[ok]))
+        return out
+
+    def _room_doors(self, rooms, min_clearance_m, max_step_m, weights):
+        """hmsg_nav_room_doors on walkable_map(max_step_m), kept until the rooms or the parameters change"""
+        assert self.maps is not None, "get_main_free_map makes the maps"
+        seeds = self.room_seeds(rooms)
+        key = (float(min_clearance_m), max_step_m, tuple(sorted(weights.items())), tuple(s.tobytes() for s in seeds))
+        if getattr(self, "_rooms_key", None) != key:
+            ws = int(weights.get("w_straight", 5))
+            self._rooms = _lib.nav_room_doors(self.walkable_map(max_step_m), seeds, lib_=self.L, device_id=self.device_id,
+                                              min_clearance=self.clearance_units(min_clearance_m, ws), **weights)
+            self._rooms_key = key
+        return self._rooms
+
+    def room_map(self, rooms, min_clearance_m=0.0, max_step_m=None, **weights):
+        """G2: int32 [rows, cols], for every cell of passable_map(min_clearance_m, max_step_m) the index in `rooms` of the room whose
+        seeds are nearest by the walk (of equal walks the smaller index), -1 where no seed reaches; where the maps are"""
+        return self._room_doors(rooms, min_clearance_m, max_step_m, weights)["label"]
+
+    def doors(self, rooms, min_clearance_m=0.0, max_step_m=None, **weights):
+        """D1 to D4: the doors between the rooms in the table's order, each a dict with `rooms` (p, q) as indices in `rooms`, its
+        `cells` int32 [n, 2] in row-major order, `n_cells`, the `middle_cell` (row, col) at position (n - 1) // 2 and `middle`, that
+        cell's centre in world coordinates (y = pcd_min[1])"""
+        t = self._room_doors(rooms, min_clearance_m, max_step_m, weights)
+        np_ = lambda v: v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)
+        pair, off, rc = np_(t["door_pair"]), np_(t["door_off"]), np_(t["door_rc"])
+        out = []
+        for k in range(len(pair)):
+            cells = rc[off[k]:off[k + 1]]
+            row, col = (int(v) for v in cells[(len(cells) - 1) // 2])
+            out.append(dict(rooms=(int(pair[k, 0]), int(pair[k, 1])), cells=cells, n_cells=len(cells), middle_cell=(row, col),
+                            middle=np.array([(col + 0.5) * self.cell_size + self.pcd_min[0], self.pcd_min[1],
+                                             (row + 0.5) * self.cell_size + self.pcd_min[2]])))
+        return out
+
+    def rooms_along(self, path_cells, rooms=None, min_clearance_m=0.0, max_step_m=None, **weights):
+        """L1: the legs of one way (cells int32 [k, 2]) on the room map made last, or on room_map(rooms, ...): a list of dicts with
+        `room` (the index, -1 off every room), `first` (the index of the leg's first cell) and `n_cells`"""
+        t = self._room_doors(rooms, min_clearance_m, max_step_m, weights) if rooms is not None else getattr(self, "_rooms", None)
+        assert t is not None, "room_map or doors makes the room map"
+        cells = self.cells_of(path_cells) if len(path_cells) else np.zeros((0, 2), np.int32)
+        _, room, first = (v.cpu().numpy() if hasattr(v, "cpu") else v for v in
+                          _lib.nav_path_rooms(t["label"], np.array([0, len(cells)], np.int64), cells, lib_=self.L, device_id=self.device_id))
+        ends = list(first[1:]) + [len(cells)]
+        return [dict(room=int(r), first=int(a), n_cells=int(b - a)) for r, a, b in zip(room, first, ends)]
 
     # ---- viewpoints (include/hmsg.h, N8: the rules V1 to V5; no counterpart in the reference)
     def sight_blocking_map(self):

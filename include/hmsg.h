@@ -1512,6 +1512,66 @@ int hmsg_nav_view_route_h(int32_t device_id, int32_t rows, int32_t cols, const u
                           int64_t n_goals, const int32_t* goal_rc, const int32_t* goal_h, const int64_t* goal_r2 /* or NULL */,
                           hmsg_nav_routes* out, int32_t* n_visible /* i32 [n_goals], may be NULL */);
 
+/* ---- N11: rooms on a floor's free map (csrc/hmsg_navrooms.hip): every reached cell gets a room, the cells where two rooms touch
+ * become doors, a way is cut into legs by room.  The scene graph has rooms as clouds and (x, z) vertices, N6 to N10 have a map
+ * whose cells belong to no room; the reference joins the two nowhere (its graph has no room-room edge, its navigation graph knows
+ * no rooms), so the rules are this library's.  Images, cells, weights and memory conventions are N7's; R1 to R6 hold.  passable is
+ * u8 [rows][cols].  The rooms' seeds are cells seed_rc i32 [sum][2] with the CSR offsets seed_off i64 [n_rooms + 1]: room r is
+ * seeded by seed_rc[seed_off[r] .. seed_off[r + 1]).  The Python layer makes the seeds from room.vertices by R6.  All of it is
+ * integer work: every output has one right answer.  The rules:
+ *  G1. Room field: dist is R2's field from the union of all rooms' seed cells.  A seed on a cell that is not passable is no
+ *      source.  Duplicate seeds are fine, within a room and between rooms.
+ *  G2. Label: label[c] is the least room index r such that R2's field from room r's seeds alone equals dist[c] at c; -1 where
+ *      dist[c] is HMSG_NAV_UNREACHED, which includes every cell that is not passable.  Labels are int32.  A room without a passable
+ *      seed labels no cell.  n_cells[r] (int64) counts the cells of label r.  Equivalent form: the label of a source cell is the
+ *      least room that seeds it, and label[c] = min label[n] over R1-legal moves n -> c with dist[n] + w == dist[c].  (Min over
+ *      tight predecessors, by induction on dist, is the least room that has a shortest walk to c.)
+ *  D1. Border move: an R1-legal move between cells a and b with label[a] >= 0, label[b] >= 0 and label[a] != label[b].  The
+ *      corner rule applies: [[1, 0], [0, 1]] is no contact.
+ *  D2. Threshold cell: other[a] is the least label[b] over a's border moves, -1 where a has none; int32 [rows][cols].  A threshold
+ *      cell has other >= 0; its pair is (min(label, other), max(label, other)).  Every threshold cell has exactly one pair.
+ *  D3. Door: a connected component of the threshold cells of equal pair, by the plain 8-neighbourhood inside the image (no corner
+ *      rule here: scipy.ndimage.label with a 3 x 3 structure restates it).
+ *  D4. Door table: the doors sorted by (p, q, least row-major index of the door's cells).  door_pair i32 [n_doors][2]; door_off
+ *      i64 [n_doors + 1]; door_rc i32 [n_door_cells][2], each door's cells in ascending row-major order.  A door's middle is the
+ *      cell at position floor((n - 1) / 2) of its list; the Python layer takes it.  adjacency i32 [n_rooms][n_rooms], optional:
+ *      the number of doors of each pair, symmetric with a zero diagonal.
+ *  L1. Legs of a way: for a path list as hmsg_nav_paths gives it (path_off, path_rc), the run-length of label along each path:
+ *      leg_off i64 [n_paths + 1], leg_room i32, leg_first i64 (the index within its path of a leg's first cell).  A path cell
+ *      outside the image has label -1.  An empty path has no leg.
+ * hmsg_nav_room_doors is the composition and only that: passable as hmsg_nav_route makes it (the mask where clearance >=
+ * min_clearance), the labels, the doors, with nothing leaving the device between them.  Every array may be host or device memory;
+ * structs and counts are host memory; seed_off, seed_rc and path_off are read and checked by the host before anything runs.  Any
+ * pointer of hmsg_nav_door_table may be NULL.  A list that is too short behaves as path_rc does in N7: everything else is written,
+ * the list is not, the counts say what is needed (HMSG_ERR_INVALID); door_capacity speaks for door_pair and door_off, cell_capacity
+ * for door_rc, capacity for leg_room and leg_first (which come together or not at all).  dist, n_cells, leg_off and passable (of
+ * hmsg_nav_room_doors) may be NULL.
+ * Refusals (HMSG_ERR_INVALID unless said): a null required pointer; rows or cols < 1; n_rooms < 0 or n_paths < 0; a negative
+ * capacity; a decreasing offset array; a seed outside the image; a label >= n_rooms or < -1 in the label image handed to
+ * hmsg_nav_doors (checked on the device, reported after the call); N7's refusals of the weights and min_clearance;
+ * HMSG_ERR_UNSUPPORTED for N7's size limits and for adjacency with n_rooms > 4096. */
+typedef struct hmsg_nav_door_table {
+    int32_t* door_pair;           /* i32 [door_capacity][2] */
+    int64_t* door_off;            /* i64 [door_capacity + 1] */
+    int32_t* door_rc;             /* i32 [cell_capacity][2] */
+    int32_t* other;               /* i32 [rows][cols] */
+    int32_t* adjacency;           /* i32 [n_rooms][n_rooms] */
+    int64_t  door_capacity, cell_capacity;
+    /* out */
+    int64_t  n_doors, n_door_cells;
+} hmsg_nav_door_table;
+int hmsg_nav_room_labels(int32_t device_id, int32_t rows, int32_t cols, const uint8_t* passable, const hmsg_route_params* prm, int32_t n_rooms,
+                         const int64_t* seed_off /* [n_rooms + 1] */, const int32_t* seed_rc, int32_t* label /* [rows][cols] */,
+                         int32_t* dist /* [rows][cols] or NULL */, int64_t* n_cells /* [n_rooms] or NULL */);
+int hmsg_nav_doors(int32_t device_id, int32_t rows, int32_t cols, const uint8_t* passable, const int32_t* label, int32_t n_rooms,
+                   hmsg_nav_door_table* out);
+int hmsg_nav_path_rooms(int32_t device_id, int32_t rows, int32_t cols, const int32_t* label, int64_t n_paths, const int64_t* path_off,
+                        const int32_t* path_rc, int64_t* leg_off /* [n_paths + 1] */, int32_t* leg_room, int64_t* leg_first, int64_t capacity,
+                        int64_t* n_needed);
+int hmsg_nav_room_doors(int32_t device_id, int32_t rows, int32_t cols, const uint8_t* main_free_map, const hmsg_route_params* prm,
+                        int32_t n_rooms, const int64_t* seed_off, const int32_t* seed_rc, int32_t* label, uint8_t* passable /* or NULL */,
+                        hmsg_nav_door_table* out);
+
 
 #ifdef __cplusplus
 }

@@ -130,6 +130,10 @@ int hmsg_test_nav_route_last(int32_t* rounds, int32_t* round_trips);
  * (one read-back per batch of rounds), of this thread's last hmsg_nav_building_fields / hmsg_nav_building_route call.  Either
  * pointer may be NULL. */
 int hmsg_test_nav_building_last(int32_t* rounds, int32_t* round_trips);
+/* the rounds that changed a tile and the host round trips (one read-back per batch of rounds) of this thread's last
+ * hmsg_nav_room_labels / hmsg_nav_room_doors call: the field's and the labels' rounds together (and the clearance's, where
+ * hmsg_nav_room_doors computes one).  The doors' three read-backs are not counted.  Either pointer may be NULL. */
+int hmsg_test_nav_rooms_last(int32_t* rounds, int32_t* round_trips);
 /* the LDS layout of hmsg_nav_viewpoints_h's kernel (N10): force_ld 16 or 17 forces the row stride of its two bitmaps (17 only
  * where the device's limit per workgroup admits it), 0 leaves the choice to that limit; *ld_in_use is what runs then, *lds_limit
  * the limit the device reports.  Either pointer may be NULL.  The setting is the process's, not the thread's. */
